@@ -1,6 +1,15 @@
 """bench.py -- publishes matched/sec at 1M wildcard subscriptions (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline and prints the
+result line (metric, value, unit, ms_per_step, the timed kernel's roofline from
+the steps' own events).  --dump-outputs DIR writes what the last timed step
+computed (dump_outputs below) as DIR/<name>.npy; the workload is seeded, so two
+builds can be compared file by file.  Everything else described below -- the
+fresh-batch, dense-CSR, two-in-flight, latency, per-publish, end-to-end, CPU,
+C1 and C5 legs and the self-checks -- runs only with --full.  (The explicit
+--workload lines and the in-process --gpus N group keep their own legs.)
 
 Workload: 1,000,000 distinct wildcard filters
 (depth <= 7, V = 1024, Zipf 1.1, p+ = 0.15, p# = 0.25, seed 2) compiled into
@@ -274,6 +283,45 @@ def c5_selfcheck(eng, b, pubs, derived, allf, live, added) -> dict:
             "mismatches": [ts[i].decode("latin-1")[:80] for i in bad[:3]],
             "checker": "oracle/c5_checker.py FinalSnapshot on the last step's snapshot",
             "seconds": round(time.time() - t0, 2)}
+
+
+DUMP_ROWS = 1 << 17            # rows sampled by --dump-outputs
+DUMP_MAX_BYTES = 64_000_000    # all files of one dump together
+
+
+def dump_outputs(path, b, n, matches, seed=0):
+    """--dump-outputs: what the last timed step left for a caller of the timed
+    path (the walk's rows of batch b, waited), as .npy files under path:
+      row_counts         float32[n]   every topic's match count (tm_batch_rows;
+                                      left out if it would take over 2/3 of the limit)
+      totals             float64[2]   topics, matches of the launch
+      sample_rows        float64[k]   a fixed, seeded, ascending sample of topics
+      sample_row_offsets float64[k+1] CSR offsets of the sampled rows
+      sample_filter_ids  float64[m]   their sorted filter ids (tm_batch_sample)
+    The sample is cut (from its end) to keep the files under DUMP_MAX_BYTES."""
+    from emqx_amd.engine import _d2h
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_MAX_BYTES - 4096             # (.npy headers)
+    files = {"totals": np.array([n, matches], np.float64)}
+    left -= files["totals"].nbytes
+    if 4 * n <= 2 * left // 3:
+        d_cnt = b.device_rows()[0]
+        cnt = np.zeros(n, np.uint32)
+        _d2h(cnt, d_cnt)
+        files["row_counts"] = cnt.astype(np.float32)     # exact: a row holds < 2^24 ids
+        left -= files["row_counts"].nbytes
+    k = min(n, DUMP_ROWS)
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.uint32)
+    offs, ids = b.sample(idx)
+    offs = offs.astype(np.int64)
+    keep = int(np.searchsorted(8 * (2 * np.arange(k + 1) + 1 + offs), left, side="right")) - 1
+    keep = max(0, min(k, keep))
+    files["sample_rows"] = idx[:keep].astype(np.float64)
+    files["sample_row_offsets"] = offs[:keep + 1].astype(np.float64)
+    files["sample_filter_ids"] = ids[:offs[keep]].astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[dump] {path}: " + ", ".join(f"{k_} {a.dtype}{list(a.shape)}" for k_, a in files.items()))
 
 
 def timed_steps(bs, steps, ms_match=None, ms_total=None):
@@ -1190,8 +1238,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--topics", type=int, default=10_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="C2: after the headline's timed steps also run every other leg and self-check of the "
+                         "line (parity sample, fresh batches, dense CSR, two in flight, latency sweeps, "
+                         "per-publish calls, end to end, CPU baseline, C1, C5); without it only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="C2: write the last timed step's result (row counts, a seeded sample of rows) as "
+                         "DIR/<name>.npy after the timed steps")
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-c5", action="store_true", help="N = 1: skip the C5 legs of the default line")
+    ap.add_argument("--no-c5", action="store_true", help="N = 1: skip the C5 legs of the --full line")
     ap.add_argument("--inflight", type=int, default=1,
                     help="C2: batches in flight in the headline steps, each on its own stream (1 = one "
                          "batch on the engine stream: walk events and rocprof durations stay un-overlapped)")
@@ -1213,8 +1268,12 @@ def main():
                     help="comma list of HIP devices: replicas of the in-process group (--gpus N without torchrun), "
                          "or the device of each local rank; default 0..N-1 (e.g. 0,0 rehearses 2 on one GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     ws, rank, local = dist_env()
+    if args.dump_outputs and (args.workload != "c2" or (ws == 1 and args.gpus > 1)):
+        ap.error("--dump-outputs writes the C2 headline's rows (one engine per process)")
     devs = [int(x) for x in args.devices.split(",")] if args.devices else None
     if devs and ws > 1:
         local = devs[local]
@@ -1300,11 +1359,21 @@ def main():
     n = len(topics)
     value = ws * n * args.steps / elapsed
     ms_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs:
+        # the rows of the last timed step (the batch it launched, before any
+        # other leg launches it again); every rank its own batch
+        last = bs[(args.steps - 1) % nb]
+        dump_outputs(args.dump_outputs if ws == 1 else os.path.join(args.dump_outputs, f"rank{rank}"),
+                     last, n, last.stats()["matches"])
+
+    # everything below the headline runs only on request: --full (every leg
+    # and check), --profile (the device legs the profiler passes were taken with)
+    legs = args.full and not args.profile
     # the timed launch checks itself (oracle as the checker, outside the timed
     # region): N = 1 against the CPU restatement; N > 1 below against rank 0's
     # replica on device 0
     c2_check = None
-    if ws == 1 and not args.profile:
+    if ws == 1 and legs:
         c2_check = c2_selfcheck(eng, b, filters, topics)
         if not c2_check["parity_sample_ok"]:
             log(f"[rank 0] C2 PARITY SAMPLE FAILED: {c2_check}")
@@ -1313,11 +1382,12 @@ def main():
     # step is the whole device pipeline of a never-seen batch (tokenise + walk
     # + CSR); reported beside the headline, which reuses the tokens
     fresh_ms, fresh_tok = [], []
-    for _ in range(max(3, min(args.steps, 10))):
-        b.retokenize().launch().wait()
-        s = b.stats()
-        fresh_ms.append(s["ms_tokenize"] + s["ms_total"])
-        fresh_tok.append(s["ms_tokenize"])
+    if args.full or args.profile:
+        for _ in range(max(3, min(args.steps, 10))):
+            b.retokenize().launch().wait()
+            s = b.stats()
+            fresh_ms.append(s["ms_tokenize"] + s["ms_total"])
+            fresh_tok.append(s["ms_tokenize"])
 
     # roofline of the dominant kernel (tm_match_tiles): algorithmic bytes per launch
     alg_bytes = (ALG_BYTES_PER_VISIT * (st["visits"] + st["hash_hits"]) + 4 * st["words"]
@@ -1355,12 +1425,13 @@ def main():
                      "iterations_per_tile": st["iterations"] / max(1, -(-n // 64)),
                      "probes_per_iteration": st["probes"] / max(1, st["iterations"])},
         "pipeline_ms": float(np.mean(ms_total)),
-        "pipeline_fresh_ms": float(np.median(fresh_ms)),
-        "tokenize_ms": float(np.median(fresh_tok)),
-        "fresh_publishes_per_s": ws * n / (1e-3 * float(np.median(fresh_ms))),
         "matches_per_step": st["matches"],
         "slow_path_topics": st["slow_topics"],
     }
+    if fresh_ms:
+        out["pipeline_fresh_ms"] = float(np.median(fresh_ms))
+        out["tokenize_ms"] = float(np.median(fresh_tok))
+        out["fresh_publishes_per_s"] = ws * n / (1e-3 * float(np.median(fresh_ms)))
     if c2_check is not None:
         out["selfcheck"] = c2_check
         out["parity_sample_ok"] = c2_check["parity_sample_ok"]
@@ -1368,7 +1439,7 @@ def main():
     # the same steps with the dense CSR built after every wait (scan + copy
     # of every row into topic order, tm_batch_device_csr): what a consumer
     # that indexes the result by offsets pays per batch
-    if nb == 1:
+    if nb == 1 and (args.full or args.profile):
         csr_ms = []
         t2 = time.perf_counter()
         for _ in range(args.steps):
@@ -1381,7 +1452,7 @@ def main():
         out["dense_csr"] = {"publishes_per_s": ws * n * args.steps / e2, "ms_per_step": 1e3 * e2 / args.steps,
                             "csr_ms": float(np.mean(csr_ms))}
 
-    if nb == 1 and not args.profile:
+    if nb == 1 and legs:
         # two batches in flight on streams of their own (TM_BATCH_STREAM): one
         # batch's CSR pass and walk tail overlap the next one's walk.  Beside
         # the headline, which keeps one batch so its walk events and rocprof
@@ -1402,18 +1473,17 @@ def main():
             x.free()
 
     if ws > 1:
+        out["devices"] = [int(x) for x in sync.allgather(str(local))]
+    if ws > 1 and legs:
         # self-check of the multi-GPU run: every rank's sampled rows (as filter
         # bytes) must equal what rank 0's replica on device 0 returns for the
         # same publishes (emqx_amd/selfcheck.py)
-        out["devices"] = [int(x) for x in sync.allgather(str(local))]
         out["selfcheck"] = replica_selfcheck(eng, b, topics, sync, rank, f"rank {rank} (device {local})")
         out["parity_sample_ok"] = out["selfcheck"]["parity_sample_ok"]
         if rank == 0 and not out["parity_sample_ok"]:
             log(f"[rank 0] PARITY SAMPLE FAILED: {out['selfcheck']}")
 
-    if args.profile:
-        args.no_cpu = True
-    if rank == 0 and not args.profile:
+    if rank == 0 and legs:
         # p99 batch latency (device-resident batches, launch -> results in HBM)
         # at B = 4,096 / 65,536 / 1,048,576; the headline
         # p99_batch_ms is B = 65,536
@@ -1466,7 +1536,7 @@ def main():
     for x in bs:
         x.free()
 
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and legs and not args.no_cpu:
         # north_star: the CPU reference timed on this host's cores in the same
         # run at every N (rank 0, after the timed region; the other ranks are done)
         host = host_cpu_share()
@@ -1479,7 +1549,7 @@ def main():
             out["coalesce"]["sync_vs_cpu_port"] = out["coalesce"]["sync_calls_per_s"] / cv
         if ws == 1:
             out["c1"] = c1_leg(host, device=local)
-    if rank == 0 and ws == 1 and not args.profile and not args.no_c5:
+    if rank == 0 and ws == 1 and legs and not args.no_c5:
         # config C5 in the driver's line: K = 100, 10 and 1000 filters per hot
         # topic, 10k subscribe/unsubscribe deltas per step; each leg checks
         # its last step's batch against the oracle on that step's snapshot

@@ -4,7 +4,7 @@
 # gpurun_out/TAG/<i>_<kind>.{json,log,err} and a one-line summary per step.
 #
 #   tests [PYTEST ARGS]      pytest -m gpu over tests/ (e.g. "tests -k 'sample or c3'")
-#   bench [BENCH ARGS]       python bench.py ARGS -> the JSON line, summarised
+#   bench [BENCH ARGS]       python bench.py ARGS -> the JSON line, summarised (--full: every leg)
 #   prof [BENCH ARGS]        rocprofv3 --kernel-trace --stats of bench.py --profile ARGS
 #   pmc COUNTERS [ARGS]      one rocprofv3 --pmc pass (COUNTERS comma-free, '+'-joined)
 #   traffic c2|c4 [ARGS]     FETCH_SIZE + WRITE_SIZE passes -> $O/pmc_<workload>.json
