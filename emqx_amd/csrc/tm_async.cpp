@@ -54,8 +54,7 @@ void tm_engine::async_stop(Replica& R) {
         if (sl->ev_done) (void)hipEventDestroy(sl->ev_done);
         if (sl->h_in) (void)hipHostFree(sl->h_in);
         if (sl->h_bin) (void)hipHostFree(sl->h_bin);
-        for (AsyncSlot::GraphCache& gc : sl->gc)
-            if (gc.exec) (void)hipGraphExecDestroy(gc.exec);
+        for (GraphCache& gc : sl->gc) gc.reset();
         if (sl->h_rows) (void)hipHostFree(sl->h_rows);
         if (sl->h_out) (void)hipHostFree(sl->h_out);
         if (sl->h_flag) (void)hipHostFree(sl->h_flag);
@@ -251,18 +250,15 @@ int tm_engine::slot_launch(AsyncSlot* sl) {
         if ((rc = slot_export_args(sl, x, sl->bound))) return rc;
         x.d_n = reinterpret_cast<const uint32_t*>(d_bin);
         x.fixed_words = tm_batch::HDR_FIXED / 4;
-        b->tail_key.assign(sizeof x + sizeof(uint32_t*), 0);
-        memcpy(b->tail_key.data(), &x, sizeof x);
-        memcpy(b->tail_key.data() + sizeof x, &sl->d_flag, sizeof(uint32_t*));
-        b->tail = [this, sl, x](hipStream_t st) { return slot_tail(sl, x, st); };
-        AsyncSlot::GraphCache& gc = sl->gc[cls];
-        std::swap(b->gexec, gc.exec);
-        std::swap(b->gkey, gc.key);
-        rc = launch(b, false);
-        std::swap(b->gexec, gc.exec);
-        std::swap(b->gkey, gc.key);
-        if (rc) return rc;
-        if (!b->tail_done) HIP_OK(slot_tail(sl, x, S));
+        const struct {
+            ExportArgs x;
+            uint32_t* d_flag;
+        } tail_args{x, sl->d_flag};
+        static_assert(sizeof tail_args == sizeof x + sizeof(uint32_t*), "the tail's key has padding");
+        SlotTail tail{sl->gc[cls], {&tail_args, sizeof tail_args},
+                      [this, sl, x](hipStream_t st) { return slot_tail(sl, x, st); }};
+        if ((rc = launch(b, false, &tail))) return rc;
+        if (!tail.in_graph) HIP_OK(slot_tail(sl, x, S));
         HIP_OK(hipEventRecord(sl->ev_done, S));
         return TM_OK;
     }
@@ -276,7 +272,6 @@ int tm_engine::slot_launch(AsyncSlot* sl) {
     rc = dev_tok ? upload_packed(b, sl->h_in, n, nb)
                  : prepare(b, sl->h_in + head, reinterpret_cast<const uint64_t*>(sl->h_in), n);
     if (rc) return rc;
-    b->tail = nullptr;
     if ((rc = launch(b, false))) return rc;
     ExportArgs x{};
     if ((rc = slot_export_args(sl, x, n))) return rc;

@@ -609,14 +609,39 @@ hipError_t tm_engine::graph_replay(tm_batch* b, hipStream_t S) {
     hipError_t e;
     if (b->dedup_timed && (e = hipEventRecord(b->evd, S)) != hipSuccess) return e;
     if ((e = hipEventRecord(b->ev0, S)) != hipSuccess) return e;
-    if ((e = hipGraphLaunch(b->gexec, S)) != hipSuccess) return e;
+    if ((e = hipGraphLaunch(b->graph.exec, S)) != hipSuccess) return e;
     if ((e = hipEventRecord(b->ev1, S)) != hipSuccess) return e;
     if ((e = hipEventRecord(b->ev2, S)) != hipSuccess) return e;
     ++graph_launches;
     return hipSuccess;
 }
 
-int tm_engine::launch(tm_batch* b, bool csr) {
+// (the policy: tm_engine_impl.hpp)
+template <class Record>
+bool tm_engine::graph_ready(GraphCache& gc, bool& gbad, std::vector<uint8_t>& key, hipStream_t S, Record&& record) {
+    if (gc.exec && gc.key == key) return true;
+    if (gc.exec) (void)hipGraphExecDestroy(gc.exec);
+    gc.exec = nullptr;
+    if (gc.key == key) {   // the second launch with these arguments: capture them
+        hipGraph_t g = nullptr;
+        if (hipStreamBeginCapture(S, hipStreamCaptureModeRelaxed) == hipSuccess) {
+            const hipError_t e = record();
+            const hipError_t e2 = hipStreamEndCapture(S, &g);
+            if (e != hipSuccess || e2 != hipSuccess || !g ||
+                hipGraphInstantiate(&gc.exec, g, nullptr, nullptr, 0) != hipSuccess)
+                gc.exec = nullptr;
+            if (g) (void)hipGraphDestroy(g);
+        }
+        if (!gc.exec) {
+            (void)hipGetLastError();
+            gbad = true;   // the direct way from now on
+        }
+    }
+    gc.key.swap(key);
+    return gc.exec != nullptr;
+}
+
+int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     if (reps.empty()) return TM_ENODEV;
     int rc;
     Replica& R = *b->rep;
@@ -759,66 +784,50 @@ int tm_engine::launch(tm_batch* b, bool csr) {
         }
         if (cap && csr_too)   // (ev2 is recorded after the graph's launch)
             return hipMemcpyAsync(b->h_hdr, b->d_hdr, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S);
-        return csr_too ? enqueue_csr(b, s, S) : hipSuccess;
+        return csr_too ? enqueue_csr(b, S) : hipSuccess;
     };
+    // At most one of the three captured forms applies (graph_ready decides
+    // replay, capture or direct); grc 0: a graph holds the launch, 1: direct
     int grc = 1;
     if (graph) {   // a repeated tokenised batch: memset + walk + read-back replayed
-        grc = launch_graph(b, a, s, S);
-        if (grc != 1 && grc) return grc;
+        std::vector<uint8_t> key = graph_key({}, a, s);
+        auto record = [&] {
+            hipError_t e = hipMemsetAsync(b->d_hdr, 0, tm_batch::HDR_FIXED, S);
+            // timing events as external nodes: every replay re-records them
+            if (e == hipSuccess) e = launch_match(a, S, b->ev0, b->ev1, false, hipEventRecordExternal);
+            if (e == hipSuccess) e = enqueue_csr(b, S, hipEventRecordExternal);
+            return e;
+        };
+        if (graph_ready(b->graph, b->gbad, key, S, record)) {
+            HIP_OK(hipGraphLaunch(b->graph.exec, S));
+            ++graph_launches;
+            grc = 0;
+        }
     }
     bool csr_done = false;
     if (dedup_now && (rc = clear_dedup_table(b, S))) return rc;   // (outside the capture below)
     if (dgraph) {
         const DedupArgs d = dedup_args(b);
-        std::vector<uint8_t> key(sizeof t + sizeof ts + sizeof a + sizeof s + sizeof d);
-        uint8_t* k = key.data();
-        memcpy(k, &t, sizeof t); k += sizeof t;
-        memcpy(k, &ts, sizeof ts); k += sizeof ts;
-        memcpy(k, &a, sizeof a); k += sizeof a;
-        memcpy(k, &s, sizeof s); k += sizeof s;
-        memcpy(k, &d, sizeof d);
-        if (b->gexec && b->gkey == key) {
+        std::vector<uint8_t> key = graph_key({}, t, ts, a, s, d);
+        const std::vector<uint8_t>& old = b->graph.key;
+        if (kn.par_trace && !(b->graph.exec && old == key) && old.size() == key.size()) {
+            // which arguments changed (offsets per struct)
+            const size_t ends[5] = {sizeof t, sizeof t + sizeof ts, sizeof t + sizeof ts + sizeof a,
+                                    sizeof t + sizeof ts + sizeof a + sizeof s, key.size()};
+            const char* names[5] = {"tok", "tscan", "match", "scan", "dedup"};
+            fprintf(stderr, "[graph key miss]");
+            size_t st = 0;
+            for (int q = 0; q < 5; ++q) {
+                for (size_t i = st; i < ends[q]; i += 4)
+                    if (memcmp(&key[i], &old[i], std::min<size_t>(4, ends[q] - i)))
+                        fprintf(stderr, " %s+%zu", names[q], i - st);
+                st = ends[q];
+            }
+            fprintf(stderr, "\n");
+        }
+        if (graph_ready(b->graph, b->gbad, key, S, [&] { return enqueue(true, true); })) {
             HIP_OK(graph_replay(b, S));
             grc = 0;
-        } else {
-            if (kn.par_trace && b->gkey.size() == key.size()) {   // which arguments changed (offsets per struct)
-                const size_t ends[5] = {sizeof t, sizeof t + sizeof ts, sizeof t + sizeof ts + sizeof a,
-                                        sizeof t + sizeof ts + sizeof a + sizeof s, key.size()};
-                const char* names[5] = {"tok", "tscan", "match", "scan", "dedup"};
-                fprintf(stderr, "[graph key miss]");
-                size_t st = 0;
-                for (int q = 0; q < 5; ++q) {
-                    for (size_t i = st; i < ends[q]; i += 4)
-                        if (memcmp(&key[i], &b->gkey[i], std::min<size_t>(4, ends[q] - i)))
-                            fprintf(stderr, " %s+%zu", names[q], i - st);
-                    st = ends[q];
-                }
-                fprintf(stderr, "\n");
-            }
-            if (b->gexec) (void)hipGraphExecDestroy(b->gexec);
-            b->gexec = nullptr;
-            if (b->gkey == key) {   // the second launch with these arguments: capture them
-                hipGraph_t g = nullptr;
-                if (hipStreamBeginCapture(S, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                    const hipError_t e = enqueue(true, true);
-                    const hipError_t e2 = hipStreamEndCapture(S, &g);
-                    if (e == hipSuccess && e2 == hipSuccess && g &&
-                        hipGraphInstantiate(&b->gexec, g, nullptr, nullptr, 0) == hipSuccess) {
-                        (void)hipGraphDestroy(g);
-                        HIP_OK(graph_replay(b, S));
-                        grc = 0;
-                    } else {
-                        if (g) (void)hipGraphDestroy(g);
-                        (void)hipGetLastError();
-                        b->gexec = nullptr;
-                        b->gbad = true;   // the direct way from now on
-                    }
-                } else {
-                    (void)hipGetLastError();
-                    b->gbad = true;
-                }
-            }
-            b->gkey.swap(key);
         }
         csr_done = grc == 0;
         if (csr_done) { b->tok_timed = false; b->graphed = true; }   // (replayed: see the enqueue above)
@@ -827,48 +836,18 @@ int tm_engine::launch(tm_batch* b, bool csr) {
     // from its second launch on the tokeniser, the walk, the generic path and
     // the slot's tail (export + flag) replay as one captured graph: ~10
     // enqueues of ~3 us host time each become one
-    b->tail_done = false;
-    if (!csr && b->bounded && b->tail && tokenize_now && use_graphs && !checked && !b->gbad && grc == 1) {
-        std::vector<uint8_t> key(sizeof t + sizeof ts + sizeof a + sizeof s + b->tail_key.size());
-        uint8_t* k = key.data();
-        memcpy(k, &t, sizeof t); k += sizeof t;
-        memcpy(k, &ts, sizeof ts); k += sizeof ts;
-        memcpy(k, &a, sizeof a); k += sizeof a;
-        memcpy(k, &s, sizeof s); k += sizeof s;
-        if (!b->tail_key.empty()) memcpy(k, b->tail_key.data(), b->tail_key.size());
-        if (b->gexec && b->gkey == key) {
-            HIP_OK(hipGraphLaunch(b->gexec, S));
+    if (tail && !csr && b->bounded && tokenize_now && use_graphs && !checked && !b->gbad && grc == 1) {
+        std::vector<uint8_t> key = graph_key(tail->key, t, ts, a, s);
+        auto record = [&] {
+            const hipError_t e = enqueue(true, false);
+            return e == hipSuccess ? tail->run(S) : e;
+        };
+        if (graph_ready(tail->gc, b->gbad, key, S, record)) {
+            HIP_OK(hipGraphLaunch(tail->gc.exec, S));
             ++graph_launches;
             grc = 0;
-        } else {
-            if (b->gexec) (void)hipGraphExecDestroy(b->gexec);
-            b->gexec = nullptr;
-            if (b->gkey == key) {   // the second launch with these arguments: capture them
-                hipGraph_t g = nullptr;
-                if (hipStreamBeginCapture(S, hipStreamCaptureModeRelaxed) == hipSuccess) {
-                    hipError_t e = enqueue(true, false);
-                    if (e == hipSuccess) e = b->tail(S);
-                    const hipError_t e2 = hipStreamEndCapture(S, &g);
-                    if (e == hipSuccess && e2 == hipSuccess && g &&
-                        hipGraphInstantiate(&b->gexec, g, nullptr, nullptr, 0) == hipSuccess) {
-                        (void)hipGraphDestroy(g);
-                        HIP_OK(hipGraphLaunch(b->gexec, S));
-                        ++graph_launches;
-                        grc = 0;
-                    } else {
-                        if (g) (void)hipGraphDestroy(g);
-                        (void)hipGetLastError();
-                        b->gexec = nullptr;
-                        b->gbad = true;   // the direct way from now on
-                    }
-                } else {
-                    (void)hipGetLastError();
-                    b->gbad = true;
-                }
-            }
-            b->gkey.swap(key);
         }
-        b->tail_done = grc == 0;
+        tail->in_graph = grc == 0;
     }
     if (grc == 1) {
         const hipError_t e = enqueue(false, false);
@@ -887,7 +866,7 @@ int tm_engine::launch(tm_batch* b, bool csr) {
     b->dense = false;
     b->csr = csr;
     if (!csr) return TM_OK;   // the async slot enqueues its read-back and event
-    if (grc == 1 && !csr_done) HIP_OK(enqueue_csr(b, s, S));   // (a graph holds it)
+    if (grc == 1 && !csr_done) HIP_OK(enqueue_csr(b, S));   // (a graph holds it)
     b->scan_args = s;
     if (b->check_tokens) HIP_OK(hipMemcpyAsync(b->h_bad, b->d_nslow, 2 * 4, hipMemcpyDeviceToHost, S));
     if (checked) HIP_OK(hipMemcpyAsync(R.h_dbg, R.d_dbg, 8 * 4, hipMemcpyDeviceToHost, S));
@@ -900,8 +879,7 @@ int tm_engine::launch(tm_batch* b, bool csr) {
     return TM_OK;
 }
 
-hipError_t tm_engine::enqueue_csr(tm_batch* b, const ScanArgs& s, hipStream_t S, unsigned ev_flags) {
-    (void)s;
+hipError_t tm_engine::enqueue_csr(tm_batch* b, hipStream_t S, unsigned ev_flags) {
     hipError_t e;
     if ((e = hipEventRecordWithFlags(b->ev2, S, ev_flags)) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(b->h_hdr, b->d_hdr, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S)) != hipSuccess)
@@ -976,44 +954,6 @@ int tm_engine::ensure_dense(tm_batch* b) {
     (void)hipEventElapsedTime(&ms, b->evc0, b->evc1);
     b->st.ms_csr = ms;
     b->dense = true;
-    return TM_OK;
-}
-
-int tm_engine::launch_graph(tm_batch* b, const MatchArgs& a, const ScanArgs& s, hipStream_t S) {
-    std::vector<uint8_t> key(sizeof(MatchArgs) + sizeof(ScanArgs));
-    memcpy(key.data(), &a, sizeof a);
-    memcpy(key.data() + sizeof a, &s, sizeof s);
-    if (!b->gexec || b->gkey != key) {
-        if (b->gexec) (void)hipGraphExecDestroy(b->gexec);
-        b->gexec = nullptr;
-        if (b->gkey != key) {   // captured only when a launch repeats the last one's arguments
-            b->gkey.swap(key);
-            return 1;
-        }
-        hipGraph_t g = nullptr;
-        if (hipStreamBeginCapture(S, hipStreamCaptureModeRelaxed) != hipSuccess) {
-            (void)hipGetLastError();
-            b->gbad = true;
-            return 1;
-        }
-        hipError_t e = hipMemsetAsync(b->d_hdr, 0, tm_batch::HDR_FIXED, S);
-        // timing events as external nodes: every replay re-records them
-        if (e == hipSuccess) e = launch_match(a, S, b->ev0, b->ev1, false, hipEventRecordExternal);
-        if (e == hipSuccess) e = enqueue_csr(b, s, S, hipEventRecordExternal);
-        const hipError_t e2 = hipStreamEndCapture(S, &g);
-        if (e != hipSuccess || e2 != hipSuccess || !g ||
-            hipGraphInstantiate(&b->gexec, g, nullptr, nullptr, 0) != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            (void)hipGetLastError();
-            b->gexec = nullptr;
-            b->gbad = true;
-            return 1;
-        }
-        (void)hipGraphDestroy(g);
-        b->gkey.swap(key);
-    }
-    HIP_OK(hipGraphLaunch(b->gexec, S));
-    ++graph_launches;
     return TM_OK;
 }
 

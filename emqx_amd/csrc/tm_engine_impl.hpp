@@ -406,6 +406,19 @@ using namespace etm_host;
 
 // ===================================================================== batch
 
+// One captured launch and the arguments it belongs to.  tm_engine::graph_ready
+// is the only code that captures, instantiates or replaces `exec`; its owner
+// (a tm_batch, or an async slot per size class) resets it when it goes away.
+struct GraphCache {
+    hipGraphExec_t exec = nullptr;
+    std::vector<uint8_t> key;   // the arguments exec was captured with, or of the last direct launch
+    void reset() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
+        key.clear();
+    }
+};
+
 struct tm_batch {
     uint32_t n = 0;
     uint64_t nwords = 0;
@@ -457,23 +470,21 @@ struct tm_batch {
     // the stream the batch runs on: async slots own one, other batches use the replica's
     hipStream_t own = nullptr;
     hipEvent_t ev_read = nullptr;   // own-stream batches: marks their walk for the replica's next upload
-    // the batch's whole pipeline (header clear, walk, generic path, scan,
-    // finalize, read-back of the control words) captured as a HIP graph and
-    // replayed while its launch arguments stay the same (small batches: one
-    // launch instead of ten API calls and their gaps)
-    hipGraphExec_t gexec = nullptr;
-    std::vector<uint8_t> gkey;      // the arguments gexec was captured with, or of the last direct launch
-    bool gbad = false;              // capture failed once: this batch launches directly
+    // the batch's own captured launch (tm_engine::graph_ready): a repeated
+    // tokenised batch's header clear, walk, generic path and read-back of the
+    // control words, or a fresh deduplicated batch's whole sequence, replayed
+    // while the launch arguments stay the same (one launch instead of ten to
+    // twenty-five API calls and their gaps)
+    GraphCache graph;
+    bool gbad = false;              // a capture failed once: this batch launches directly from then on
     // A bounded batch (the async slots' fresh batches, tm_async.cpp): sized
     // for n topics and bytes_cap bytes once, its input read by the tokeniser
     // straight from mapped pinned memory and its count from *d_nb (pinned
     // too), so every launch has the same arguments and replays one captured
-    // graph: tokeniser, walk, generic path and `tail` (the slot's export).
+    // graph of the slot's (SlotTail): tokeniser, walk, generic path and the
+    // slot's export.
     bool bounded = false;
     uint32_t* d_nb = nullptr;
-    std::function<hipError_t(hipStream_t)> tail;
-    std::vector<uint8_t> tail_key;  // the tail's arguments (part of the graph key)
-    bool tail_done = false;         // the last launch enqueued the tail (in the graph)
     bool own_user = false;   // TM_BATCH_STREAM: a caller's batch on a stream of its own (async slots: false)
     // generic-path scratch, per batch (batches on different streams run concurrently)
     uint32_t s_waves = 0, s_qcap = 1u << 13, s_ocap = 1u << 14;
@@ -669,9 +680,7 @@ struct tm_batch {
         if (evq) (void)hipEventDestroy(evq);
         ev0 = ev1 = ev2 = evt = ev_read = evc0 = evc1 = ev_end = evq = nullptr;
         end_recorded = false;
-        if (gexec) (void)hipGraphExecDestroy(gexec);
-        gexec = nullptr;
-        gkey.clear();
+        graph.reset();
     }
 };
 
@@ -700,13 +709,10 @@ struct AsyncSlot {
     uint64_t bytes_cap = 0;
     // the bounded batch's captured graphs, one per size class (a batch of n
     // calls runs in the smallest class >= n: a 20-call batch would otherwise
-    // launch the grids of a 16,384-call one); swapped into b.gexec / b.gkey
-    // around each launch
+    // launch the grids of a 16,384-call one); slot_launch hands the class's
+    // cache to launch() with the tail (SlotTail), async_stop resets them
     static constexpr uint32_t NCLASS = 4;
-    struct GraphCache {
-        hipGraphExec_t exec = nullptr;
-        std::vector<uint8_t> key;
-    } gc[NCLASS];
+    GraphCache gc[NCLASS];
     // written by tm_export_host: [ctrl | stats | src n u64 | count n u32] and the rows
     uint8_t* h_out = nullptr;
     size_t c_out = 0;
@@ -730,6 +736,21 @@ struct AsyncSlot {
     uint32_t nchunks = 0, next_chunk = 0, chunks_done = 0;
     const uint32_t* d_count = nullptr;   // (ready) the per-call counts and row starts in h_out
     const unsigned long long* d_src = nullptr;
+};
+
+// What a slot's bounded launch hands to launch(), for that one call: the
+// graph cache of the batch's size class and the slot's tail (export + flag),
+// which is captured behind the walk.  Launches without it (the packed form,
+// the recovery launch of slot_wait) never enter the bounded-graph block.
+struct KeyBytes {   // a byte range appended to a graph key
+    const void* p = nullptr;
+    size_t n = 0;
+};
+struct SlotTail {
+    GraphCache& gc;
+    KeyBytes key;                                  // the tail's arguments (part of the graph key), the caller's
+    std::function<hipError_t(hipStream_t)> run;    // enqueues the tail
+    bool in_graph = false;                         // out: the launch enqueued the tail (in the graph)
 };
 
 // One device copy of the trie (a replica): the HBM tables, the stream the
@@ -2108,14 +2129,15 @@ struct tm_engine {
     // Enqueues the pipeline on the batch's stream.  csr = false (async slots):
     // stop after the walk -- rows stay in the staging area, described by the
     // per-topic (src, count) of the header block, and the caller enqueues its
-    // own read-back; ev2 then marks the end of the walk.
-    int launch(tm_batch* b, bool csr = true);
+    // own read-back; ev2 then marks the end of the walk.  tail: an async
+    // slot's bounded launch (SlotTail).
+    int launch(tm_batch* b, bool csr = true, SlotTail* tail = nullptr);
 
     // the read-back of the control words after the walk.  The batch's result is
     // then what the walk left in HBM -- row i = sfids[src[i] .. + count[i]),
     // sorted and deduplicated -- and the dense CSR (scan + finalize copy) is
     // built only for a consumer that asks for offsets (ensure_dense).
-    hipError_t enqueue_csr(tm_batch* b, const ScanArgs& s, hipStream_t S, unsigned ev_flags = 0);
+    hipError_t enqueue_csr(tm_batch* b, hipStream_t S, unsigned ev_flags = 0);
     hipError_t graph_replay(tm_batch* b, hipStream_t S);
 
     // tm_match_batch's tail, enqueued behind the walk: scan + finalize (the
@@ -2138,13 +2160,39 @@ struct tm_engine {
     // wrote them and never builds it.
     int ensure_dense(tm_batch* b);
 
-    // Replays the batch's captured pipeline, capturing it first when its
-    // arguments changed (tables moved or grew, the root record, the staging
-    // capacity...).  1: capture is unavailable, launch the direct way.
+    // Captured launches (DESIGN.md §5 "Captured launches").  A launch is keyed
+    // by the bytes of its argument structs (+ a trailing byte range: a
+    // slot's tail arguments); graph_ready decides replay, capture or direct:
+    //   key == gc.key and an exec: true, the caller launches gc.exec.
+    //   otherwise the exec (captured with other arguments) is destroyed; if
+    //   key == gc.key -- the second launch in a row with these arguments
+    //   (tables moved or grew, the root record, the staging capacity...
+    //   change them) -- `record()` is captured on S (relaxed) and
+    //   instantiated: true.  A capture that fails leaves no exec and sets
+    //   gbad, and the batch launches directly from then on.  The key is
+    //   remembered (swapped out of `key`) in every case.  false: launch the
+    //   direct way.
+    // Nothing is waited for: a replaced exec is destroyed without a wait for
+    // its last replay on S.
     static constexpr uint32_t GRAPH_MAX = 1u << 20;
     static constexpr uint32_t ONESHOT_MAX = 1u << 20;   // tm_match_batch: one-shot result up to this many topics
     bool use_graphs = true;
-    int launch_graph(tm_batch* b, const MatchArgs& a, const ScanArgs& s, hipStream_t S);
+    // (a template defined in tm_batch.cpp, beside launch(), its only caller:
+    // a caller in another file needs the definition moved here)
+    template <class Record>
+    bool graph_ready(GraphCache& gc, bool& gbad, std::vector<uint8_t>& key, hipStream_t S, Record&& record);
+    template <class... Args>
+    static std::vector<uint8_t> graph_key(KeyBytes tail, const Args&... args) {
+        static_assert((std::is_trivially_copyable_v<Args> && ...), "graph keys are the arguments' bytes");
+        std::vector<uint8_t> key;
+        key.reserve((sizeof(Args) + ... + tail.n));
+        auto put = [&key](const void* p, size_t n) {
+            key.insert(key.end(), static_cast<const uint8_t*>(p), static_cast<const uint8_t*>(p) + n);
+        };
+        (put(&args, sizeof args), ...);
+        put(tail.p, tail.n);
+        return key;
+    }
 
     // control words of a finished launch: TM_EOVERFLOW past the u32 CSR, the
     // retry reasons in *err (0 = clean)

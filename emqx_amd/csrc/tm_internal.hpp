@@ -621,7 +621,7 @@ hipError_t launch_dedup(const DedupArgs& a, ScanArgs rows_scan, ScanArgs bytes_s
 hipError_t launch_dedup_expand(const DedupArgs& a, hipStream_t s);
 hipError_t launch_dedup_rowof(const DedupArgs& a, hipStream_t s);
 // A captured launch is keyed by the bytes of its argument structs
-// (tm_batch.cpp launch / launch_graph): no implicit padding, so equal
+// (tm_engine::graph_key, tm_batch.cpp launch): no implicit padding, so equal
 // arguments always give equal keys (the pads are members, zeroed by `{}`)
 static_assert(std::has_unique_object_representations_v<MatchArgs>, "MatchArgs has implicit padding");
 static_assert(std::has_unique_object_representations_v<ScanArgs>, "ScanArgs has implicit padding");

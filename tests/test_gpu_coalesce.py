@@ -136,6 +136,48 @@ def test_async_staging_miss_recovers_through_the_csr_path():
     assert np.array_equal(counts.astype(np.int64), np.diff(offs.astype(np.int64)))
     assert np.array_equal(hashes, LD.row_hashes(offs, ids))
     assert eng.async_stats()["recoveries"] >= 1
+    # after a recovery (a slot's batch re-run as a packed batch) the engine's
+    # slots go on serving bounded batches: a window of 32 calls (the smallest
+    # size class; whichever slots are free take them) and one of max_batch
+    # calls, the overflowing batch again, which may recover once more
+    for window in (32, len(T)):
+        Tw = T[-window:]
+        offs, ids = eng.match_batch(Tw)
+        st, counts, hashes = LD.run(eng, Tw, LD.ASYNC, 1, window)
+        assert st["errors"] == 0 and st["calls"] == window
+        assert np.array_equal(counts.astype(np.int64), np.diff(offs.astype(np.int64)))
+        assert np.array_equal(hashes, LD.row_hashes(offs, ids))
+
+
+def test_async_slots_replay_one_graph_per_size_class():
+    """Windows of 16, 300 and 2,000 calls in flight land in different size
+    classes of the async slots (32 / 64 / 512 / 4096 calls with max_batch =
+    4096), each with a captured graph of its own: going back and forth
+    between them gives every call match_batch's row, graph launches keep
+    counting up and no batch needs the recovery path."""
+    p = replace(gen.C1, n_filters=2000)
+    F = gen.gen_filters(p)
+    eng = Engine(device=0)
+    eng.insert_many(F)
+    eng.sync()
+    eng.coalesce_config(max_batch=4096)
+    T = gen.gen_topics(p, F, 47, 6000)
+    offs, ids = eng.match_batch(T)
+    offs, ids = offs.copy(), ids.copy()
+    exp_c = np.diff(offs.astype(np.int64))
+    exp_h = LD.row_hashes(offs, ids)
+    g0 = eng.stats()["graph_launches"]
+    seen = []
+    for window in (16, 300, 16, 300, 2000, 16):
+        n = min(8 * window, len(T))         # (the first n topics: a few batches of up to `window` calls)
+        st, counts, hashes = LD.run(eng, T.slice(0, n), LD.ASYNC, 1, window)
+        assert st["errors"] == 0 and st["calls"] == n
+        assert np.array_equal(counts.astype(np.int64), exp_c[:n])
+        assert np.array_equal(hashes, exp_h[:n])
+        seen.append(eng.stats()["graph_launches"])
+    print("graph_launches:", seen, "async:", eng.async_stats())
+    assert seen[-1] > g0 and seen == sorted(seen)
+    assert eng.async_stats()["recoveries"] == 0
 
 
 def test_async_read_your_writes_and_errors_per_batch():
