@@ -1024,6 +1024,12 @@ void tm_engine::fill_stats(tm_batch* b) {
     b->st.ms_total = ms_total;
     b->total = b->st.matches;
     b->st.delivered = b->dedup_dev ? b->h_stats[ST_DELIVERED] : b->st.matches;
+#if TM_PHASE_CYCLES
+    // dev build: the tile walk's cycle sums over all waves, one line per batch
+    fprintf(stderr, "tm_phase_cycles prologue=%llu loop=%llu readback=%llu sort=%llu ms_match=%.4f\n",
+            b->h_stats[ST_PHASE + 0], b->h_stats[ST_PHASE + 1], b->h_stats[ST_PHASE + 2], b->h_stats[ST_PHASE + 3],
+            ms_match);
+#endif
 }
 
 int tm_engine::wait(tm_batch* b, bool drained, uint32_t* relaunched) {

@@ -142,9 +142,16 @@ constexpr uint32_t ERR_CSR_RANGE = 8;    // the batch's match count does not fit
 constexpr uint64_t MAX_RESULT = 0xFFFFFFF0ull;
 
 
+#ifndef TM_PHASE_CYCLES
+#define TM_PHASE_CYCLES 0   // 1 (dev builds): the tile walk sums cycles per phase; fill_stats prints them
+#endif
+// phase cycle sums of the tile walk: prologue, frontier loop, log read-back, sort + staging
+constexpr uint32_t PHASE_N = TM_PHASE_CYCLES ? 4 : 0;
+
 enum StatIdx : uint32_t { ST_VISITS = 0, ST_HASH = 1, ST_WORDS = 2, ST_MATCHES = 3, ST_SLOW = 4, ST_PROBES = 5, ST_ITERS = 6,
                           ST_DELIVERED = 7,   // TM_BATCH_DEDUP: sum over the publishes of their rows' lengths
-                          ST_N = 8 };
+                          ST_PHASE = 8,       // PHASE_N sums (none in the default build)
+                          ST_N = 8 + PHASE_N };
 
 // The batch header block: ctrl (CTRL_WORDS u32) | stats (ST_N u64) | one
 // 128-B line per walk group (see TICKET_GROUPS): u32 tail ticket at +0, u64
@@ -159,7 +166,7 @@ __host__ __device__ __forceinline__ uint64_t xg_top_read(const uint32_t* hdr, ui
     return (uint64_t)w[0] | ((uint64_t)w[1] << 32);
 }
 
-constexpr uint32_t WSTATS = 8;   // u64 partial sums per walk wave (MatchArgs.wstats)
+constexpr uint32_t WSTATS = TM_PHASE_CYCLES ? 16 : 8;   // u64 partial sums per walk wave (MatchArgs.wstats)
 // walks of at least this many waves sum their stats by tm_stats_reduce: ~4,000
 // waves ending together queued ~24k same-line device atomics (C5 K = 100 walk
 // 0.48 -> 0.23 ms without them, C2 4.75 -> 4.62 ms)

@@ -256,6 +256,96 @@ __device__ __forceinline__ unsigned long long xor_lane64(unsigned long long v, u
     return ((unsigned long long)xor_lane32((uint32_t)(v >> 32), j) << 32) | xor_lane32((uint32_t)v, j);
 }
 
+// Per-wave cycle sums of a tile's four phases (-DTM_PHASE_CYCLES=1, dev builds
+// only: python -m emqx_amd.build --variant phase -DTM_PHASE_CYCLES=1).  The
+// sums leave with the wave's wstats partials and fill_stats prints them.  In
+// the default build the struct is empty and its calls compile to nothing.
+enum : int { PH_PROLOGUE = 0, PH_LOOP = 1, PH_READBACK = 2, PH_SORT = 3 };
+struct PhaseClk {
+#if TM_PHASE_CYCLES
+    unsigned long long sum[PHASE_N] = {0, 0, 0, 0}, t0 = 0;
+    __device__ __forceinline__ void start() { t0 = __builtin_readcyclecounter(); }
+    __device__ __forceinline__ void lap(int p) {
+        const unsigned long long now = __builtin_readcyclecounter();
+        sum[p] += now - t0;
+        t0 = now;
+    }
+#else
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void lap(int) {}
+#endif
+};
+
+// xor_lane32 for j <= 8 with bound_ctrl set (every lane has a source, so the
+// value is the same): the form the compiler folds into the v_min / v_max that
+// use it as their DPP operand
+__device__ __forceinline__ uint32_t xor_lane32_bc(uint32_t v, uint32_t j) {
+    const int x = (int)v;
+    switch (j) {
+    case 1: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);
+    case 2: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);
+    case 4: return (uint32_t)__builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true),
+                                                         0x1B, 0xF, 0xF, true);
+    default: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);
+    }
+}
+
+#ifndef TM_TAGGED_SORT
+#define TM_TAGGED_SORT 1   // 0: every size class sorts u64 (A/B builds)
+#endif
+// Tagged 32-bit row sort.  When every entry of a chunk has zero bits below
+// `free` in the high word of its path code (and a zero bit 31), a row of size
+// class W with log2(W) <= free sorts as ONE u32 per lane: the code's high word
+// with the entry's index in the row in the free bits.  Path codes are distinct
+// within a row -- a code spells the branch taken at every level (literal / '+' /
+// '#' terminal / end have different digits in every word class, and the ''
+// re-digit 4 -> 1 takes a value no other branch of the C_EMPTY class has), a
+// literal '#' word's duplicate is never emitted (M_SKIPE) and a literal '+'
+// word is never probed as a literal, so two entries of one topic with one code
+// would be one filter emitted twice -- hence the tag never decides a compare
+// and the order is the u64 sort's (code, then filter id; merge_runs_out relies
+// on the same fact).  A stage is v_min_u32 / v_max_u32 on the exchanged value
+// plus one select on a compile-time lane mask: lane e keeps the lower value
+// iff ((e & j) == 0) == ((e & kk) == 0).
+constexpr uint64_t keep_lo_mask(uint32_t W, uint32_t kk, uint32_t j) {
+    uint64_t m = 0;
+    for (uint32_t l = 0; l < 64; ++l) {
+        const uint32_t e = l & (W - 1);
+        if (((e & j) == 0) == ((e & kk) == 0)) m |= 1ull << l;
+    }
+    return m;
+}
+
+template <uint32_t W, uint32_t KK, uint32_t J>
+__device__ __forceinline__ uint32_t tag_stage(uint32_t k) {
+    constexpr uint64_t M = keep_lo_mask(W, KK, J);
+    uint32_t lo, hi;
+    if constexpr (J >= 16) {
+        // after the swap both lanes of a pair hold {own, partner} in {p[0], p[1]}
+        const auto p = J == 16 ? __builtin_amdgcn_permlane16_swap(k, k, false, false)
+                               : __builtin_amdgcn_permlane32_swap(k, k, false, false);
+        lo = min(p[0], p[1]);
+        hi = max(p[0], p[1]);
+    } else {
+        const uint32_t other = xor_lane32_bc(k, J);
+        lo = min(k, other);
+        hi = max(k, other);
+    }
+    return __builtin_amdgcn_inverse_ballot_w64(M) ? lo : hi;
+}
+template <uint32_t W, uint32_t KK, uint32_t J>
+__device__ __forceinline__ uint32_t tag_merge(uint32_t k) {
+    k = tag_stage<W, KK, J>(k);
+    if constexpr (J > 1) k = tag_merge<W, KK, J / 2>(k);
+    return k;
+}
+template <uint32_t W, uint32_t KK = 2>
+__device__ __forceinline__ uint32_t tag_sort(uint32_t k) {
+    k = tag_merge<W, KK, KK / 2>(k);
+    if constexpr (KK < W) k = tag_sort<W, KK * 2>(k);
+    return k;
+}
+
 // Tile epilogue: sort the 64 rows of this wave and write their filter ids to
 // sfids[dst .. dst + c).  The rows are pulled into LDS a chunk of whole rows at
 // a time (at most STAGE elements), eight rows per batch of independent loads:
@@ -264,9 +354,11 @@ __device__ __forceinline__ unsigned long long xor_lane64(unsigned long long v, u
 // of size class W (W/2 < c <= W, W = 2..64) are then packed 64/W per
 // wave-instruction, one element per lane, and sorted by a W-wide bitonic
 // network of __shfl_xor exchanges.  65..128 elements: rank count, two per lane.
+// `free` (wave-uniform): zero low bits of every staged code's high word; a
+// class with log2(W) <= free takes the tagged u32 network above.
 template <bool CK, class LT>
 __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool keep, uint32_t c, uint32_t pos,
-                                             uint32_t dst) {
+                                             uint32_t dst, uint32_t free) {
     constexpr uint32_t STAGE = LT::STAGE;
     const uint32_t lane = threadIdx.x;
     const unsigned long long* stg = reinterpret_cast<const unsigned long long*>(L.q);
@@ -288,6 +380,24 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
             const uint32_t cr = __shfl(c, owner, 64);
             const uint32_t pr = __shfl(pos, owner, 64);
             const uint32_t dr = __shfl(dst, owner, 64);
+            if (TM_TAGGED_SORT && (W >> free) <= 1) {   // log2(W) <= free
+                const uint32_t* stg32 = reinterpret_cast<const uint32_t*>(L.q);
+                uint32_t k32 = 0xFFFFFFFFu;   // padding: no code's top digit exceeds 4
+                if (rv && e < cr) k32 = stg32[2 * CK_(pr + e, STAGE, 42) + 1] | e;
+                switch (W) {
+                case 2: k32 = tag_sort<2>(k32); break;
+                case 4: k32 = tag_sort<4>(k32); break;
+                case 8: k32 = tag_sort<8>(k32); break;
+                case 16: k32 = tag_sort<16>(k32); break;
+                case 32: k32 = tag_sort<32>(k32); break;
+                default: k32 = tag_sort<64>(k32); break;
+                }
+                // sorted place e holds the entry that arrived as number k32 & (W - 1)
+                if (rv && e < cr)
+                    a.sfids[CK_((uint64_t)dr + e, a.sfids_cap, 44)] =
+                        stg32[2 * CK_(pr + (k32 & (W - 1)), STAGE, 43)] & (uint32_t)~KEY_MASK;
+                continue;
+            }
             unsigned long long key = ~0ull;
             if (rv && e < cr) key = stg[CK_(pr + e, STAGE, 42)];
 #pragma unroll
@@ -347,7 +457,8 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
 // sorted as before.
 template <bool CK, class LT>
 __device__ __forceinline__ void sort_rows_log(const MatchArgs& a, LT& L, bool keep, uint32_t c, uint32_t dst,
-                                              unsigned long long* wlog, uint8_t* wlane, uint32_t lcount) {
+                                              unsigned long long* wlog, uint8_t* wlane, uint32_t lcount,
+                                              PhaseClk& pc) {
     constexpr uint32_t STAGE = LT::STAGE;
     const uint32_t lane = threadIdx.x;
     unsigned long long* stg = reinterpret_cast<unsigned long long*>(L.q);
@@ -369,6 +480,7 @@ __device__ __forceinline__ void sort_rows_log(const MatchArgs& a, LT& L, bool ke
         L.depth[lane] = in_chunk ? pos - p0 : NONE;
         L.toff[lane] = 0;                            // row fill cursor
         __syncthreads();
+        uint32_t kor = 0;   // OR of the placed entries' code bits 31..62
         for (uint32_t k0 = 0; k0 < lcount; k0 += 64 * TM_LOG_U) {
             unsigned long long e[TM_LOG_U];
             uint32_t r[TM_LOG_U];
@@ -387,11 +499,24 @@ __device__ __forceinline__ void sort_rows_log(const MatchArgs& a, LT& L, bool ke
                 if (base == NONE) continue;
                 const uint32_t at = base + atomicAdd(&L.toff[r[u]], 1u);
                 stg[CK_(at, STAGE, 49)] = e[u];
+                kor |= (uint32_t)(e[u] >> 31);
             }
         }
+        // free low bits of the chunk's code high words: tz = ctz of the OR of
+        // the codes, free = clamp(tz - 32, 0, 8) (bit 31, the level-10 digit's
+        // lowest, is part of the code: set anywhere -> 0)
+        uint32_t free = 0;
+        if (TM_TAGGED_SORT) {
+#pragma unroll
+            for (uint32_t j = 1; j < 64; j <<= 1) kor |= xor_lane32(kor, j);
+            const uint32_t tz = (uint32_t)__builtin_ctz(__builtin_amdgcn_readfirstlane(kor) | 0x200u);   // 0..9
+            free = tz ? tz - 1 : 0u;
+        }
         __syncthreads();
-        sort_classes<CK, LT>(a, L, in_chunk, c, pos - p0, dst);
+        pc.lap(PH_READBACK);
+        sort_classes<CK, LT>(a, L, in_chunk, c, pos - p0, dst, free);
         __syncthreads();
+        pc.lap(PH_SORT);
         rs = re;
     }
 }
@@ -415,7 +540,8 @@ __device__ __forceinline__ void send_to_slow(const MatchArgs& a, bool mine, uint
 template <bool CK, bool BIG, bool IN_LDS, class LT>
 __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t0, uint32_t tend, uint32_t wbase,
                                            uint8_t fl, bool valid, unsigned long long& sV, unsigned long long& sH,
-                                           unsigned long long& sW, unsigned long long& sM, unsigned long long& sP) {
+                                           unsigned long long& sW, unsigned long long& sM, unsigned long long& sP,
+                                           PhaseClk& pc) {
     const uint32_t lane = threadIdx.x;
     const uint32_t t = t0 + lane;
     const uint32_t* wsrc = IN_LDS ? L.words : a.words;
@@ -479,6 +605,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     const uint32_t qd = lane >> 2, qs = lane & 3;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<Slot*>(a.slots), 0, BIG ? 0u : a.nslots * 16u, 0x00020000);
+    pc.lap(PH_PROLOGUE);
     while (qn > 0) {
         const uint32_t k = min(qn, 64u);
         const bool has = lane < k;
@@ -628,6 +755,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         }
     }
     __syncthreads();
+    pc.lap(PH_LOOP);
 
     if (ovf) {
         // probe stack overflow: every regular topic of the tile goes to the slow path
@@ -658,8 +786,9 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     base64 += (uint64_t)g * a.rcap;
     const uint32_t base = (uint32_t)base64;
     const uint32_t dst = base + incl - c;
+    pc.lap(PH_SORT);   // the staging reservation counts as staging
     if (fits) {
-        sort_rows_log<CK, LT>(a, L, keep, c, dst, wrows, wlane, lcount);
+        sort_rows_log<CK, LT>(a, L, keep, c, dst, wrows, wlane, lcount, pc);
     } else if (lane == 0) {
         atomicOr(&a.ctrl[CTRL_ERR], ERR_STAGING);   // host grows sfids[] and reruns
     }
@@ -668,6 +797,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         a.src[CK_(t, a.n, 17)] = dst;
         sM += c_me;
     }
+    pc.lap(PH_SORT);
     (void)tend;
 }
 
@@ -698,6 +828,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
     const uint32_t tt = a.tile_topics;   // topics per tile: 64, or fewer for small batches
     const uint32_t ntiles = (a.n + tt - 1) / tt;
     unsigned long long sV = 0, sH = 0, sW = 0, sM = 0, sP = 0;
+    PhaseClk pc;
 
     // static round-robin tiles, then tickets for the tail; a ticket is taken at
     // the start of a tile so its latency hides behind the tile's work
@@ -706,6 +837,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
         // the next tile: round-robin for the first static_rounds, then from a
         // ticket (a contended counter's latency would stall every in-order vmcnt
         // wait of the tile, so only the tail balances by tickets, per XCD)
+        pc.start();
         uint32_t ticket = 0;
         if (round + 1 >= a.static_rounds && lane == 0)
             ticket = atomicAdd(&a.xg[(blockIdx.x % TICKET_GROUPS) * TICKET_STRIDE], 1u);
@@ -724,8 +856,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
         L.depth[lane] = my_end - my_off;
         L.cnt[lane] = 0;
         __syncthreads();
-        if (in_lds) match_tile<CK, BIG, true>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP);
-        else match_tile<CK, BIG, false>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP);
+        if (in_lds) match_tile<CK, BIG, true>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc);
+        else match_tile<CK, BIG, false>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc);
         __syncthreads();
         ++round;
         tile = round < a.static_rounds
@@ -745,33 +877,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
         unsigned long long* w = a.wstats + (uint64_t)blockIdx.x * WSTATS;
         w[0] = sV; w[1] = sH; w[2] = sW; w[3] = sM;
         w[4] = sP & ((1ull << 40) - 1); w[5] = sP >> 40;
+#if TM_PHASE_CYCLES
+        for (uint32_t k = 0; k < PHASE_N; ++k) w[6 + k] = pc.sum[k];
+#endif
     } else if (lane == 0) {
         atomicAdd(&a.stats[ST_VISITS], sV); atomicAdd(&a.stats[ST_HASH], sH);
         atomicAdd(&a.stats[ST_WORDS], sW); atomicAdd(&a.stats[ST_MATCHES], sM);
         atomicAdd(&a.stats[ST_PROBES], sP & ((1ull << 40) - 1));
         atomicAdd(&a.stats[ST_ITERS], sP >> 40);
+#if TM_PHASE_CYCLES
+        for (uint32_t k = 0; k < PHASE_N; ++k) atomicAdd(&a.stats[ST_PHASE + k], pc.sum[k]);
+#endif
     }
 }
 
 // the walk waves' sums -> the batch's stats (one block; after the walk)
 __global__ __launch_bounds__(256) void tm_stats_reduce(const unsigned long long* w, uint32_t waves,
                                                        unsigned long long* stats) {
-    __shared__ unsigned long long sh[4][6];
-    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+    constexpr uint32_t NS = 6 + PHASE_N;   // 6, or 10 with the phase cycle sums (TM_PHASE_CYCLES)
+    __shared__ unsigned long long sh[4][NS];
+    unsigned long long v[NS] = {};
     for (uint32_t i = threadIdx.x; i < waves; i += 256)
 #pragma unroll
-        for (uint32_t k = 0; k < 6; ++k) v[k] += w[(uint64_t)i * WSTATS + k];
+        for (uint32_t k = 0; k < NS; ++k) v[k] += w[(uint64_t)i * WSTATS + k];
 #pragma unroll
-    for (uint32_t k = 0; k < 6; ++k) {
+    for (uint32_t k = 0; k < NS; ++k) {
         for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
         if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
     }
     __syncthreads();
-    if (threadIdx.x < 6) {
+    if (threadIdx.x < NS) {
         const uint32_t k = threadIdx.x;
         const unsigned long long t = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
         const uint32_t idx[6] = {ST_VISITS, ST_HASH, ST_WORDS, ST_MATCHES, ST_PROBES, ST_ITERS};
-        if (t) atomicAdd(&stats[idx[k]], t);
+        if (t) atomicAdd(&stats[k < 6 ? idx[k] : ST_PHASE + (k - 6)], t);
     }
 }
 
