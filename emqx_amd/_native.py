@@ -119,6 +119,33 @@ class ShardedStats(C.Structure):
                 ("part_topics", C.c_uint32 * 64), ("ms_stage", C.c_float), ("ms_plan", C.c_float)]
 
 
+TM_ACL_DENY, TM_ACL_ALLOW, TM_ACL_NOMATCH = 0, 1, 2
+TM_ACL_PUBLISH, TM_ACL_SUBSCRIBE, TM_ACL_PUBSUB = 1, 2, 3
+(TM_WHO_ALL, TM_WHO_CLIENT_ALL, TM_WHO_USER_ALL, TM_WHO_CLIENT, TM_WHO_USER, TM_WHO_IPADDR, TM_WHO_AND,
+ TM_WHO_OR) = range(8)
+TM_ACL_MAX_WHO_DEPTH = 32
+
+
+class AclWho(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("n_children", C.c_uint32), ("val", C.c_void_p), ("val_len", C.c_uint32),
+                ("family", C.c_uint8), ("lo", C.c_uint8 * 16), ("hi", C.c_uint8 * 16)]
+
+
+class AclTopic(C.Structure):
+    _fields_ = [("filter", C.c_void_p), ("len", C.c_uint32), ("eq", C.c_uint32)]
+
+
+class AclRule(C.Structure):
+    _fields_ = [("allow", C.c_uint32), ("access", C.c_uint32), ("who", C.POINTER(AclWho)), ("n_who", C.c_uint32),
+                ("topics", C.POINTER(AclTopic)), ("n_topics", C.c_uint32)]
+
+
+class AclClients(C.Structure):
+    _fields_ = [("m", C.c_uint32), ("clientids", C.c_void_p), ("clientid_offsets", C.c_void_p),
+                ("usernames", C.c_void_p), ("username_offsets", C.c_void_p), ("flags", C.c_void_p),
+                ("family", C.c_void_p), ("peerhost", C.c_void_p)]
+
+
 # void (*tm_match_cb)(void* ctx, int rc, const uint32_t* ids, uint32_t n)
 MATCH_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_uint32), C.c_uint32)
 
@@ -194,6 +221,10 @@ SIGNATURES = {
     "tm_topic_wildcard": (C.c_int, [U8P, SZ]),
     "tm_topic_validate": (C.c_int, [C.c_int, U8P, SZ, C.POINTER(C.c_char_p)]),
     "tm_rules_match": (C.c_int, [P, P, P, C.c_uint32, P, P, C.c_uint32, C.c_int, P]),
+    "tm_acl_create": (C.c_int, [P, C.POINTER(AclRule), C.c_uint32, C.POINTER(P)]),
+    "tm_acl_free": (None, [P, P]),
+    "tm_acl_check": (C.c_int, [P, P, C.POINTER(AclClients), P, P, P, P, C.c_uint32, P, P]),
+    "tm_acl_kernel_ms": (C.c_float, [P, P]),
     "tm_group_create": (C.c_int, [P, C.c_uint32, C.POINTER(Config), C.POINTER(P)]),
     "tm_group_destroy": (None, [P]),
     "tm_group_size": (C.c_uint32, [P]),

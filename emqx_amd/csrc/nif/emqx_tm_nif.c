@@ -32,6 +32,7 @@
 #include "emqx_tm.h"
 
 static ErlNifResourceType* ENGINE_RT;
+static ErlNifResourceType* ACL_RT;
 
 typedef struct {
     tm_engine* e;
@@ -39,7 +40,9 @@ typedef struct {
 
 static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_TRUE, ATOM_FALSE, ATOM_UNDEFINED, ATOM_ROOT,
     ATOM_TRIE_NODE, ATOM_NODE_NOT_FOUND, ATOM_ENOMEM, ATOM_EIO, ATOM_EINVAL, ATOM_ENODEV,
-    ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH;
+    ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH,
+    ATOM_ALLOW, ATOM_DENY, ATOM_NOMATCH, ATOM_NONE, ATOM_ALL, ATOM_CLIENT, ATOM_USER, ATOM_IPADDR, ATOM_AND, ATOM_OR,
+    ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB;
 
 /* set while a match callback runs on the engine's completion thread */
 static __thread int in_engine_callback;
@@ -592,6 +595,302 @@ static ERL_NIF_TERM nif_rules_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM
     return out;
 }
 
+/* ---- ACL check (emqx_access_control:check_acl/3 on the device) ---------- */
+/* A rule set lives in a resource of its own, which keeps its engine alive. */
+typedef struct {
+    tm_acl* a;
+    engine_res* owner;
+} acl_res;
+
+static void acl_dtor(ErlNifEnv* env, void* obj) {
+    (void)env;
+    acl_res* r = (acl_res*)obj;
+    if (r->a && r->owner && r->owner->e) tm_acl_free(r->owner->e, r->a);
+    r->a = NULL;
+    if (r->owner) enif_release_resource(r->owner);
+    r->owner = NULL;
+}
+
+typedef struct {
+    tm_acl_who* v;
+    unsigned n, cap;
+} who_vec;
+
+/* an inet tuple -> 16 bytes in network order (IPv4 in the first 4); returns the family or 0 */
+static int get_inet(ErlNifEnv* env, ERL_NIF_TERM t, uint8_t out[16]) {
+    int ar;
+    const ERL_NIF_TERM* el;
+    unsigned x;
+    memset(out, 0, 16);
+    if (!enif_get_tuple(env, t, &ar, &el)) return 0;
+    if (ar == 4) {
+        for (int i = 0; i < 4; i++) {
+            if (!enif_get_uint(env, el[i], &x) || x > 255) return 0;
+            out[i] = (uint8_t)x;
+        }
+        return 4;
+    }
+    if (ar == 8) {
+        for (int i = 0; i < 8; i++) {
+            if (!enif_get_uint(env, el[i], &x) || x > 65535) return 0;
+            out[2 * i] = (uint8_t)(x >> 8);
+            out[2 * i + 1] = (uint8_t)x;
+        }
+        return 6;
+    }
+    return 0;
+}
+
+/* a compiled who term -> pre-order nodes appended to w (binaries are borrowed from the call's terms) */
+#define ACL_PARSE_DEPTH 40   /* deeper than tm_acl_create accepts: it names the rule in its error */
+static int parse_who(ErlNifEnv* env, ERL_NIF_TERM t, who_vec* w, int depth) {
+    if (depth > ACL_PARSE_DEPTH) return 0;
+    if (w->n == w->cap) {
+        unsigned cap = w->cap ? w->cap * 2 : 16;
+        tm_acl_who* nv = enif_alloc(sizeof(tm_acl_who) * cap);
+        if (w->n) memcpy(nv, w->v, sizeof(tm_acl_who) * w->n);
+        if (w->v) enif_free(w->v);
+        w->v = nv;
+        w->cap = cap;
+    }
+    const unsigned at = w->n++;
+    memset(&w->v[at], 0, sizeof(tm_acl_who));
+    if (enif_is_identical(t, ATOM_ALL)) { w->v[at].kind = TM_WHO_ALL; return 1; }
+    int ar;
+    const ERL_NIF_TERM* el;
+    if (!enif_get_tuple(env, t, &ar, &el) || ar != 2) return 0;
+    if (enif_is_identical(el[0], ATOM_CLIENT) || enif_is_identical(el[0], ATOM_USER)) {
+        const int isc = enif_is_identical(el[0], ATOM_CLIENT);
+        ErlNifBinary b;
+        if (enif_is_identical(el[1], ATOM_ALL)) { w->v[at].kind = isc ? TM_WHO_CLIENT_ALL : TM_WHO_USER_ALL; return 1; }
+        if (!enif_inspect_binary(env, el[1], &b) || b.size > 0xFFFFFFu) return 0;
+        w->v[at].kind = isc ? TM_WHO_CLIENT : TM_WHO_USER;
+        w->v[at].val = b.data;
+        w->v[at].val_len = (uint32_t)b.size;
+        return 1;
+    }
+    if (enif_is_identical(el[0], ATOM_IPADDR)) {
+        int car;
+        const ERL_NIF_TERM* c;
+        if (!enif_get_tuple(env, el[1], &car, &c) || car != 3) return 0;
+        const int f0 = get_inet(env, c[0], w->v[at].lo), f1 = get_inet(env, c[1], w->v[at].hi);
+        if (!f0 || f0 != f1) return 0;
+        w->v[at].kind = TM_WHO_IPADDR;
+        w->v[at].family = (uint8_t)f0;
+        return 1;
+    }
+    if (enif_is_identical(el[0], ATOM_AND) || enif_is_identical(el[0], ATOM_OR)) {
+        unsigned nc;
+        ERL_NIF_TERM head, tail = el[1];
+        if (!enif_get_list_length(env, tail, &nc)) return 0;
+        w->v[at].kind = enif_is_identical(el[0], ATOM_AND) ? TM_WHO_AND : TM_WHO_OR;
+        w->v[at].n_children = nc;
+        for (unsigned i = 0; i < nc; i++)
+            if (!enif_get_list_cell(env, tail, &head, &tail) || !parse_who(env, head, w, depth + 1)) return 0;
+        return 1;
+    }
+    return 0;   /* a bare binary included: emqx_access_rule:compile/2 has no clause for it */
+}
+
+/* acl_new(Engine, Rules) -> {ok, Acl} | {error, Reason}
+ * Rules as emqx_access_rule:compile/1 leaves the who part, topics as binaries:
+ * {A, all} | {A, Who, publish | subscribe | pubsub, [Topic | {eq, Topic}]},
+ * Who = all | {client | user, all | Bin} | {ipaddr, {Start, End, Len}} |
+ * {'and' | 'or', [Who]}.  The list's order is the order of the fold. */
+static ERL_NIF_TERM nif_acl_new(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    unsigned n;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_get_list_length(env, argv[1], &n)) return enif_make_badarg(env);
+    tm_acl_rule* rules = enif_alloc(sizeof(tm_acl_rule) * (n ? n : 1));
+    unsigned* who_at = enif_alloc(sizeof(unsigned) * (n ? n : 1));
+    unsigned* top_at = enif_alloc(sizeof(unsigned) * (n ? n : 1));
+    who_vec w = {NULL, 0, 0};
+    tm_acl_topic* tops = NULL;
+    unsigned ntop = 0, captop = 0;
+    int ok = 1;
+    ERL_NIF_TERM head, tail = argv[1];
+    for (unsigned j = 0; ok && j < n; j++) {
+        int ar;
+        const ERL_NIF_TERM* el;
+        memset(&rules[j], 0, sizeof(tm_acl_rule));
+        who_at[j] = w.n;
+        top_at[j] = ntop;
+        ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_tuple(env, head, &ar, &el) && (ar == 2 || ar == 4);
+        if (!ok) break;
+        if (enif_is_identical(el[0], ATOM_ALLOW)) rules[j].allow = TM_ACL_ALLOW;
+        else if (enif_is_identical(el[0], ATOM_DENY)) rules[j].allow = TM_ACL_DENY;
+        else ok = 0;
+        if (ok && ar == 2) { ok = enif_is_identical(el[1], ATOM_ALL); continue; }   /* {A, all}: access 0 */
+        if (!ok) break;
+        if (enif_is_identical(el[2], ATOM_PUBLISH)) rules[j].access = TM_ACL_PUBLISH;
+        else if (enif_is_identical(el[2], ATOM_SUBSCRIBE)) rules[j].access = TM_ACL_SUBSCRIBE;
+        else if (enif_is_identical(el[2], ATOM_PUBSUB)) rules[j].access = TM_ACL_PUBSUB;
+        else ok = 0;
+        unsigned nt = 0;
+        ok = ok && parse_who(env, el[1], &w, 1) && enif_get_list_length(env, el[3], &nt);
+        if (!ok) break;
+        rules[j].n_who = w.n - who_at[j];
+        rules[j].n_topics = nt;
+        ERL_NIF_TERM th, tt = el[3];
+        for (unsigned f = 0; ok && f < nt; f++) {
+            ErlNifBinary b;
+            int tar;
+            const ERL_NIF_TERM* te;
+            uint32_t eq = 0;
+            ok = enif_get_list_cell(env, tt, &th, &tt);
+            if (ok && enif_get_tuple(env, th, &tar, &te)) {
+                ok = tar == 2 && enif_is_identical(te[0], ATOM_EQ);
+                if (ok) th = te[1];
+                eq = 1;
+            }
+            ok = ok && enif_inspect_binary(env, th, &b) && b.size <= 0xFFFFFFu;
+            if (!ok) break;
+            if (ntop == captop) {
+                unsigned cap = captop ? captop * 2 : 16;
+                tm_acl_topic* nv = enif_alloc(sizeof(tm_acl_topic) * cap);
+                if (ntop) memcpy(nv, tops, sizeof(tm_acl_topic) * ntop);
+                if (tops) enif_free(tops);
+                tops = nv;
+                captop = cap;
+            }
+            tops[ntop].filter = b.data;
+            tops[ntop].len = (uint32_t)b.size;
+            tops[ntop].eq = eq;
+            ntop++;
+        }
+    }
+    ERL_NIF_TERM out;
+    if (!ok) {
+        out = enif_make_badarg(env);
+    } else {
+        for (unsigned j = 0; j < n; j++) {   /* the arrays no longer move */
+            rules[j].who = w.v ? w.v + who_at[j] : NULL;
+            rules[j].topics = tops ? tops + top_at[j] : NULL;
+        }
+        tm_acl* a = NULL;
+        const int rc = tm_acl_create(r->e, rules, n, &a);
+        if (rc) {
+            out = err(env, rc);
+        } else {
+            acl_res* ar = enif_alloc_resource(ACL_RT, sizeof(acl_res));
+            ar->a = a;
+            ar->owner = r;
+            enif_keep_resource(r);
+            out = enif_make_tuple2(env, ATOM_OK, enif_make_resource(env, ar));
+            enif_release_resource(ar);
+        }
+    }
+    enif_free(rules); enif_free(who_at); enif_free(top_at);
+    if (w.v) enif_free(w.v);
+    if (tops) enif_free(tops);
+    return out;
+}
+
+/* acl_check(Engine, Acl, Clients, Requests) -> [{allow | deny | nomatch, RuleIndex | none}]
+ * Clients = [{ClientId | undefined, Username | undefined, PeerTuple | undefined}],
+ * Requests = [{ClientIndex, publish | subscribe, Topic}] (0-based index);
+ * emqx_mod_acl_internal:check_acl/5 (src/emqx_mod_acl_internal.erl:69-90) per
+ * request, RuleIndex 0-based in the list given to acl_new/2. */
+static ERL_NIF_TERM nif_acl_check(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    acl_res* ar;
+    unsigned m, n;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_get_resource(env, argv[1], ACL_RT, (void**)&ar) || !ar->a ||
+        ar->owner != r || !enif_get_list_length(env, argv[2], &m) || !enif_get_list_length(env, argv[3], &n))
+        return enif_make_badarg(env);
+    ErlNifBinary* cb = enif_alloc(sizeof(ErlNifBinary) * 2 * (m ? m : 1));   /* ids, then names */
+    uint64_t* coff = enif_alloc(sizeof(uint64_t) * 2 * (m + 1));
+    uint8_t* cmeta = enif_alloc(18 * (size_t)(m ? m : 1));                    /* flags | family | peerhost */
+    uint8_t *flags = cmeta, *family = cmeta + m, *peer = cmeta + 2 * (size_t)m;
+    ErlNifBinary* tb = enif_alloc(sizeof(ErlNifBinary) * (n ? n : 1));
+    uint64_t* toff = enif_alloc(sizeof(uint64_t) * (n + 1));
+    uint32_t* cof = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+    uint8_t* acc = enif_alloc(n ? n : 1);
+    uint8_t *idb = NULL, *nmb = NULL, *tbuf = NULL, *verdict = NULL;
+    uint32_t* rule = NULL;
+    int ok = 1;
+    ERL_NIF_TERM head, tail = argv[2];
+    uint64_t *ioff = coff, *uoff = coff + m + 1;
+    ioff[0] = uoff[0] = 0;
+    for (unsigned i = 0; ok && i < m; i++) {
+        int a3;
+        const ERL_NIF_TERM* el;
+        ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_tuple(env, head, &a3, &el) && a3 == 3;
+        if (!ok) break;
+        flags[i] = 0;
+        for (int k = 0; ok && k < 2; k++) {
+            ErlNifBinary* b = &cb[(size_t)k * m + i];
+            b->size = 0;
+            b->data = NULL;
+            if (enif_is_identical(el[k], ATOM_UNDEFINED)) continue;
+            ok = enif_inspect_binary(env, el[k], b);
+            flags[i] |= (uint8_t)(1u << k);
+        }
+        if (!ok) break;
+        ioff[i + 1] = ioff[i] + cb[i].size;
+        uoff[i + 1] = uoff[i] + cb[(size_t)m + i].size;
+        memset(peer + 16 * (size_t)i, 0, 16);
+        family[i] = 0;
+        if (!enif_is_identical(el[2], ATOM_UNDEFINED)) {
+            family[i] = (uint8_t)get_inet(env, el[2], peer + 16 * (size_t)i);
+            ok = family[i] != 0;
+        }
+    }
+    tail = argv[3];
+    toff[0] = 0;
+    for (unsigned i = 0; ok && i < n; i++) {
+        int a3;
+        const ERL_NIF_TERM* el;
+        unsigned ci;
+        ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_tuple(env, head, &a3, &el) && a3 == 3 &&
+             enif_get_uint(env, el[0], &ci) && ci < m && enif_inspect_binary(env, el[2], &tb[i]);
+        if (!ok) break;
+        if (enif_is_identical(el[1], ATOM_PUBLISH)) acc[i] = TM_ACL_PUBLISH;
+        else if (enif_is_identical(el[1], ATOM_SUBSCRIBE)) acc[i] = TM_ACL_SUBSCRIBE;
+        else ok = 0;
+        cof[i] = ci;
+        toff[i + 1] = toff[i] + tb[i].size;
+    }
+    ERL_NIF_TERM out;
+    if (!ok) {
+        out = enif_make_badarg(env);
+    } else {
+        idb = enif_alloc(ioff[m] ? ioff[m] : 1);
+        nmb = enif_alloc(uoff[m] ? uoff[m] : 1);
+        tbuf = enif_alloc(toff[n] ? toff[n] : 1);
+        verdict = enif_alloc(n ? n : 1);
+        rule = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+        for (unsigned i = 0; i < m; i++) {
+            if (cb[i].size) memcpy(idb + ioff[i], cb[i].data, cb[i].size);
+            if (cb[(size_t)m + i].size) memcpy(nmb + uoff[i], cb[(size_t)m + i].data, cb[(size_t)m + i].size);
+        }
+        for (unsigned i = 0; i < n; i++)
+            if (tb[i].size) memcpy(tbuf + toff[i], tb[i].data, tb[i].size);
+        tm_acl_clients cl = {m, idb, ioff, nmb, uoff, flags, family, peer};
+        const int rc = tm_acl_check(r->e, ar->a, &cl, tbuf, toff, cof, acc, n, verdict, rule);
+        if (rc) {
+            out = err(env, rc);
+        } else {
+            out = enif_make_list(env, 0);
+            for (unsigned i = n; i-- > 0;) {
+                ERL_NIF_TERM v = verdict[i] == TM_ACL_ALLOW ? ATOM_ALLOW : verdict[i] == TM_ACL_DENY ? ATOM_DENY
+                                                                                                      : ATOM_NOMATCH;
+                ERL_NIF_TERM ri = rule[i] == TM_NONE ? ATOM_NONE : enif_make_uint(env, rule[i]);
+                out = enif_make_list_cell(env, enif_make_tuple2(env, v, ri), out);
+            }
+        }
+    }
+    enif_free(cb); enif_free(coff); enif_free(cmeta); enif_free(tb); enif_free(toff); enif_free(cof); enif_free(acc);
+    if (idb) enif_free(idb);
+    if (nmb) enif_free(nmb);
+    if (tbuf) enif_free(tbuf);
+    if (verdict) enif_free(verdict);
+    if (rule) enif_free(rule);
+    return out;
+}
+
 /* topic_match(Name, Filter) -> boolean()  (emqx_topic:match/2, src/emqx_topic.erl:65-87) */
 static ERL_NIF_TERM nif_topic_match(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
     ErlNifBinary a, f;
@@ -604,6 +903,8 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     (void)priv; (void)info;
     ENGINE_RT = enif_open_resource_type(env, NULL, "tm_engine", engine_dtor, ERL_NIF_RT_CREATE, NULL);
     if (!ENGINE_RT) return -1;
+    ACL_RT = enif_open_resource_type(env, NULL, "tm_acl", acl_dtor, ERL_NIF_RT_CREATE, NULL);
+    if (!ACL_RT) return -1;
     reap_stop = 0;
     if (pthread_create(&reap_thread, NULL, reaper, NULL) != 0) return -1;
     reap_running = 1;
@@ -624,6 +925,20 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     ATOM_WRITE = enif_make_atom(env, "write");
     ATOM_DELETE_OBJECT = enif_make_atom(env, "delete_object");
     ATOM_EMQX_TM_MATCH = enif_make_atom(env, "emqx_tm_match");
+    ATOM_ALLOW = enif_make_atom(env, "allow");
+    ATOM_DENY = enif_make_atom(env, "deny");
+    ATOM_NOMATCH = enif_make_atom(env, "nomatch");
+    ATOM_NONE = enif_make_atom(env, "none");
+    ATOM_ALL = enif_make_atom(env, "all");
+    ATOM_CLIENT = enif_make_atom(env, "client");
+    ATOM_USER = enif_make_atom(env, "user");
+    ATOM_IPADDR = enif_make_atom(env, "ipaddr");
+    ATOM_AND = enif_make_atom(env, "and");
+    ATOM_OR = enif_make_atom(env, "or");
+    ATOM_EQ = enif_make_atom(env, "eq");
+    ATOM_PUBLISH = enif_make_atom(env, "publish");
+    ATOM_SUBSCRIBE = enif_make_atom(env, "subscribe");
+    ATOM_PUBSUB = enif_make_atom(env, "pubsub");
     return 0;
 }
 
@@ -645,6 +960,8 @@ static ErlNifFunc funcs[] = {
     {"match_routes_batch", 2, nif_match_routes_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"rules_match", 4, nif_rules_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"topic_match", 2, nif_topic_match, 0},
+    {"acl_new", 2, nif_acl_new, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"acl_check", 4, nif_acl_check, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 /* the reaper destroys what is queued, then exits */

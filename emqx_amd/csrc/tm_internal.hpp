@@ -331,10 +331,58 @@ struct RulesArgs {
     uint32_t* bits;
 };
 
+// Batched ACL check (tm_acl_check).  The compiled rule set is one flat block of
+// u32 words followed by bytes (tm_acl.cpp builds it, the kernel reads it with
+// wave-uniform addresses):
+//   rule j    blk[ACL_HDR + ACL_RULE_W * j ..]: flags (allow | access << 8 |
+//             is_all << 16), who program (word index, word count), topic
+//             table (word index, entry count)
+//   topic     ACL_TOPIC_W words: byte offset of the filter in the block, its
+//             length | eq << 31, level table (word index, entry count)
+//   level     one word: start in the filter | length << 13 | kind << 26 |
+//             last << 29
+//   who       postfix program over a 32-bit stack of booleans: 'and' / 'or'
+//             fold their children into an accumulator pushed first
+//             (lists:foldl, src/emqx_access_rule.erl:115-122), so the stack
+//             holds one bit per nesting level.  op word = op | operand << 4;
+//             CLIENT / USER: operand = length, next word = byte offset;
+//             IPADDR: operand = family, next 8 words = lo, hi as four
+//             big-endian u32 each.
+constexpr uint32_t ACL_HDR = 4;
+constexpr uint32_t ACL_RULE_W = 5;
+constexpr uint32_t ACL_TOPIC_W = 4;
+constexpr uint32_t ACL_EQ = 1u << 31;
+enum : uint32_t { ACL_L_LIT = 0, ACL_L_PLUS = 1, ACL_L_HASH = 2, ACL_L_VARC = 3, ACL_L_VARU = 4 };
+constexpr uint32_t ACL_L_LEN_SHIFT = 13, ACL_L_KIND_SHIFT = 26, ACL_L_LAST = 1u << 29, ACL_L_MASK = 0x1FFF;
+enum : uint32_t { ACL_OP_TRUE = 0, ACL_OP_FALSE = 1, ACL_OP_CLIENT = 2, ACL_OP_USER = 3, ACL_OP_IPADDR = 4,
+                  ACL_OP_AND = 5, ACL_OP_OR = 6 };
+constexpr uint32_t ACL_NOMATCH = 2;      // TM_ACL_NOMATCH (a rule's allow bit is TM_ACL_DENY / TM_ACL_ALLOW)
+constexpr uint32_t ACL_STAGE = 16384;   // LDS budget for one block's name bytes
+struct AclArgs {
+    const uint32_t* blk;       // the compiled rule set
+    uint32_t n_rules;
+    const uint8_t* topics;     // the slice's name bytes, 16-B aligned, 16 B of padding behind them
+    const uint64_t* offs;      // n + 1 (offsets of the whole batch; base is subtracted)
+    uint64_t base;
+    const uint32_t* client_of; // n
+    const uint8_t* access;     // n
+    uint32_t n;
+    const uint8_t* cid;        // clients
+    const uint64_t* cid_off;
+    const uint8_t* usr;
+    const uint64_t* usr_off;
+    const uint8_t* cflags;
+    const uint8_t* cfamily;
+    const uint4* peer;
+    uint8_t* verdict;          // n
+    uint32_t* rule;            // n
+};
+
 // text of the last TM_EIO on this thread (tm_last_error), shared by the C++ modules
 char* error_buf();
 
 // kernel launchers (tm_kernels.hip)
+hipError_t launch_acl_check(const AclArgs& a, hipStream_t s);
 hipError_t launch_rules_match(const RulesArgs& a, hipStream_t s);
 hipError_t launch_gather_rows(const uint32_t* src, const int64_t* src_off, const int64_t* idx, uint32_t n,
                               const int64_t* dst_off, uint32_t* dst, hipStream_t s);

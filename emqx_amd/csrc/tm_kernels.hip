@@ -1890,6 +1890,192 @@ __global__ __launch_bounds__(256) void tm_rules_match(RulesArgs a) {
     }
 }
 
+// ------------------------------------------------ batched ACL check (tm_acl_check)
+
+// a >= b over four big-endian words (an address in network order)
+__device__ __forceinline__ bool acl_ip_ge(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint32_t b0,
+                                          uint32_t b1, uint32_t b2, uint32_t b3) {
+    return a0 != b0 ? a0 > b0 : a1 != b1 ? a1 > b1 : a2 != b2 ? a2 > b2 : a3 >= b3;
+}
+
+// match_who/2 (src/emqx_access_rule.erl:101-124) of client c over the rule's
+// postfix program blk[pc .. pe): every lane of the wave runs the same ops
+// (uniform reads), only the client's bytes differ per lane.
+__device__ __forceinline__ bool acl_who(const AclArgs& a, const uint8_t* bb, uint32_t pc, uint32_t pe, uint32_t c,
+                                        uint32_t cf) {
+    uint32_t st = 0;
+    while (pc < pe) {
+        const uint32_t w = a.blk[pc], op = w & 15u, arg = w >> 4;
+        if (op == ACL_OP_TRUE || op == ACL_OP_FALSE) {
+            st = (st << 1) | (op == ACL_OP_TRUE ? 1u : 0u);
+            pc += 1;
+        } else if (op == ACL_OP_CLIENT || op == ACL_OP_USER) {
+            // binary equality; an undefined field equals no binary (:107-110)
+            const bool isc = op == ACL_OP_CLIENT;
+            const uint8_t* v = bb + a.blk[pc + 1];
+            bool ok = (cf & (isc ? 1u : 2u)) != 0;
+            if (ok) {
+                const uint64_t* off = isc ? a.cid_off : a.usr_off;
+                const uint64_t o = off[c], l = off[c + 1] - o;
+                const uint8_t* p = (isc ? a.cid : a.usr) + o;
+                ok = l == arg;
+                for (uint32_t i = 0; ok && i < arg; ++i) ok = p[i] == v[i];
+            }
+            st = (st << 1) | (ok ? 1u : 0u);
+            pc += 2;
+        } else if (op == ACL_OP_IPADDR) {
+            // Start =< IP =< End within one family; peerhost undefined -> false (:111-114)
+            bool ok = a.cfamily[c] == arg;
+            if (ok) {
+                const uint4 q = a.peer[c];
+                const uint32_t i0 = __builtin_bswap32(q.x), i1 = __builtin_bswap32(q.y), i2 = __builtin_bswap32(q.z),
+                               i3 = __builtin_bswap32(q.w);
+                ok = acl_ip_ge(i0, i1, i2, i3, a.blk[pc + 1], a.blk[pc + 2], a.blk[pc + 3], a.blk[pc + 4]) &&
+                     acl_ip_ge(a.blk[pc + 5], a.blk[pc + 6], a.blk[pc + 7], a.blk[pc + 8], i0, i1, i2, i3);
+            }
+            st = (st << 1) | (ok ? 1u : 0u);
+            pc += 9;
+        } else {   // AND / OR: fold the child on top into the accumulator below it (:115-122)
+            const uint32_t b = st & 1u;
+            st >>= 1;
+            st = op == ACL_OP_AND ? (st & (~1u | b)) : (st | b);
+            pc += 1;
+        }
+    }
+    return (st & 1u) != 0;
+}
+
+// One lane = one request, the rules in list order: the access mask
+// (emqx_mod_acl_internal:filter/2, src/emqx_mod_acl_internal.erl:110-121), the
+// who program, then the name's bytes against each filter level by level --
+// emqx_topic:match/2 on word lists (src/emqx_topic.erl:74-87: an equal word or
+// a '+' filter word advances, a last '#' takes the rest, both exhausted
+// match; no '$' rule), where a level is a word and words compare as bytes
+// except that a %c / %u level holding the client's id / name (feed_var,
+// src/emqx_access_rule.erl:141-154) is a binary and so never equals the atoms
+// '' / '+' / '#' of the name.  {eq, T} is byte equality of the whole topic.
+// The first matching rule decides (src/emqx_mod_acl_internal.erl:82-90); the
+// wave leaves the rule loop once every lane has decided.  LDS: the block's
+// names were staged into sm (name bytes at sm + (o - a0)); otherwise they are
+// read from global memory.
+template <bool LDS>
+__device__ __forceinline__ void acl_lane(const AclArgs& a, const uint8_t* sm, uint64_t a0, uint32_t t) {
+    const bool active = t < a.n;
+    uint32_t nlen = 0, c = 0, acc = 0, cf = 0;
+    uint64_t o = a0;
+    if (active) {
+        o = a.offs[t] - a.base;
+        nlen = (uint32_t)(a.offs[t + 1] - a.offs[t]);
+        c = a.client_of[t];
+        acc = a.access[t];
+        cf = a.cflags[c];
+    }
+    const uint8_t* ns = sm + (uint32_t)(o - a0);
+    const uint8_t* ng = a.topics + o;
+    auto nb = [&](uint32_t i) -> uint32_t { return LDS ? ns[i] : ng[i]; };
+    // the name level at pos is exactly the l bytes at p (a level holds no '/':
+    // a client id with one is one word and equals no level)
+    auto level_is = [&](uint32_t pos, const uint8_t* p, uint32_t l) -> bool {
+        if (pos + l > nlen) return false;
+        if (pos + l < nlen && nb(pos + l) != '/') return false;
+        for (uint32_t i = 0; i < l; ++i) {
+            const uint32_t b = p[i];
+            if (b == '/' || nb(pos + i) != b) return false;
+        }
+        return true;
+    };
+    const uint8_t* bb = reinterpret_cast<const uint8_t*>(a.blk);
+    uint32_t verdict = ACL_NOMATCH, rule = NONE;
+    bool decided = !active;
+    for (uint32_t j = 0; j < a.n_rules; ++j) {
+        if (__ballot(!decided) == 0ull) break;
+        const uint32_t* rw = a.blk + ACL_HDR + ACL_RULE_W * j;
+        const uint32_t flags = rw[0];
+        if (decided) continue;
+        bool m = (flags >> 16) & 1u;                       // {A, all}
+        if (!m && (((flags >> 8) & 3u) & acc) && acl_who(a, bb, rw[1], rw[1] + rw[2], c, cf)) {
+            const uint32_t ntop = rw[4];
+            for (uint32_t f = 0; f < ntop && !m; ++f) {
+                const uint32_t* tw = a.blk + rw[3] + ACL_TOPIC_W * f;
+                const uint8_t* fb = bb + tw[0];
+                const uint32_t flen = tw[1] & ~ACL_EQ;
+                if (tw[1] & ACL_EQ) {
+                    m = flen == nlen;
+                    for (uint32_t i = 0; m && i < flen; ++i) m = nb(i) == fb[i];
+                    continue;
+                }
+                const uint32_t nlev = tw[3];
+                uint32_t pos = 0;
+                bool have = true;                          // the name has a level at pos
+                bool done = false;
+                for (uint32_t k = 0; k < nlev; ++k) {
+                    const uint32_t lv = a.blk[tw[2] + k];
+                    const uint32_t kind = (lv >> ACL_L_KIND_SHIFT) & 7u;
+                    uint32_t l = (lv >> ACL_L_LEN_SHIFT) & ACL_L_MASK;
+                    const uint8_t* p = fb + (lv & ACL_L_MASK);
+                    bool adv = false;
+                    if (have) {
+                        if (kind == ACL_L_PLUS) {
+                            uint32_t e = pos;
+                            while (e < nlen && nb(e) != '/') ++e;
+                            l = e - pos;
+                            adv = true;
+                        } else {
+                            bool ok = true;
+                            const bool vc = kind == ACL_L_VARC && (cf & 1u), vu = kind == ACL_L_VARU && (cf & 2u);
+                            if (vc || vu) {
+                                const uint64_t* off = vc ? a.cid_off : a.usr_off;
+                                const uint64_t vo = off[c], vl = off[c + 1] - vo;
+                                p = (vc ? a.cid : a.usr) + vo;
+                                l = (uint32_t)(vl < 0xFFFFull ? vl : 0xFFFFull);
+                                // the name's '' / '+' / '#' levels are atoms, the value a binary
+                                ok = l > 1u || (l == 1u && p[0] != '+' && p[0] != '#');
+                            }
+                            adv = ok && level_is(pos, p, l);
+                        }
+                    }
+                    if (adv) {
+                        if (pos + l == nlen) have = false;
+                        else pos += l + 1u;
+                        continue;
+                    }
+                    m = kind == ACL_L_HASH && (lv & ACL_L_LAST);
+                    done = true;
+                    break;
+                }
+                if (!done) m = !have;
+            }
+        }
+        if (m) {
+            decided = true;
+            verdict = flags & 1u;
+            rule = j;
+        }
+    }
+    if (active) {
+        a.verdict[t] = (uint8_t)verdict;
+        a.rule[t] = rule;
+    }
+}
+
+__global__ __launch_bounds__(256) void tm_acl_check(AclArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t sm[ACL_STAGE + 16];
+    const uint32_t t0 = blockIdx.x * 256u, t1 = min(a.n, t0 + 256u);
+    // the block's names are one contiguous byte range
+    const uint64_t b0 = a.offs[t0] - a.base, b1 = a.offs[t1] - a.base;
+    const uint64_t a0 = b0 & ~15ull;
+    if (b1 - a0 <= ACL_STAGE) {
+        const uint32_t nv = (uint32_t)((b1 - a0 + 15u) >> 4);
+        const uint4* src = reinterpret_cast<const uint4*>(a.topics + a0);
+        uint4* dst = reinterpret_cast<uint4*>(sm);
+        for (uint32_t i = threadIdx.x; i < nv; i += 256u) dst[i] = src[i];
+        __syncthreads();
+        acl_lane<true>(a, sm, a0, t0 + threadIdx.x);
+    } else {
+        acl_lane<false>(a, sm, a0, t0 + threadIdx.x);
+    }
+}
+
 // ------------------------------------------------ device dedup (TM_BATCH_DEDUP)
 
 // 8 bytes at byte offset s of a 4-aligned LDS array (any alignment of s)
@@ -3293,6 +3479,11 @@ uint32_t fan_fill_tile() { return FAN_FILL_TILE; }
 
 hipError_t launch_rules_match(const RulesArgs& a, hipStream_t s) {
     if (a.n) hipLaunchKernelGGL(tm_rules_match, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_acl_check(const AclArgs& a, hipStream_t s) {
+    if (a.n) hipLaunchKernelGGL(tm_acl_check, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

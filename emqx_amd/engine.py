@@ -413,6 +413,41 @@ class Group:
         return C.string_at(p, n.value)
 
 
+def _acl_check(L, rc, what):
+    if rc == N.TM_EINVAL:   # the ACL calls say which rule / request was refused
+        raise N.TmError(rc, what + " [" + (L.tm_last_error() or b"").decode(errors="replace") + "]")
+    return N.check(rc, what)
+
+
+class Acl:
+    """A compiled, immutable rule set on the engine's devices (tm_acl)."""
+
+    def __init__(self, engine: "Engine", h, n_rules: int):
+        self.engine, self._h, self.n_rules = engine, h, n_rules
+
+    @property
+    def h(self):
+        if self._h is None:
+            raise RuntimeError("rule set is closed (or its engine was)")
+        return self._h
+
+    @property
+    def kernel_ms(self) -> float:
+        """Device time of the last acl_check's kernel."""
+        return float(self.engine.L.tm_acl_kernel_ms(self.engine.h, self.h))
+
+    def close(self):
+        if self._h is not None:
+            self.engine.L.tm_acl_free(self.engine.h, self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     def __init__(self, device: int = 0, init_slots: int = 0, host_threads: int = 0, frozen_dict: bool = False,
                  host_tokenize: bool = False, devices=None):
@@ -462,6 +497,8 @@ class Engine:
 
     def close(self):
         if getattr(self, "_h", None):
+            for a in list(getattr(self, "_acls", ())):   # rule sets hold device memory of this engine
+                a.close()
             if getattr(self, "_owned", True):
                 self.L.tm_destroy(self._h)
             self._h = None
@@ -669,6 +706,40 @@ class Engine:
                                       int(dollar_rule), bits.ctypes.data), "tm_rules_match")
         b = np.unpackbits(bits.view(np.uint8).reshape(n, wpr * 4), axis=1, bitorder="little")
         return b[:, :r].astype(bool)
+
+    # ---- batched emqx_access_control:check_acl/3 -----------------------------
+    def acl_create(self, rules) -> "Acl":
+        """Compiles an ordered rule list (emqx_access_rule terms, as
+        emqx_mod_acl_internal.rules takes them) into a device rule set."""
+        from . import acl as A
+        from . import emqx_access_rule as AR
+        arr, keep = A.encode_rules([AR.compile(r) for r in rules])
+        h = C.c_void_p()
+        _acl_check(self.L, self.L.tm_acl_create(self.h, arr, len(rules), C.byref(h)), "tm_acl_create")
+        del keep
+        a = Acl(self, h, len(rules))
+        self.__dict__.setdefault("_acls", weakref.WeakSet()).add(a)
+        return a
+
+    def acl_check(self, acl: "Acl", clients, requests, nomatch=None):
+        """requests = [(client index, "publish" | "subscribe", topic)] against the
+        rule set -> (verdict u8[n], rule u32[n]): TM_ACL_ALLOW / _DENY /
+        _NOMATCH and the index of the deciding rule (TM_NONE on nomatch).
+        nomatch = "allow" | "deny" folds the zone's acl_nomatch default into
+        the verdicts (emqx_access_control:do_check_acl/3)."""
+        from . import acl as A
+        n = len(requests)
+        verdict = np.full(n, N.TM_ACL_NOMATCH, np.uint8)
+        rule = np.full(n, N.TM_NONE, np.uint32)
+        cs, keep = A.encode_clients(clients)
+        buf, offs, cof, acc = A.encode_requests(requests)
+        _acl_check(self.L, self.L.tm_acl_check(self.h, acl.h, C.byref(cs), buf.ctypes.data, offs.ctypes.data,
+                                               cof.ctypes.data, acc.ctypes.data, n, verdict.ctypes.data,
+                                               rule.ctypes.data), "tm_acl_check")
+        del keep
+        if nomatch is not None:
+            verdict[verdict == N.TM_ACL_NOMATCH] = N.TM_ACL_ALLOW if nomatch == "allow" else N.TM_ACL_DENY
+        return verdict, rule
 
     # ---- bulk load / filter-sharded mode -----------------------------------
     def insert_many(self, filters, shard: int = 0, nshards: int = 1) -> int:

@@ -24,6 +24,10 @@
         , dispatch_batch/2
         , match_routes_batch/2
         , rules_match/4
+        , acl_new/2
+        , acl_load/2
+        , acl_check/4
+        , check_acl/4
         ]).
 
 -on_load(init/0).
@@ -123,3 +127,55 @@ match_routes_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
 %% rewrite / tracer filters: true); per name the indices of the matching rules.
 -spec(rules_match(reference(), [binary()], [binary()], boolean()) -> [[non_neg_integer()]]).
 rules_match(_Engine, _Names, _Rules, _DollarRule) -> erlang:nif_error(nif_not_loaded).
+
+%% A compiled, immutable ACL rule set on the engine's devices.  Rules in the
+%% NIF's form: {A, all} | {A, Who, Access, [Topic | {eq, Topic}]} with binary
+%% topics and Who as emqx_access_rule:compile/1 leaves it (ipaddr as
+%% {ipaddr, {Start, End, Len}}); acl_load/2 makes them from acl.conf terms.
+-spec(acl_new(reference(), list()) -> {ok, reference()} | {error, term()}).
+acl_new(_Engine, _Rules) -> erlang:nif_error(nif_not_loaded).
+
+%% The terms of etc/acl.conf (file:consult/1) -> a rule set, in the file's
+%% order: emqx_mod_acl_internal:rules_from_file/1 (src/emqx_mod_acl_internal.erl:
+%% 92-98) with the publish/subscribe split left to the device's access mask.
+-spec(acl_load(reference(), [emqx_access_rule:rule()]) -> {ok, reference()} | {error, term()}).
+acl_load(Engine, Terms) ->
+    acl_new(Engine, [acl_rule(emqx_access_rule:compile(Term)) || Term <- Terms]).
+
+acl_rule({A, all}) -> {A, all};
+acl_rule({A, Who, Access, Topics}) -> {A, Who, Access, [acl_topic(T) || T <- Topics]}.
+
+%% compiled topics are word lists: the device takes their bytes
+acl_topic({eq, Words}) -> {eq, emqx_topic:join(Words)};
+acl_topic({pattern, Words}) -> emqx_topic:join(Words);
+acl_topic(Words) -> emqx_topic:join(Words).
+
+%% emqx_mod_acl_internal:check_acl/5 for a batch: Clients =
+%% [{ClientId | undefined, Username | undefined, PeerHost | undefined}],
+%% Requests = [{ClientIndex (0-based), publish | subscribe, Topic}] ->
+%% [{allow | deny | nomatch, RuleIndex | none}].
+-spec(acl_check(reference(), reference(), list(), list()) -> list() | {error, term()}).
+acl_check(_Engine, _Acl, _Clients, _Requests) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_access_control:check_acl/3 (src/emqx_access_control.erl:47-67, no ACL
+%% cache) for a batch of {ClientInfo, PubSub, Topic}: nomatch falls to the
+%% zone's acl_nomatch, anything but allow denies.  Any other PubSub sees no
+%% rule (emqx_mod_acl_internal:lookup/2).
+-spec(check_acl(reference(), reference(), [{map(), atom(), binary()}], allow | deny) -> [allow | deny]).
+check_acl(Engine, Acl, Requests, AclNomatch) ->
+    Default = case AclNomatch of allow -> allow; _ -> deny end,
+    Known = [R || R = {_, PubSub, _} <- Requests, PubSub =:= publish orelse PubSub =:= subscribe],
+    Clients = [{maps:get(clientid, CI, undefined), maps:get(username, CI, undefined),
+                maps:get(peerhost, CI, undefined)} || {CI, _, _} <- Known],
+    Reqs = [{I, PubSub, Topic} || {I, {_, PubSub, Topic}} <- lists:zip(lists:seq(0, length(Known) - 1), Known)],
+    case acl_check(Engine, Acl, Clients, Reqs) of
+        {error, _} = Error -> Error;
+        Results -> acl_fold(Requests, Results, Default)
+    end.
+
+acl_fold([], [], _Default) -> [];
+acl_fold([{_, PubSub, _} | Reqs], [{Verdict, _Rule} | Results], Default)
+  when PubSub =:= publish; PubSub =:= subscribe ->
+    [case Verdict of nomatch -> Default; allow -> allow; deny -> deny end | acl_fold(Reqs, Results, Default)];
+acl_fold([_ | Reqs], Results, Default) ->
+    [Default | acl_fold(Reqs, Results, Default)].

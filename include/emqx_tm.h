@@ -130,7 +130,7 @@ TM_API int  tm_create(const tm_config* cfg, tm_engine** out);
  * is made once and its delta uploaded to every replica, so filter ids are the
  * same everywhere.  Per-publish calls (tm_match_async / tm_match_coalesced)
  * are dealt over the replicas; whole-batch calls (tm_match_batch,
- * tm_match_routes_batch, tm_rules_match) of 65,536+ publishes are split into
+ * tm_match_routes_batch, tm_rules_match, tm_acl_check) of 65,536+ publishes are split into
  * one contiguous slice per replica and their results concatenated (no
  * collective); a fresh tm_batch goes to the next replica round-robin, or to
  * the one named by tm_batch_prepare_on.  n_devices = 0: host-only engine. */
@@ -559,6 +559,91 @@ TM_API int  tm_topic_validate(int is_name, const uint8_t* topic, size_t len, con
 TM_API int  tm_rules_match(tm_engine* e, const uint8_t* names, const uint64_t* name_offsets, uint32_t n,
                            const uint8_t* rules, const uint64_t* rule_offsets, uint32_t r, int dollar_rule,
                            uint32_t* bits);
+
+/* ---- ACL check: emqx_access_control:check_acl/3 on the device ---------- */
+/* A batch of (client, access, topic) requests against one ordered rule list:
+ * emqx_mod_acl_internal:check_acl/5 (src/emqx_mod_acl_internal.erl:69-121)
+ * over compiled emqx_access_rule rules (src/emqx_access_rule.erl:43-154) --
+ * the who clause, the publish/subscribe split as a per-rule mask, pattern
+ * filters (a %c / %u level takes the client's id / name as ONE word that is
+ * never an atom; an undefined field leaves the level a literal), {eq, T}
+ * filters (byte equality), emqx_topic:match/2 in its word-list form (no '$'
+ * rule, src/emqx_topic.erl:74-87) and the first-match-wins fold.  One kernel,
+ * from the raw topic bytes; nothing is tokenised on the host. */
+#define TM_ACL_DENY      0u
+#define TM_ACL_ALLOW     1u
+#define TM_ACL_NOMATCH   2u      /* verdict only: falls to the zone's acl_nomatch */
+#define TM_ACL_PUBLISH   1u      /* request access, and rule access: */
+#define TM_ACL_SUBSCRIBE 2u
+#define TM_ACL_PUBSUB    3u      /* rules only; rule access 0 = {A, all} (who and topics ignored) */
+#define TM_WHO_ALL        0u
+#define TM_WHO_CLIENT_ALL 1u
+#define TM_WHO_USER_ALL   2u
+#define TM_WHO_CLIENT     3u
+#define TM_WHO_USER       4u
+#define TM_WHO_IPADDR     5u
+#define TM_WHO_AND        6u
+#define TM_WHO_OR         7u
+#define TM_ACL_MAX_WHO_DEPTH 32u  /* a leaf is depth 1, 'and' / 'or' 1 + its deepest child */
+/* A who expression as a pre-order node array: AND / OR carry the count of
+ * their direct children, which follow (each with its own subtree). */
+typedef struct {
+    uint32_t       kind;         /* TM_WHO_* */
+    uint32_t       n_children;   /* AND / OR */
+    const uint8_t* val;          /* CLIENT / USER: the binary */
+    uint32_t       val_len;
+    uint8_t        family;       /* IPADDR: 4 | 6 */
+    uint8_t        lo[16];       /* IPADDR: inclusive range, network order (IPv4 in the first 4 bytes) */
+    uint8_t        hi[16];
+} tm_acl_who;
+typedef struct {
+    const uint8_t* filter;
+    uint32_t       len;          /* <= TM_MAX_TOPIC_LEN */
+    uint32_t       eq;           /* 1: {eq, Topic} -- literal, no pattern */
+} tm_acl_topic;
+typedef struct {
+    uint32_t            allow;     /* TM_ACL_DENY | TM_ACL_ALLOW */
+    uint32_t            access;    /* 0 | TM_ACL_PUBLISH | TM_ACL_SUBSCRIBE | TM_ACL_PUBSUB */
+    const tm_acl_who*   who;
+    uint32_t            n_who;     /* nodes of the who array (exactly one tree) */
+    const tm_acl_topic* topics;
+    uint32_t            n_topics;  /* 0: the rule never matches (src/emqx_access_rule.erl:126-127) */
+} tm_acl_rule;
+typedef struct {
+    uint32_t        m;
+    const uint8_t*  clientids;         /* concatenated */
+    const uint64_t* clientid_offsets;  /* m + 1 */
+    const uint8_t*  usernames;
+    const uint64_t* username_offsets;  /* m + 1 */
+    const uint8_t*  flags;             /* m: bit 0 clientid defined, bit 1 username defined */
+    const uint8_t*  family;            /* m: 0 peerhost undefined | 4 | 6 */
+    const uint8_t*  peerhost;          /* 16 B per client, network order (IPv4 in the first 4 bytes) */
+} tm_acl_clients;
+typedef struct tm_acl tm_acl;
+/* Compiles the n rules on the host into one flat block (rule table, who
+ * programs in postfix form, filter bytes with per-level kinds) and uploads it
+ * to every replica of the engine; the handle is immutable (a reload creates a
+ * new one and frees the old; no lock is shared with the trie) and must be
+ * freed before the engine is destroyed.  Works on a host-only engine (no
+ * upload).  TM_EINVAL + tm_last_error(): allow > 1, access > 3, a who array
+ * that is not exactly one tree, who nesting deeper than TM_ACL_MAX_WHO_DEPTH
+ * (the device evaluates who over a 32-bit stack), an unknown who kind, an
+ * IPADDR family other than 4 / 6, a filter longer than TM_MAX_TOPIC_LEN. */
+TM_API int  tm_acl_create(tm_engine* e, const tm_acl_rule* rules, uint32_t n, tm_acl** out);
+TM_API void tm_acl_free(tm_engine* e, tm_acl* acl);
+/* Request i = (clients[client_of[i]], access[i], topic i); topics / offsets as
+ * in tm_match_batch.  verdict[i] = TM_ACL_ALLOW / _DENY / _NOMATCH, rule[i] =
+ * index of the deciding rule in the list given to tm_acl_create, TM_NONE on
+ * nomatch.  TM_EINVAL + tm_last_error(): a name longer than TM_MAX_TOPIC_LEN,
+ * client_of[i] >= m, access[i] not TM_ACL_PUBLISH / TM_ACL_SUBSCRIBE, a
+ * client family not 0 / 4 / 6.  TM_ENODEV on a host-only engine.  On an
+ * engine with several replicas a batch of 65,536+ requests is split over them. */
+TM_API int  tm_acl_check(tm_engine* e, tm_acl* acl, const tm_acl_clients* clients, const uint8_t* topics,
+                         const uint64_t* offsets, const uint32_t* client_of, const uint8_t* access, uint32_t n,
+                         uint8_t* verdict, uint32_t* rule);
+/* Device time (HIP events) of the kernel of the last tm_acl_check on this
+ * handle, the slowest slice of a split batch; 0 before the first. */
+TM_API float tm_acl_kernel_ms(tm_engine* e, tm_acl* acl);
 
 /* ---- replicated multi-device group (BASELINE config C3) --------------- */
 /* A view of one tm_create_replicated engine (tm_group_engine(g, i) returns it
