@@ -81,6 +81,22 @@ TM_DISPATCH_MATCH_OFFSETS = 2
 TM_DISPATCH_DEVICE = 4
 
 
+TM_SHARED_RANDOM, TM_SHARED_ROUND_ROBIN, TM_SHARED_HASH = 0, 1, 2
+TM_SHARED_COUNT_ONLY = 1
+TM_SHARED_DEVICE = 2
+SHARED_STRATEGIES = {"random": TM_SHARED_RANDOM, "round_robin": TM_SHARED_ROUND_ROBIN, "hash": TM_SHARED_HASH}
+
+
+class SharedOpts(C.Structure):
+    _fields_ = [("strategy", C.c_uint32), ("flags", C.c_uint32), ("keys", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class SharedDeliveries(C.Structure):
+    _fields_ = [("n_topics", C.c_uint32), ("n_deliveries", C.c_uint64), ("row_offsets", C.POINTER(C.c_uint32)),
+                ("filter_ids", C.POINTER(C.c_uint32)), ("groups", C.POINTER(C.c_uint32)),
+                ("subscribers", C.POINTER(C.c_uint32)), ("kernel_ms", C.c_float)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -221,6 +237,11 @@ SIGNATURES = {
     "tm_topic_wildcard": (C.c_int, [U8P, SZ]),
     "tm_topic_validate": (C.c_int, [C.c_int, U8P, SZ, C.POINTER(C.c_char_p)]),
     "tm_rules_match": (C.c_int, [P, P, P, C.c_uint32, P, P, C.c_uint32, C.c_int, P]),
+    "tm_shared_subscribe": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32]),
+    "tm_shared_unsubscribe": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32]),
+    "tm_shared_member_down": (C.c_int, [P, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "tm_shared_members": (C.c_int, [P, U8P, SZ, C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "tm_batch_dispatch_shared": (C.c_int, [P, P, C.POINTER(SharedOpts), C.POINTER(SharedDeliveries)]),
     "tm_acl_create": (C.c_int, [P, C.POINTER(AclRule), C.c_uint32, C.POINTER(P)]),
     "tm_acl_free": (None, [P, P]),
     "tm_acl_check": (C.c_int, [P, P, C.POINTER(AclClients), P, P, P, P, C.c_uint32, P, P]),

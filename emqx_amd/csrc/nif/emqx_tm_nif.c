@@ -42,7 +42,7 @@ static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_TRUE, ATOM_FALSE, ATOM_UNDEFINED, 
     ATOM_TRIE_NODE, ATOM_NODE_NOT_FOUND, ATOM_ENOMEM, ATOM_EIO, ATOM_EINVAL, ATOM_ENODEV,
     ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH,
     ATOM_ALLOW, ATOM_DENY, ATOM_NOMATCH, ATOM_NONE, ATOM_ALL, ATOM_CLIENT, ATOM_USER, ATOM_IPADDR, ATOM_AND, ATOM_OR,
-    ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB;
+    ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB, ATOM_RANDOM, ATOM_ROUND_ROBIN, ATOM_HASH;
 
 /* set while a match callback runs on the engine's completion thread */
 static __thread int in_engine_callback;
@@ -563,6 +563,122 @@ static ERL_NIF_TERM nif_match_routes_batch(ErlNifEnv* env, int argc, const ERL_N
     return out;
 }
 
+/* shared_subscribe(Engine, Topic, GroupDestId, SubId) -> ok
+ * emqx_shared_sub's handle_call({subscribe, Group, Topic, SubPid})
+ * (src/emqx_shared_sub.erl:297-305): the first member of (Group, Topic) also
+ * adds the (Topic, Group) route; a repeated member is a no-op. */
+static ERL_NIF_TERM nif_shared_subscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    ErlNifBinary b;
+    unsigned group, sub;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &b) ||
+        !enif_get_uint(env, argv[2], &group) || !enif_get_uint(env, argv[3], &sub))
+        return enif_make_badarg(env);
+    int rc = tm_shared_subscribe(r->e, b.data, b.size, group, sub);
+    return rc ? err(env, rc) : ATOM_OK;
+}
+
+/* shared_unsubscribe(Engine, Topic, GroupDestId, SubId) -> ok  (:307-315; not a
+ * member -> ok, a delete_object of no record) */
+static ERL_NIF_TERM nif_shared_unsubscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    ErlNifBinary b;
+    unsigned group, sub;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &b) ||
+        !enif_get_uint(env, argv[2], &group) || !enif_get_uint(env, argv[3], &sub))
+        return enif_make_badarg(env);
+    int rc = tm_shared_unsubscribe(r->e, b.data, b.size, group, sub);
+    return (rc && rc != TM_ENOENT) ? err(env, rc) : ATOM_OK;
+}
+
+/* shared_member_down(Engine, SubId) -> {ok, NRemoved}  (cleanup_down/1, :358-367) */
+static ERL_NIF_TERM nif_shared_member_down(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    unsigned sub;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_get_uint(env, argv[1], &sub)) return enif_make_badarg(env);
+    uint64_t n = 0;
+    int rc = tm_shared_member_down(r->e, sub, &n);
+    return rc ? err(env, rc) : enif_make_tuple2(env, ATOM_OK, enif_make_uint64(env, n));
+}
+
+/* shared_dispatch_batch(Engine, [Topic], random | round_robin | hash, Keys | Seed)
+ *   -> [[{To, GroupDestId, SubId}]]
+ * emqx_shared_sub:dispatch/3 for every {To, Group} route of every publish
+ * (src/emqx_broker.erl:245-248, src/emqx_shared_sub.erl:110-125, 260-275): one
+ * picked member per (publish, matched filter, group).  hash: the 4th argument
+ * is the list of erlang:phash2(ClientId), one integer per publish; random: the
+ * seed (an unsigned 32-bit integer here); round_robin ignores it. */
+static ERL_NIF_TERM nif_shared_dispatch_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    unsigned n, nk = 0, seed = 0;
+    uint8_t* buf;
+    uint64_t* offs;
+    uint32_t* keys = NULL;
+    tm_shared_opts o;
+    (void)argc;
+    memset(&o, 0, sizeof o);
+    if (enif_compare(argv[2], ATOM_RANDOM) == 0) o.strategy = TM_SHARED_RANDOM;
+    else if (enif_compare(argv[2], ATOM_ROUND_ROBIN) == 0) o.strategy = TM_SHARED_ROUND_ROBIN;
+    else if (enif_compare(argv[2], ATOM_HASH) == 0) o.strategy = TM_SHARED_HASH;
+    else return enif_make_badarg(env);
+    if (!get_engine(env, argv[0], &r)) return enif_make_badarg(env);
+    if (o.strategy == TM_SHARED_HASH) {
+        if (!enif_get_list_length(env, argv[3], &nk)) return enif_make_badarg(env);
+        keys = enif_alloc(sizeof(uint32_t) * (nk ? nk : 1));
+        ERL_NIF_TERM l = argv[3], h;
+        for (unsigned i = 0; i < nk; ++i) {
+            unsigned k;
+            if (!enif_get_list_cell(env, l, &h, &l) || !enif_get_uint(env, h, &k)) {
+                enif_free(keys);
+                return enif_make_badarg(env);
+            }
+            keys[i] = k;
+        }
+    } else if (o.strategy == TM_SHARED_RANDOM && !enif_get_uint(env, argv[3], &seed)) {
+        return enif_make_badarg(env);
+    }
+    if (!pack_binaries(env, argv[1], &n, &buf, &offs)) {
+        if (keys) enif_free(keys);
+        return enif_make_badarg(env);
+    }
+    if (keys && nk != n) {   /* one key per publish */
+        enif_free(keys); enif_free(buf); enif_free(offs);
+        return enif_make_badarg(env);
+    }
+    o.keys = keys;
+    o.seed = seed;
+    tm_batch* b;
+    tm_shared_deliveries d;
+    packed p;
+    int rc = run_batch(r->e, buf, offs, n, &b);
+    enif_free(buf); enif_free(offs);
+    if (!rc) rc = tm_batch_dispatch_shared(r->e, b, &o, &d);
+    if (keys) enif_free(keys);
+    if (!rc) rc = pack_filters(r->e, d.filter_ids, d.n_deliveries, &p);
+    if (rc) {
+        if (b) tm_batch_free(r->e, b);
+        return err(env, rc);
+    }
+    ERL_NIF_TERM out = enif_make_list(env, 0);
+    uint32_t k = p.n;
+    for (unsigned i = n; i-- > 0;) {
+        ERL_NIF_TERM row = enif_make_list(env, 0);
+        while (k > 0 && p.keep[k - 1] >= d.row_offsets[i]) {
+            --k;
+            ERL_NIF_TERM f = make_bin(env, p.buf + p.offs[k], p.offs[k + 1] - p.offs[k]);
+            row = enif_make_list_cell(env, enif_make_tuple3(env, f, enif_make_uint(env, d.groups[p.keep[k]]),
+                                                            enif_make_uint(env, d.subscribers[p.keep[k]])), row);
+        }
+        out = enif_make_list_cell(env, row, out);
+    }
+    packed_free(&p);
+    tm_batch_free(r->e, b);
+    return out;
+}
+
 /* rules_match(Engine, [Name], [Rule], DollarRule) -> [[RuleIndex]]
  * emqx_topic:match/2 of every name against every rule on the device (ACL rules
  * with DollarRule = false, rewrite / tracer filters with true); per name the
@@ -939,6 +1055,9 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     ATOM_PUBLISH = enif_make_atom(env, "publish");
     ATOM_SUBSCRIBE = enif_make_atom(env, "subscribe");
     ATOM_PUBSUB = enif_make_atom(env, "pubsub");
+    ATOM_RANDOM = enif_make_atom(env, "random");
+    ATOM_ROUND_ROBIN = enif_make_atom(env, "round_robin");
+    ATOM_HASH = enif_make_atom(env, "hash");
     return 0;
 }
 
@@ -962,6 +1081,10 @@ static ErlNifFunc funcs[] = {
     {"topic_match", 2, nif_topic_match, 0},
     {"acl_new", 2, nif_acl_new, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acl_check", 4, nif_acl_check, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"shared_subscribe", 4, nif_shared_subscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"shared_unsubscribe", 4, nif_shared_unsubscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"shared_member_down", 2, nif_shared_member_down, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"shared_dispatch_batch", 4, nif_shared_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
 };
 
 /* the reaper destroys what is queued, then exits */

@@ -603,8 +603,28 @@ struct tm_batch {
     size_t c_moff = 0, c_fbsums = 0, c_ftotal = 0, c_drow = 0, c_fout = 0, c_ftile = 0;
     size_t ch_ftotal = 0, ch_drow = 0, ch_moff = 0, ch_fout = 0;
     hipEvent_t fev0 = nullptr, fev1 = nullptr;
+    // shared-subscription dispatch (tm_batch_dispatch_shared)
+    uint32_t *d_gcount = nullptr, *d_geoff = nullptr, *d_gbsums = nullptr, *d_grow = nullptr, *d_gtotal = nullptr;
+    uint32_t *d_gkeys = nullptr, *d_gfid = nullptr, *d_ggrp = nullptr, *d_gsub = nullptr;
+    unsigned long long *d_gtot64 = nullptr, *h_gtot64 = nullptr;
+    uint32_t *h_gkeys = nullptr, *h_grow = nullptr, *h_gfid = nullptr, *h_ggrp = nullptr, *h_gsub = nullptr;
+    size_t c_gcount = 0, c_geoff = 0, c_gbsums = 0, c_grow = 0, c_gtotal = 0, c_gkeys = 0, c_gfid = 0, c_ggrp = 0;
+    size_t c_gsub = 0, c_gtot64 = 0, ch_gtot64 = 0, ch_gkeys = 0, ch_grow = 0, ch_gfid = 0, ch_ggrp = 0, ch_gsub = 0;
+    hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};   // around count + scan + rows, around the pick
 
     void release() {
+        dev_free(d_gcount); dev_free(d_geoff); dev_free(d_gbsums); dev_free(d_grow); dev_free(d_gtotal);
+        dev_free(d_gkeys); dev_free(d_gfid); dev_free(d_ggrp); dev_free(d_gsub); dev_free(d_gtot64);
+        for (uint32_t** h : {&h_gkeys, &h_grow, &h_gfid, &h_ggrp, &h_gsub}) {
+            if (*h) (void)hipHostFree(*h);
+            *h = nullptr;
+        }
+        if (h_gtot64) (void)hipHostFree(h_gtot64);
+        h_gtot64 = nullptr;
+        for (hipEvent_t& ev : gev) {
+            if (ev) (void)hipEventDestroy(ev);
+            ev = nullptr;
+        }
         dev_free(d_moff); dev_free(d_moff32); dev_free(d_fbig); dev_free(d_dcount); dev_free(d_fmeta);
         if (h_fmeta) (void)hipHostFree(h_fmeta);
         h_fmeta = nullptr; dev_free(d_fbsums); dev_free(d_ftotal); dev_free(d_drow); dev_free(d_fout);
@@ -832,6 +852,15 @@ struct Replica {
     uint32_t* d_sone = nullptr;
     size_t c_soff = 0, c_subs = 0, c_scnt = 0, c_sone = 0;
     uint64_t subs_gen = ~0ull;
+    // shared subscriptions: gcnt / goff by node id, runs, members (engine
+    // shared_gen when uploaded); the run slots' cursors stay here across uploads
+    uint8_t* d_gcnt = nullptr;
+    uint32_t *d_goff = nullptr, *d_gmem = nullptr;
+    uint4* d_gruns = nullptr;
+    uint2* d_gupd = nullptr;
+    SharedSlot* d_gslots = nullptr;
+    size_t c_gcnt = 0, c_goff = 0, c_gmem = 0, c_gruns = 0, c_gupd = 0, c_gslots = 0;
+    uint64_t shared_gen = ~0ull;
     // tm_rules_match
     uint32_t* d_rl = nullptr;
     size_t c_rl = 0;
@@ -1926,6 +1955,40 @@ struct tm_engine {
 
     // tm_batch_dispatch: deliveries of a waited batch, resolved on the device
     int batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out);
+
+    // ---- shared subscriptions: the ?SHARED_SUBS bag of the local node
+    // (src/emqx_shared_sub.erl:287-315, 358-367).  topic -> its (group, topic)
+    // runs in first-added order, each with its members in insertion order and
+    // a run slot it keeps for as long as it has members (the round-robin
+    // cursor of the slot lives on every replica); subscriber -> its (topic,
+    // group) memberships.  A freed slot is handed out again under a new epoch,
+    // which resets its cursor on the device.
+    struct SharedRun {
+        uint32_t group, slot;
+        std::vector<uint32_t> members;
+    };
+    std::unordered_map<std::string, std::vector<SharedRun>> shared_of;
+    std::unordered_map<uint32_t, std::vector<std::pair<std::string, uint32_t>>> shared_topics_of;
+    std::vector<uint32_t> shared_epoch;       // per slot: epoch of its current (or last) owner, from 1
+    std::vector<uint32_t> shared_free;        // slots without an owner
+    bool shared_dirty = true;
+    uint64_t shared_entries = 0, shared_runs = 0, shared_version = 0;
+    uint64_t shared_gen = 0;                  // bumped when the host arrays below are rebuilt
+    uint32_t shared_nn = 0;
+    std::vector<uint8_t> h_gcnt;
+    std::vector<uint32_t> h_goff, h_gmem;
+    std::vector<uint4> h_gruns;
+    std::vector<uint2> h_gupd;                // per slot: {member count, epoch}
+
+    int shared_subscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub);
+    int shared_unsubscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub);
+    int shared_member_down(uint32_t sub, uint64_t* n_removed);
+    int shared_members(const uint8_t* t, size_t len, uint32_t group, uint32_t* buf, uint32_t cap, uint32_t* n);
+    // tables by node id: rebuilt on the host after membership or trie changes,
+    // uploaded to a replica holding an older build, whose cursors are then folded
+    int sync_shared(Replica& R);
+    // tm_batch_dispatch_shared: one picked delivery per (publish, filter, group)
+    int batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_shared_deliveries* out);
 
     // tm_rules_match: rules tokenised with their own dictionary, names against it
     int rules_match(Replica& R, const uint8_t* names, const uint64_t* noffs, uint32_t n, const uint8_t* rules,

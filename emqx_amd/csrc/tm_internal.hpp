@@ -316,6 +316,51 @@ __host__ __device__ inline uint64_t region_cap(uint64_t sfids_cap, bool one_regi
     return (one_region ? sfids_cap : sfids_cap / TICKET_GROUPS) & ~15ull;
 }
 
+// Shared-subscription dispatch over a batch's match CSR
+// (tm_batch_dispatch_shared): emqx_shared_sub:dispatch/3 for every {To, Group}
+// route of every publish.  Device tables, by trie node id (a filter id):
+//   gcnt[f]   min(groups on f, 255) -- the count kernel's 1-B gather; 255 = read goff
+//   goff[f]   runs goff[f] .. goff[f + 1] of the run table (nnodes + 1)
+//   runs[k]   {group id, first member in mem, member count, run slot}
+//   mem       the members of every run, each run in insertion order
+//   slots[s]  the state of run slot s, which a (group, topic) keeps for as
+//             long as it has members; it stays in HBM across table uploads
+enum : uint32_t { SH_RANDOM = 0, SH_ROUND_ROBIN = 1, SH_HASH = 2 };   // TM_SHARED_* (tm_shared.cpp asserts it)
+struct SharedSlot {
+    unsigned long long cur;   // round-robin cursor: the next pick is cur rem cnt
+    unsigned long long base;  // cur as the last fold left it: cur != base <=> picked since
+    uint32_t cnt;             // member count the picks since the last fold ran under
+    uint32_t epoch;           // host epoch of the slot's owner; a new owner resets the cursor
+};
+struct SharedArgs {
+    const uint32_t* row_off;  // match CSR (n + 1) and filter ids (m entries)
+    const uint32_t* ids;
+    uint32_t n;
+    uint32_t m;
+    const uint8_t* gcnt;
+    const uint32_t* goff;
+    const uint4* runs;
+    const uint32_t* mem;
+    uint32_t nnodes;
+    uint32_t nruns;
+    uint32_t nmem;
+    uint32_t nslots;
+    SharedSlot* slots;
+    uint32_t* ecount;         // per match entry: groups on its filter
+    uint32_t* eoff;           // m + 1: exclusive scan of ecount (block-local + bsums)
+    uint32_t* bsums;
+    const uint32_t* total;    // the scan's total (u32)
+    unsigned long long* total64;   // sum of ecount in u64: a total past u32 is seen, not wrapped
+    uint32_t* g_rowoff;       // n + 1: delivery CSR offsets
+    uint32_t strategy;        // TM_SHARED_*
+    const uint32_t* keys;     // n (TM_SHARED_HASH)
+    unsigned long long seed;  // TM_SHARED_RANDOM
+    uint32_t* out_fid;        // delivery i: filter id, group id, subscriber
+    uint32_t* out_grp;
+    uint32_t* out_sub;
+    uint64_t cap;             // capacity of the three
+};
+
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
 struct RulesArgs {
     const uint32_t* nwords;   // name word ids (rule dictionary; unknown = W_UNKNOWN)
@@ -386,6 +431,12 @@ hipError_t launch_acl_check(const AclArgs& a, hipStream_t s);
 hipError_t launch_rules_match(const RulesArgs& a, hipStream_t s);
 hipError_t launch_gather_rows(const uint32_t* src, const int64_t* src_off, const int64_t* idx, uint32_t n,
                               const int64_t* dst_off, uint32_t* dst, hipStream_t s);
+hipError_t launch_shared_count(const SharedArgs& a, hipStream_t s);
+hipError_t launch_shared_rows(const SharedArgs& a, hipStream_t s);
+hipError_t launch_shared_pick(const SharedArgs& a, hipStream_t s);
+// folds every run slot's cursor onto the member counts / owners of a new table
+// build: upd[s] = {member count, epoch} of slot s
+hipError_t launch_shared_fold(SharedSlot* slots, const uint2* upd, uint32_t nslots, hipStream_t s);
 hipError_t launch_route_count(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_rows(const RouteArgs& a, hipStream_t s);
 hipError_t launch_route_fill(const RouteArgs& a, hipStream_t s);

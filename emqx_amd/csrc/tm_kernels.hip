@@ -1434,6 +1434,100 @@ __global__ __launch_bounds__(256) void tm_route_fill(RouteArgs a) {
     }
 }
 
+// ----------------------- shared subscriptions (emqx_shared_sub:dispatch/3)
+//
+// do_route({To, Group}, Delivery) (src/emqx_broker.erl:245-248) for every
+// matched filter To of every publish: one delivery per group run on the
+// filter, the member picked by pick_subscriber/5 (src/emqx_shared_sub.erl:
+// 260-275).  Entry-parallel like the routes: count = groups on the entry's
+// filter (a 1-B gather, most entries stop there), the u32 scan, then one
+// thread per entry picks for each of its runs.  Only an entry with groups
+// looks for its publish (a binary search of the match CSR's row offsets).
+
+__global__ __launch_bounds__(256) void tm_shared_count(SharedArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    uint32_t c = 0;
+    if (i < a.m) {
+        const uint32_t f = a.ids[i];
+        if (f < a.nnodes) {
+            c = a.gcnt[f];
+            if (c == 255) c = a.goff[f + 1] - a.goff[f];
+        }
+        a.ecount[i] = c;
+    }
+    unsigned long long s = c;
+    for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd(a.total64, s);
+}
+__device__ __forceinline__ uint32_t shared_eoff(const SharedArgs& a, uint32_t j) {
+    return j < a.m ? a.eoff[j] + a.bsums[j / SCAN_TILE] : *a.total;
+}
+__global__ __launch_bounds__(256) void tm_shared_rows(SharedArgs a) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t <= a.n) a.g_rowoff[t] = shared_eoff(a, a.row_off[t]);
+}
+__device__ __forceinline__ unsigned long long shared_mix(unsigned long long z) {
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__global__ __launch_bounds__(256) void tm_shared_pick(SharedArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.m) return;
+    const uint32_t f = a.ids[i];
+    if (f >= a.nnodes || a.gcnt[f] == 0) return;
+    // the publish of entry i: the last row p with row_off[p] <= i (rows before it may be empty)
+    uint32_t lo = 0, hi = a.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.row_off[mid] <= i) lo = mid; else hi = mid;
+    }
+    const uint32_t p = lo;
+    uint64_t o = shared_eoff(a, i);
+    const uint32_t ke = min(a.goff[f + 1], a.nruns);
+    for (uint32_t k = a.goff[f]; k < ke && o < a.cap; ++k, ++o) {
+        const uint4 run = a.runs[k];   // group, first member, count, slot
+        const uint32_t cnt = run.z;
+        uint32_t nth = 0;
+        if (cnt > 1) {   // [Sub] -> Sub: no state, no key (:260)
+            if (a.strategy == SH_HASH) {
+                nth = a.keys[p] % cnt;
+            } else if (a.strategy == SH_ROUND_ROBIN) {
+                if (run.w < a.nslots) nth = (uint32_t)(atomicAdd(&a.slots[run.w].cur, 1ull) % cnt);
+            } else {
+                constexpr unsigned long long G = 0x9E3779B97F4A7C15ull;
+                unsigned long long z = shared_mix(a.seed + G * ((unsigned long long)p + 1));
+                z = shared_mix((z ^ ((unsigned long long)f << 32 | run.x)) + G);
+                nth = (uint32_t)(z >> 32) % cnt;
+            }
+        }
+        const uint64_t mi = (uint64_t)run.y + nth;
+        a.out_fid[o] = f;
+        a.out_grp[o] = run.x;
+        a.out_sub[o] = (cnt && mi < a.nmem) ? a.mem[mi] : NONE;
+    }
+}
+// A new build of the tables reached the replica: upd[s] = {member count, owner
+// epoch} of run slot s.  A slot whose owner changed starts over (the first pick
+// ever is member 1).  A slot that was picked from since its last fold stores
+// the reference's remainder N = last pick index as cur = N + 1
+// (src/emqx_shared_sub.erl:270-274), so the next pick under the new count is
+// (N + 1) rem NewCount; one that was not picked from keeps its N.
+__global__ __launch_bounds__(256) void tm_shared_fold(SharedSlot* slots, const uint2* upd, uint32_t nslots) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= nslots) return;
+    SharedSlot v = slots[s];
+    const uint2 u = upd[s];
+    if (v.epoch != u.y) {
+        v.cur = v.base = 0;
+        v.epoch = u.y;
+    } else if (v.cur != v.base && v.cnt) {
+        v.cur = v.base = (v.cur - 1) % v.cnt + 1;
+    }
+    v.cnt = u.x;
+    slots[s] = v;
+}
+
 // ------------------------------------------ fan-out (emqx_broker:dispatch/2)
 //
 // dispatch(To, Delivery) folds over subscribers(To) for every local route of the
@@ -3426,6 +3520,26 @@ hipError_t launch_finalize(const ScanArgs& a, hipStream_t s, bool checked) {
     const uint32_t grid = min(ntiles, 256u * 32u);   // 8 waves per SIMD
     if (checked) hipLaunchKernelGGL(tm_finalize<true>, dim3(grid), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(tm_finalize<false>, dim3(grid), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shared_count(const SharedArgs& a, hipStream_t s) {
+    if (a.m) hipLaunchKernelGGL(tm_shared_count, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shared_rows(const SharedArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(tm_shared_rows, dim3((a.n + 1 + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shared_pick(const SharedArgs& a, hipStream_t s) {
+    if (a.m) hipLaunchKernelGGL(tm_shared_pick, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_shared_fold(SharedSlot* slots, const uint2* upd, uint32_t nslots, hipStream_t s) {
+    if (nslots) hipLaunchKernelGGL(tm_shared_fold, dim3((nslots + 255) / 256), dim3(256), 0, s, slots, upd, nslots);
     return hipGetLastError();
 }
 

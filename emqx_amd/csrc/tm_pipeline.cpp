@@ -59,6 +59,8 @@ void tm_engine::destroy() {
         dev_free(R->d_dblob);
         dev_free(R->d_dbg); dev_free(R->d_roff); dev_free(R->d_rdest); dev_free(R->d_rl);
         dev_free(R->d_soff); dev_free(R->d_subs); dev_free(R->d_scnt); dev_free(R->d_sone);
+        dev_free(R->d_gcnt); dev_free(R->d_goff); dev_free(R->d_gmem); dev_free(R->d_gruns); dev_free(R->d_gupd);
+        dev_free(R->d_gslots);
         if (R->h_dbg) (void)hipHostFree(R->h_dbg);
         if (R->h_app) (void)hipHostFree(R->h_app);
         if (R->ev_delta) (void)hipEventDestroy(R->ev_delta);

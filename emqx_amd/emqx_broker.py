@@ -7,7 +7,9 @@ the first subscriber of a topic adds its node() route and the last one removes
 it, as the broker pool does through emqx_router (:438-469).  publish_batch runs
 the whole publish path of a batch on the device: match (emqx_router:
 match_routes/1) then fan-out (dispatch/2 for every local route,
-tm_batch_dispatch).  Shared subscriptions (emqx_shared_sub) are not mirrored.
+tm_batch_dispatch).  The other local clause of do_route/2, {To, Group}
+(:245-248), is emqx_shared_sub.dispatch_batch (tm_batch_dispatch_shared);
+shared and non-shared subscribers share the pid -> u32 id map below.
 
 Subscriber pids are arbitrary hashable terms here, mapped to u32 ids.
 """
@@ -38,6 +40,8 @@ def clear_tables():
     _ids, _terms = {}, []
     _topics_of, _nsubs = {}, {}
     _order.clear()
+    from . import emqx_shared_sub
+    emqx_shared_sub.clear()        # its members lived in the engine that was just replaced
 
 
 _topics_of = {}   # subscriber id -> [topic]: which node() routes subscriptions hold

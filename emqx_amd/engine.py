@@ -164,6 +164,46 @@ class Batch:
         d = self._dispatch(N.TM_DISPATCH_ROWS)
         return int(d.n_deliveries), float(d.fill_ms)
 
+    def dispatch_shared(self, strategy, keys=None, seed: int = 0, counts_only: bool = False):
+        """Shared-subscription dispatch (tm_batch_dispatch_shared):
+        emqx_shared_sub:dispatch/3 for every {To, Group} route of every publish
+        -> (row_offsets u32[n+1], filter_ids, groups, subscribers), the three
+        None with counts_only.  strategy: N.TM_SHARED_* or "random" /
+        "round_robin" / "hash"; keys = one u32 per publish (hash:
+        erlang:phash2(ClientId)); seed for random."""
+        d = self._dispatch_shared(strategy, keys, seed, N.TM_SHARED_COUNT_ONLY if counts_only else 0)
+        n, t = d.n_topics, int(d.n_deliveries)
+        offs = np.ctypeslib.as_array(d.row_offsets, shape=(n + 1,)).copy()
+        if counts_only:
+            return offs, None, None, None
+        cp = lambda p: np.ctypeslib.as_array(p, shape=(t,)).copy() if t else np.zeros(0, np.uint32)  # noqa: E731
+        return offs, cp(d.filter_ids), cp(d.groups), cp(d.subscribers)
+
+    def dispatch_shared_device(self, strategy, keys=None, seed: int = 0):
+        """TM_SHARED_DEVICE: -> (n_deliveries, kernel ms, device ptrs
+        row_offsets / filter_ids / groups / subscribers)."""
+        d = self._dispatch_shared(strategy, keys, seed, N.TM_SHARED_DEVICE)
+        ptr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        return (int(d.n_deliveries), float(d.kernel_ms), ptr(d.row_offsets), ptr(d.filter_ids), ptr(d.groups),
+                ptr(d.subscribers))
+
+    def _dispatch_shared(self, strategy, keys, seed: int, flags: int) -> "N.SharedDeliveries":
+        o = N.SharedOpts()
+        o.strategy = N.SHARED_STRATEGIES.get(strategy, strategy) if isinstance(strategy, str) else int(strategy)
+        o.flags = flags
+        o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        if keys is not None:
+            k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32))
+            if len(k) != self.n:
+                raise ValueError(f"{len(k)} keys for {self.n} publishes")
+            if not len(k):
+                k = np.zeros(1, np.uint32)
+            o.keys = k.ctypes.data
+        d = N.SharedDeliveries()
+        N.check(self.eng.L.tm_batch_dispatch_shared(self.eng.h, self.h, C.byref(o), C.byref(d)),
+                "tm_batch_dispatch_shared")
+        return d
+
     def _dispatch(self, flags: int) -> "N.Deliveries":
         d = N.Deliveries()
         N.check(self.eng.L.tm_batch_dispatch(self.eng.h, self.h, flags, C.byref(d)), "tm_batch_dispatch")
@@ -677,6 +717,33 @@ class Engine:
         n = C.c_uint64()
         N.check(self.L.tm_subscriber_down(self.h, sub, node_dest, C.byref(n)), "tm_subscriber_down")
         return n.value
+
+    # ---- shared subscriptions (emqx_shared_sub subscribe/unsubscribe/cleanup_down) --
+    def shared_subscribe(self, topic: bytes, group_dest: int, sub: int):
+        N.check(self.L.tm_shared_subscribe(self.h, topic, len(topic), group_dest, sub), "tm_shared_subscribe")
+
+    def shared_unsubscribe(self, topic: bytes, group_dest: int, sub: int) -> bool:
+        rc = self.L.tm_shared_unsubscribe(self.h, topic, len(topic), group_dest, sub)
+        if rc == N.TM_ENOENT:
+            return False
+        N.check(rc, "tm_shared_unsubscribe")
+        return True
+
+    def shared_member_down(self, sub: int) -> int:
+        n = C.c_uint64()
+        N.check(self.L.tm_shared_member_down(self.h, sub, C.byref(n)), "tm_shared_member_down")
+        return n.value
+
+    def shared_members(self, topic: bytes, group_dest: int) -> list:
+        """subscribers/2: the members of (group, topic) in insertion order."""
+        n = C.c_uint32()
+        buf = np.zeros(64, np.uint32)
+        while True:
+            N.check(self.L.tm_shared_members(self.h, topic, len(topic), group_dest, buf.ctypes.data, len(buf),
+                                             C.byref(n)), "tm_shared_members")
+            if n.value <= len(buf):
+                return buf[:n.value].tolist()
+            buf = np.zeros(n.value, np.uint32)
 
     def match_routes_batch(self, topics):
         """-> (row_offsets, filter_ids, dests): aggre(match_routes(T)) per topic."""

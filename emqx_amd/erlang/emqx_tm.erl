@@ -28,6 +28,11 @@
         , acl_load/2
         , acl_check/4
         , check_acl/4
+        , shared_subscribe/4
+        , shared_unsubscribe/4
+        , shared_member_down/2
+        , shared_dispatch_batch/4
+        , shared_dispatch/3
         ]).
 
 -on_load(init/0).
@@ -118,6 +123,41 @@ subscriber_down(_Engine, _SubId, _NodeDestId) -> erlang:nif_error(nif_not_loaded
 %% SubIds to deliver to ([] = {error, no_subscribers}).
 -spec(dispatch_batch(reference(), [binary()]) -> [[non_neg_integer()]]).
 dispatch_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
+
+%% Shared-subscription members (emqx_shared_sub's handle_call({subscribe |
+%% unsubscribe, Group, Topic, SubPid}) and cleanup_down/1,
+%% src/emqx_shared_sub.erl:297-315, 358-367): GroupDestId = the caller's id of
+%% {Group, _} in route_add/3; the first member of (Group, Topic) adds that
+%% route, the last one deletes it.
+-spec(shared_subscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
+shared_subscribe(_Engine, _Topic, _GroupDestId, _SubId) -> erlang:nif_error(nif_not_loaded).
+
+-spec(shared_unsubscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
+shared_unsubscribe(_Engine, _Topic, _GroupDestId, _SubId) -> erlang:nif_error(nif_not_loaded).
+
+-spec(shared_member_down(reference(), non_neg_integer()) -> {ok, non_neg_integer()} | {error, term()}).
+shared_member_down(_Engine, _SubId) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_shared_sub:dispatch/3 for every {To, Group} route of every publish: per
+%% publish [{To, GroupDestId, SubId}].  hash: Arg = [erlang:phash2(ClientId)],
+%% one per publish; random: Arg = the seed; round_robin: Arg is ignored.
+-spec(shared_dispatch_batch(reference(), [binary()], random | round_robin | hash, [non_neg_integer()] | non_neg_integer())
+      -> [[{binary(), non_neg_integer(), non_neg_integer()}]] | {error, term()}).
+shared_dispatch_batch(_Engine, _Topics, _Strategy, _Arg) -> erlang:nif_error(nif_not_loaded).
+
+%% The same for a batch of {From, Topic} publishes (From = #message.from, the
+%% publisher's client id, src/emqx_shared_sub.erl:113-115) under Strategy: the
+%% hash keys are erlang:phash2(From), the reference's own (:267-268); random is
+%% seeded from the caller's rand state.
+-spec(shared_dispatch(reference(), [{term(), binary()}], random | round_robin | hash)
+      -> [[{binary(), non_neg_integer(), non_neg_integer()}]] | {error, term()}).
+shared_dispatch(Engine, Publishes, hash) ->
+    {Froms, Topics} = lists:unzip(Publishes),
+    shared_dispatch_batch(Engine, Topics, hash, [erlang:phash2(From) || From <- Froms]);
+shared_dispatch(Engine, Publishes, random) ->
+    shared_dispatch_batch(Engine, [T || {_, T} <- Publishes], random, rand:uniform(16#100000000) - 1);
+shared_dispatch(Engine, Publishes, round_robin) ->
+    shared_dispatch_batch(Engine, [T || {_, T} <- Publishes], round_robin, 0).
 
 %% aggre(match_routes(Topic)) for a batch of publishes, resolved on the device.
 -spec(match_routes_batch(reference(), [binary()]) -> [[{binary(), non_neg_integer()}]]).

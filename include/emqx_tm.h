@@ -430,6 +430,93 @@ typedef struct {
 #define TM_DISPATCH_ROWS          8u
 TM_API int  tm_batch_dispatch(tm_engine* e, tm_batch* b, uint32_t flags, tm_deliveries* out);
 
+/* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
+/* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
+ * 287-305) of the local node.  group_dest = the aggregated dest id the caller
+ * uses for {Group, _} in tm_route_add (emqx_broker:aggre/1), so the ids in
+ * tm_routes.dests and the group ids here are the same; subscriber ids are the
+ * caller's.  All four calls work on a host-only engine.
+ * tm_shared_subscribe: handle_call({subscribe, Group, Topic, SubPid})
+ * (:297-305): the first member of (group, topic) adds the route (topic,
+ * group_dest) (:299-302); a repeated (group, topic, subscriber) is a no-op (a
+ * bag stores an object once, :304); members keep insertion order. */
+TM_API int  tm_shared_subscribe(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest,
+                                uint32_t subscriber);
+/* handle_call({unsubscribe, Group, Topic, SubPid}) (:307-315): TM_ENOENT if
+ * the subscriber is not a member (delete_object of no record); the last
+ * member deletes the route (:310-313). */
+TM_API int  tm_shared_unsubscribe(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest,
+                                  uint32_t subscriber);
+/* cleanup_down/1 (:358-367): drops every shared membership of the subscriber;
+ * *n_removed (may be NULL) = how many.  The non-shared bag is not touched
+ * (that is tm_subscriber_down). */
+TM_API int  tm_shared_member_down(tm_engine* e, uint32_t subscriber, uint64_t* n_removed);
+/* subscribers/2 (:277-278): the members of (group, topic) in insertion order;
+ * writes up to cap ids, *n = full count (0 for an unknown group or topic). */
+TM_API int  tm_shared_members(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest,
+                              uint32_t* buf, uint32_t cap, uint32_t* n);
+
+/* dispatch(Group, To, Delivery) (:110-125) for every {To, Group} route of every
+ * publish of a waited batch (do_route/2, src/emqx_broker.erl:245-248): one
+ * delivery (filter id, group id, subscriber) per (publish, matched filter,
+ * group on that filter), the subscriber picked by pick_subscriber/5
+ * (:260-275): lists:nth(Nth, Members) over the group's Count members, a
+ * one-member group always that member without touching any state (:260).
+ * Row i = deliveries [row_offsets[i], row_offsets[i+1]): filters in match
+ * (Erlang binary) order, a filter's groups in first-added order -- the order of
+ * tm_routes.
+ *   TM_SHARED_HASH (:267-268): Nth = 1 + keys[i] rem Count; the caller passes
+ *     erlang:phash2(ClientId) of publish i, which makes the pick the
+ *     reference's, bit for bit.
+ *   TM_SHARED_ROUND_ROBIN (:269-275): one 64-bit cursor per (group, topic), per
+ *     replica, in HBM; a pick takes the next cursor value c and Nth = 1 + c
+ *     rem Count; the first pick ever is member 1.  When Count changed since
+ *     the last pick the next pick is (previous pick index + 1) rem NewCount,
+ *     the reference's (N + 1) rem Count on the stored remainder.  Which
+ *     publish of a batch gets which cursor value is unordered; the multiset of
+ *     a batch's picks is exactly the next K cursor values.  (The reference
+ *     keeps the counter in each publishing process's dictionary; a batch has
+ *     no publisher identity.)
+ *   TM_SHARED_RANDOM (:265-266): rand:uniform/1 has no reproducible answer;
+ *     here Nth = 1 + (r >> 32) rem Count with, in wrapping u64 arithmetic,
+ *       G = 0x9E3779B97F4A7C15
+ *       mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *               z *= 0x94D049BB133111EB; z ^= z >> 31
+ *       r = mix((mix(seed + G * (i + 1)) ^ (filter id << 32 | group id)) + G)
+ *     for publish index i: reproducible for a seed, uniform over the members.
+ * TM_SHARED_COUNT_ONLY: row_offsets and n_deliveries only, no pick (a
+ * round-robin cursor does not move), the three arrays NULL.
+ * TM_SHARED_DEVICE: no copy back; the pointers are device memory of the batch.
+ * Otherwise batch-owned pinned memory.  Both valid until the batch's next
+ * tm_batch_dispatch_shared, re-prepare or free.  kernel_ms = device time of
+ * the count, scan and pick kernels.
+ * TM_EINVAL + tm_last_error(): batch not waited, unknown strategy or flag,
+ * TM_SHARED_HASH without keys, a TM_BATCH_DEDUP batch (the pick is per
+ * publish).  TM_ENODEV on a host-only engine.  TM_EOVERFLOW for more than
+ * 2^32 - 16 deliveries. */
+#define TM_SHARED_RANDOM      0u
+#define TM_SHARED_ROUND_ROBIN 1u
+#define TM_SHARED_HASH        2u
+#define TM_SHARED_COUNT_ONLY  1u
+#define TM_SHARED_DEVICE      2u
+typedef struct {
+    uint32_t        strategy;   /* TM_SHARED_RANDOM | _ROUND_ROBIN | _HASH */
+    uint32_t        flags;      /* TM_SHARED_COUNT_ONLY | TM_SHARED_DEVICE */
+    const uint32_t* keys;       /* TM_SHARED_HASH: n_topics host keys, one per publish */
+    uint64_t        seed;       /* TM_SHARED_RANDOM */
+} tm_shared_opts;
+typedef struct {
+    uint32_t        n_topics;
+    uint64_t        n_deliveries;
+    const uint32_t* row_offsets;  /* n_topics + 1 */
+    const uint32_t* filter_ids;   /* n_deliveries, or NULL */
+    const uint32_t* groups;       /* n_deliveries, or NULL */
+    const uint32_t* subscribers;  /* n_deliveries, or NULL */
+    float           kernel_ms;
+} tm_shared_deliveries;
+TM_API int  tm_batch_dispatch_shared(tm_engine* e, tm_batch* b, const tm_shared_opts* opts,
+                                     tm_shared_deliveries* out);
+
 /* ---- bulk load + filter-sharded mode ------------------ */
 /* emqx_trie:insert/1 over n filters (filters = concatenated bytes, offsets[n+1]).
  * nshards <= 1: every filter.  Otherwise only the filters whose
