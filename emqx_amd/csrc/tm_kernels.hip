@@ -549,7 +549,6 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     (void)wbase;
 
     uint32_t qn = 0;
-    bool ovf = false;
     const bool active = !(fl & TF_SLOW);
     unsigned long long* const wrows = a.rows + (uint64_t)blockIdx.x * a.tile_topics * a.row_cap;
     // the wave's emission log: its rows region (entries) + a byte per entry
@@ -603,28 +602,55 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     // that spilled past its home bucket is pushed again as a continuation
     // (displacement + 1) rather than holding the whole wave for a dependent read.
     const uint32_t qd = lane >> 2, qs = lane & 3;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<Slot*>(a.slots), 0, BIG ? 0u : a.nslots * 16u, 0x00020000);
+    // The loop's wave-uniform operands get scalar registers of their own (the
+    // empty asm defines them anew): as parts of the kernel-argument tuples
+    // they were spilled to VGPR lanes with the tuples' cold parts and read
+    // back by v_readlane in every iteration.
+    uint32_t nbk = a.nbuckets, maxp = a.max_probe, rcap = a.row_cap, nrec = BIG ? 0u : a.nslots * 16u;
+    Slot* sbase = const_cast<Slot*>(a.slots);
+    asm volatile("" : "+s"(nbk), "+s"(maxp), "+s"(rcap), "+s"(nrec), "+s"(sbase));
+    // (a pointer that passes through the asm is generic: the loop reads the
+    // table and HBM words through global pointers made from the integers)
+    uint64_t wbits = IN_LDS ? 0ull : (uint64_t)a.words;
+    if constexpr (!IN_LDS) asm volatile("" : "+s"(wbits));
+    typedef const __attribute__((address_space(1))) uint32_t* gwords_t;
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4_t* gslots_t;
+    const auto word_at = [&](uint64_t i) -> uint32_t { return IN_LDS ? L.words[i] : ((gwords_t)wbits)[i]; };
     pc.lap(PH_PROLOGUE);
     while (qn > 0) {
         const uint32_t k = min(qn, 64u);
         const bool has = lane < k;
         qn -= k;
-        tP += lane == 0 ? k + (1u << 20) : 0u;   // bucket reads (hits, misses, continuations) | iterations << 20
-        const uint32_t idx = qn + lane;
-        uint4 e = uint4{0u, 0u, 0u, 0u};
-        if (has) e = L.q[idx];
+        // bucket reads (hits, misses, continuations) | iterations << 20: the same
+        // in every lane; kept in a VGPR (as a scalar it is spilled to a lane
+        // and reloaded every iteration)
+        tP += k + (1u << 20);
+        asm volatile("" : "+v"(tP));
+        // A lane without a probe of its own (k < 64, the stack's last pop)
+        // takes lane 0's entry along: every index derived from it (topic
+        // lane, word offsets, row count) is then a live one, so the reads
+        // below need no exec region of their own and `has` only gates what a
+        // lane pushes, emits and counts.  Its bucket store repeats lane 0's
+        // value at lane 0's address.
+        const uint32_t idx = qn + (has ? lane : 0u);
+        const uint4 e = L.q[idx];
         const uint32_t meta = e.x & 0x7FFFFFFFu;
         const uint64_t key = ((uint64_t)e.y << 32) | (e.x & 0x80000000u);
         const uint32_t parent = e.z, pw = e.w;
         const uint32_t tl = meta & 63;
         const uint32_t lc = (meta >> M_LVL_SHIFT) & M_LVL_MASK;
         const uint32_t disp = (meta >> M_DISP_SHIFT) & M_DISP_MASK;
-        if (has) {
-            uint32_t hb = home_bucket(parent, pw, a.nbuckets) + disp;
-            if (hb >= a.nbuckets) hb -= a.nbuckets;
+        {
+            uint32_t hb = home_bucket(parent, pw, nbk) + disp;
+            if (hb >= nbk) hb -= nbk;
             L.q[idx].x = hb;
         }
+        // the slot table's descriptor, put together here from its scalars (the
+        // asm keeps it from being hoisted: as a loop-invariant 4-dword tuple it
+        // was spilled and read back lane by lane, with a hazard pad, every time)
+        asm volatile("" : "+s"(sbase), "+s"(nrec));
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(sbase, 0, nrec, 0x00020000);
         uint32_t rp[4], rw[4];
         uint4 sl[4];
 #pragma unroll
@@ -638,98 +664,103 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
             if (!BIG) {
                 sl[r] = ld_b128(rsrc, v ? (uint32_t)si * 16u : 0xFFFFFFF0u);   // out of range: reads 0
             } else {
-                sl[r] = v ? reinterpret_cast<const uint4*>(a.slots)[si] : uint4{0u, 0u, 0u, 0u};
+                const u32x4_t g = v ? ((gslots_t)(uint64_t)sbase)[si] : u32x4_t{0u, 0u, 0u, 0u};
+                sl[r] = uint4{g[0], g[1], g[2], g[3]};
             }
         }
         // the topic's words are read while the buckets are in flight (the
         // barrier keeps the compiler from hoisting these LDS reads, and their
         // waits, above the bucket loads)
         __builtin_amdgcn_sched_barrier(0);
-        uint32_t d = 0, w_here = 0, w_prev = 0;
-        if (has) {
-            const uint32_t base = L.toff[tl];
-            d = L.depth[tl];
-            w_here = lc < d ? wsrc[CK_(base + lc, wlim, 11)] : 0u;
-            w_prev = wsrc[CK_(base + lc - 1, wlim, 10)];
-        }
+        // (every pushed entry has 1 <= lc <= d: a push raises lc only below
+        // the end of the words)  At the end of the words w_here repeats
+        // w_prev; nothing that is used there reads it.
+        const uint32_t base = L.toff[tl];
+        const uint32_t d = L.depth[tl];
+        const bool at_end = lc == d;
+        const uint32_t w_here = word_at(CK_(base + lc - (at_end ? 1u : 0u), wlim, 11));
+        const uint32_t w_prev = word_at(CK_(base + lc - 1, wlim, 10));
         // The quad reports to the owner through the owner's LDS entry, not
         // through ballots: the matching lane writes the child summary and a
         // FOUND mark, the lane of the bucket's last slot a TAIL mark when that
         // slot is free (the probe run ends in this bucket).  Parent ids and
-        // word ids never equal the marks.
+        // word ids never equal the marks.  (rp is SLOT_EMPTY where the quad
+        // has no probe, which no masked parent field equals.)
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
-            const bool m = rp[r] != SLOT_EMPTY && (sl[r].x & ID_MASK) == rp[r] && (sl[r].y & WID_MASK) == rw[r];
+            const bool m = (sl[r].x & ID_MASK) == rp[r] && (sl[r].y & WID_MASK) == rw[r];
             if (m) {
                 L.q[qn + 16 * r + qd].x = sl[r].z;
                 L.q[qn + 16 * r + qd].y = sl[r].w;
                 L.q[qn + 16 * r + qd].z = Q_FOUND | slot_lsig(sl[r].x, sl[r].y);
             }
-            if (qs == 3 && sl[r].x == SLOT_EMPTY) L.q[qn + 16 * r + qd].w = Q_TAIL;   // out-of-range loads read 0
         }
-        uint4 res = uint4{0u, 0u, 0u, 0u};
-        if (has) res = L.q[idx];
+        // The last slot's lane writes the word field in every round, under one
+        // exec region for the four: TAIL, or the word it read from there.  A
+        // quad without a probe (out-of-range load: reads 0) puts entry qn's
+        // word into a place above the popped ones: when k < 64, qn is 0 after
+        // the pop and qn + p < 64 is unused stack; when k = 64 every quad has
+        // a probe.
+        uint32_t qs_now = qs;   // (compared here: the hoisted lane mask would be one more spilled pair)
+        asm volatile("" : "+v"(qs_now));
+        if (qs_now == 3) {
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) L.q[qn + 16 * r + qd].w = sl[r].x == SLOT_EMPTY ? Q_TAIL : rw[r];
+        }
+        const uint4 res = L.q[idx];
         // a row already longer than K goes to the generic path whole: its
         // entries are not expanded further (C5 K = 1000: ~10k rows of ~1,000
         // matches each stopped at K + 1 instead of walked to the end)
-        const bool gone = has && L.cnt[tl] > a.row_cap;
-        const bool found = has && !gone && res.z >= Q_FOUND;
-        const bool cont = has && !gone && !found && res.w != Q_TAIL && disp < a.max_probe;
-        Node s;
-        s.child = 0; s.term = NONE; s.hterm = NONE; s.flags = 0;
-        if (found) {
-            const uint32_t hz = res.x, hw = res.y;
-            s.child = hz & ID_MASK;
-            s.term = (hz & B_TOPIC) ? s.child : NONE;
-            s.hterm = (hw & B_HTERM) ? (hw & ID_MASK) : NONE;
-            s.flags = ((hz & B_PLUS) ? NF_PLUS : 0u) | ((hw & B_HASH) ? NF_HASH : 0u);
-        }
+        const bool live = has & (L.cnt[tl] <= rcap);
+        const bool found = live & (res.z >= Q_FOUND);
+        const bool cont = live & !found & (res.w != Q_TAIL) & (disp < maxp);
+        // the found child's summary (bits of the slot's child and hash fields)
+        const uint32_t hz = res.x, hw = res.y;
+        const uint32_t child = hz & ID_MASK, hterm = hw & ID_MASK;
+        const bool n_topic = (hz & B_TOPIC) != 0, n_plus = (hz & B_PLUS) != 0;
+        const bool n_hterm = (hw & B_HTERM) != 0, n_hash = (hw & B_HASH) != 0;
         // Expansion of the found node, match_node/3 (src/emqx_trie.erl:168-177),
         // with fixed roles instead of expand()'s packed lists: emissions A, B;
         // push L (the literal word, or the continuation) and push P ('+').
         // lc <= FAST_MAX_DEPTH here, so every level has a digit position.
-        const bool at_end = lc == d;
+        // Straight-line: both arms are computed and selected (non-short-circuit
+        // & and |), since an exec region costs more than the few VALU it skips.
         const uint32_t cls = w_here >> WID_BITS, id = w_here & WID_MASK;
         const int sh = key_shift(lc);
-        bool eA = false, eB = false, pL = false, pP = false;
-        uint32_t fA = 0;
-        uint64_t kA = key;
-        if (found) {
-            if (!(meta & M_DSTART)) tV += 1;
-            if (s.flags & NF_HASH) tH += 1;
-            if (at_end) {   // end of the words: own topic, then the '#' child's
-                eA = !(meta & M_SKIPE) && s.term != NONE;
-                fA = s.term;
-                // '' word at level lc-1 followed by the end: "P/" sorts before "P/#"
-                if ((w_prev >> WID_BITS) == C_EMPTY) {
-                    const int sp = key_shift(lc - 1);
-                    if (((kA >> sp) & 7) == 4) kA = (kA & ~(7ull << sp)) | (1ull << sp);
-                }
-                eB = s.hterm != NONE;
-            } else {        // '#' child's topic, then the literal and '+' edges
-                eA = s.hterm != NONE;
-                fA = s.hterm;
-                kA = key | ((uint64_t)dig_H(cls) << sh);
-                // a literal word whose signature bit is clear has no edge here
-                // (and, for a node without a '#' child, its 30-bit signature)
-                pL = id == W_HASH ? (s.flags & NF_HASH) != 0
-                                  : (id != W_UNKNOWN && id != W_PLUS && ((res.z >> lsig_pos(id)) & 1u) &&
-                                     ((res.y & B_HASH) || ((res.y >> lext_pos(id)) & 1u)));
-                pP = (s.flags & NF_PLUS) != 0;
-            }
-        }
-        const bool sL = cont || pL;
+        tV += (found & !(meta & M_DSTART)) ? 1u : 0u;
+        tH += (found & n_hash) ? 1u : 0u;
+        // end of the words: own topic, then the '#' child's; otherwise the '#'
+        // child's topic, then the literal and '+' edges
+        const bool eA0 = found & (at_end ? (!(meta & M_SKIPE) & n_topic) : n_hterm);
+        const bool eB0 = found & at_end & n_hterm;
+        const uint32_t fA = at_end ? child : hterm;
+        // '' word at level lc-1 followed by the end: "P/" sorts before "P/#"
+        // (digit 4 -> 1 at that level)
+        const int sp = sh + 3;   // key_shift(lc - 1)
+        const bool redigit = ((w_prev >> WID_BITS) == C_EMPTY) & (((key >> sp) & 7) == 4);
+        // one shift for both arms: level lc's digit bits are still zero in
+        // key, so or-ing the '#' digit in is an xor as well
+        const uint64_t kA = key ^ ((uint64_t)(at_end ? (redigit ? 5u : 0u) : dig_H(cls)) << (at_end ? sp : sh));
+        // a literal word whose signature bit is clear has no edge here
+        // (and, for a node without a '#' child, its 30-bit signature)
+        const bool lit = (id != W_UNKNOWN) & (id != W_PLUS) & (((res.z >> lsig_pos(id)) & 1u) != 0) &
+                         (n_hash | (((hw >> lext_pos(id)) & 1u) != 0));
+        const bool pL = found & !at_end & (id == W_HASH ? n_hash : lit);
+        const bool pP = found & !at_end & n_plus;
+        bool eA = eA0, eB = eB0;
+        const bool sL = cont | pL;
         const uint64_t bL = __ballot(sL), bP = __ballot(pP);
         const uint32_t ptot = __popcll(bL) + __popcll(bP);
-        if (qn + ptot > (uint32_t)LT::QCAP) { ovf = true; break; }
+        if (qn + ptot > (uint32_t)LT::QCAP) break;   // stack overflow: leaves qn > 0 (ptot <= 128 < QCAP)
         const uint32_t pre = qn + prefix_count(bL) + prefix_count(bP);
         const uint32_t nmeta = tl | ((lc + 1) << M_LVL_SHIFT);
         if (sL) {
-            const uint32_t lfl = (id == W_HASH && lc + 1 == d) ? M_SKIPE : 0u;
-            L.q[pre] = cont ? q_pack(key, meta + (1u << M_DISP_SHIFT), parent, pw)
-                            : q_pack(key | ((uint64_t)dig_L(cls) << sh), nmeta | lfl, s.child, id);
+            const uint32_t lfl = ((id == W_HASH) & (lc + 1 == d)) ? M_SKIPE : 0u;
+            const uint64_t kL = cont ? key : key | ((uint64_t)dig_L(cls) << sh);
+            L.q[pre] = q_pack(kL, cont ? meta + (1u << M_DISP_SHIFT) : nmeta | lfl, cont ? parent : child,
+                              cont ? pw : id);
         }
-        if (pP) L.q[pre + (sL ? 1u : 0u)] = q_pack(key | ((uint64_t)dig_P(cls) << sh), nmeta | M_PLUS, s.child, W_PLUS);
+        if (pP) L.q[pre + (sL ? 1u : 0u)] = q_pack(key | ((uint64_t)dig_P(cls) << sh), nmeta | M_PLUS, child, W_PLUS);
         qn += ptot;
         {
             // row sizes; a row's entries past K are not logged (the row goes to
@@ -737,8 +768,8 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
             uint32_t slot = 0;
             if (eA | eB) slot = atomicAdd(&L.cnt[tl], (eA ? 1u : 0u) + (eB ? 1u : 0u));
             const uint32_t slotB = slot + (eA ? 1u : 0u);
-            eA = eA && slot < a.row_cap;
-            eB = eB && slotB < a.row_cap;
+            eA = eA && slot < rcap;
+            eB = eB && slotB < rcap;
             const uint64_t mA = __ballot(eA), mB = __ballot(eB);
             const uint32_t nA = (uint32_t)__popcll(mA), nE = nA + (uint32_t)__popcll(mB);
             if (eA) {
@@ -748,7 +779,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
             }
             if (eB) {
                 const uint32_t i = lcount + nA + prefix_count(mB);
-                wrows[CK_(i, lcap, 14)] = ((key | (2ull << sh)) & KEY_MASK) | s.hterm;
+                wrows[CK_(i, lcap, 14)] = ((key | (2ull << sh)) & KEY_MASK) | hterm;
                 wlane[i] = (uint8_t)tl;
             }
             lcount += nE;
@@ -757,13 +788,13 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     __syncthreads();
     pc.lap(PH_LOOP);
 
-    if (ovf) {
+    if (qn > 0) {
         // probe stack overflow: every regular topic of the tile goes to the slow path
         send_to_slow<CK>(a, valid && active, t);
         return;
     }
     sV += tV; sH += tH; sW += tW;
-    sP += (tP & 0xFFFFFu) | ((unsigned long long)(tP >> 20) << 40);   // probes | iterations << 40
+    if (lane == 0) sP += (tP & 0xFFFFFu) | ((unsigned long long)(tP >> 20) << 40);   // probes | iterations << 40
     const uint32_t c_me = L.cnt[lane];
     const bool row_ovf = valid && active && c_me > a.row_cap;   // row longer than K
     send_to_slow<CK>(a, row_ovf, t);
