@@ -13,12 +13,10 @@ struct tm_acl {
     // per replica: the block's copy in HBM and the buffers of one check call
     // (calls on one engine are serialised by its mutex)
     struct Dev {
-        uint32_t* d_blk = nullptr;
-        uint8_t* d_buf = nullptr;
-        size_t c_buf = 0;
-        uint8_t* h_buf = nullptr;   // pinned: the call's inputs packed for one copy, then its outputs
-        size_t ch_buf = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        DevBuf<uint32_t> d_blk;
+        DevBuf<uint8_t> d_buf;
+        PinBuf<uint8_t> h_buf;   // pinned: the call's inputs packed for one copy, then its outputs
+        Event ev0, ev1;
         float ms = 0.f;
     };
     std::vector<Dev> dev;
@@ -190,9 +188,9 @@ int acl_slice(tm_acl* acl, Replica& R, const tm_acl_clients* cl, const uint8_t* 
     const size_t o_ver = o;  o = up16(o + n);
     const size_t total = o;
     int rc;
-    if ((rc = dev_reserve(D.d_buf, D.c_buf, total))) return rc;
-    if ((rc = host_reserve(D.h_buf, D.ch_buf, total))) return rc;
-    uint8_t* h = D.h_buf;
+    if ((rc = D.d_buf.reserve(total))) return rc;
+    if ((rc = D.h_buf.reserve(total))) return rc;
+    uint8_t* h = D.h_buf.p;
     if (nbytes) memcpy(h + o_top, topics + base, nbytes);
     memset(h + o_top + nbytes, 0, 16);
     memcpy(h + o_off, offsets + lo, ((size_t)n + 1) * 8);
@@ -209,10 +207,10 @@ int acl_slice(tm_acl* acl, Replica& R, const tm_acl_clients* cl, const uint8_t* 
         memcpy(h + o_peer, cl->peerhost, (size_t)m * 16);
     }
     const hipStream_t s = R.stream;
-    uint8_t* d = D.d_buf;
+    uint8_t* d = D.d_buf.p;
     HIP_OK(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
     AclArgs a{};
-    a.blk = D.d_blk;
+    a.blk = D.d_blk.p;
     a.n_rules = acl->n_rules;
     a.topics = d + o_top;
     a.offs = reinterpret_cast<const uint64_t*>(d + o_off);
@@ -229,12 +227,12 @@ int acl_slice(tm_acl* acl, Replica& R, const tm_acl_clients* cl, const uint8_t* 
     a.peer = reinterpret_cast<const uint4*>(d + o_peer);
     a.verdict = d + o_ver;
     a.rule = reinterpret_cast<uint32_t*>(d + o_rule);
-    HIP_OK(hipEventRecord(D.ev0, s));
+    HIP_OK(hipEventRecord(D.ev0.e, s));
     HIP_OK(launch_acl_check(a, s));
-    HIP_OK(hipEventRecord(D.ev1, s));
+    HIP_OK(hipEventRecord(D.ev1.e, s));
     HIP_OK(hipMemcpyAsync(h + o_rule, d + o_rule, total - o_rule, hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    HIP_OK(hipEventElapsedTime(&D.ms, D.ev0, D.ev1));
+    HIP_OK(hipEventElapsedTime(&D.ms, D.ev0.e, D.ev1.e));
     memcpy(rule + lo, h + o_rule, (size_t)n * 4);
     memcpy(verdict + lo, h + o_ver, n);
     return TM_OK;
@@ -256,11 +254,11 @@ int tm_acl_create(tm_engine* e, const tm_acl_rule* rules, uint32_t n, tm_acl** o
             tm_acl::Dev& D = acl->dev[i];
             rc = [&]() -> int {
                 HIP_OK(hipSetDevice(e->reps[i]->device));
-                HIP_OK(hipMalloc((void**)&D.d_blk, acl->blk.size() * 4));
-                HIP_OK(hipMemcpy(D.d_blk, acl->blk.data(), acl->blk.size() * 4, hipMemcpyHostToDevice));
-                HIP_OK(hipEventCreate(&D.ev0));
-                HIP_OK(hipEventCreate(&D.ev1));
-                return TM_OK;
+                int r;
+                if ((r = D.d_blk.alloc(acl->blk.size()))) return r;
+                HIP_OK(hipMemcpy(D.d_blk.p, acl->blk.data(), acl->blk.size() * 4, hipMemcpyHostToDevice));
+                if ((r = D.ev0.create())) return r;
+                return D.ev1.create();
             }();
         }
         if (!e->reps.empty()) (void)e->set_device();
@@ -279,13 +277,8 @@ void tm_acl_free(tm_engine* e, tm_acl* acl) {
     if (!acl) return;
     (void)e;
     for (size_t i = 0; i < acl->dev.size(); ++i) {
-        tm_acl::Dev& D = acl->dev[i];
         if (i < acl->e->reps.size()) (void)hipSetDevice(acl->e->reps[i]->device);
-        if (D.ev0) (void)hipEventDestroy(D.ev0);
-        if (D.ev1) (void)hipEventDestroy(D.ev1);
-        dev_free(D.d_blk);
-        dev_free(D.d_buf);
-        if (D.h_buf) (void)hipHostFree(D.h_buf);
+        acl->dev[i] = {};
     }
     if (!acl->dev.empty()) (void)acl->e->set_device();
     delete acl;

@@ -17,7 +17,7 @@ int tm_engine::async_start(Replica& R) {
             R.a_slots.push_back(sl);
             sl->b.rep = &R;
             HIP_OK(hipStreamCreateWithFlags(&sl->b.own, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&sl->ev_done, hipEventDisableTiming));
+            if (int rc = sl->ev_done.create(hipEventDisableTiming)) return rc;
             R.a_free.push_back(sl);
             R.readers.push_back(&sl->b);
         }
@@ -51,14 +51,8 @@ void tm_engine::async_stop(Replica& R) {
         forget_launch(&sl->b);
         sl->b.release();
         if (sl->b.own) (void)hipStreamDestroy(sl->b.own);
-        if (sl->ev_done) (void)hipEventDestroy(sl->ev_done);
-        if (sl->h_in) (void)hipHostFree(sl->h_in);
-        if (sl->h_bin) (void)hipHostFree(sl->h_bin);
         for (GraphCache& gc : sl->gc) gc.reset();
-        if (sl->h_rows) (void)hipHostFree(sl->h_rows);
-        if (sl->h_out) (void)hipHostFree(sl->h_out);
-        if (sl->h_flag) (void)hipHostFree(sl->h_flag);
-        delete sl;
+        delete sl;   // (its event and pinned buffers with it)
     }
     R.a_slots.clear();
     R.a_free.clear();
@@ -233,16 +227,16 @@ int tm_engine::slot_launch(AsyncSlot* sl) {
         if (nb > sl->bytes_cap || sl->bytes_cap < (uint64_t)R.a_max * 64)
             sl->bytes_cap = std::max<uint64_t>({sl->bytes_cap, (uint64_t)R.a_max * 64, (uint64_t)nb + nb / 2});
         const size_t o_offs = 64, o_bytes = (o_offs + ((size_t)sl->bound + 1) * 8 + 15) & ~(size_t)15;
-        if ((rc = host_reserve_coherent(sl->h_bin, sl->c_bin, o_bytes + sl->bytes_cap + 32))) return rc;
-        *reinterpret_cast<volatile uint32_t*>(sl->h_bin) = n;
-        memcpy(sl->h_bin + o_offs, sl->offs.data(), ((size_t)n + 1) * 8);
-        if (nb) memcpy(sl->h_bin + o_bytes, sl->bytes.data(), nb);
+        if ((rc = sl->h_bin.reserve(o_bytes + sl->bytes_cap + 32))) return rc;
+        *reinterpret_cast<volatile uint32_t*>(sl->h_bin.p) = n;
+        memcpy(sl->h_bin.p + o_offs, sl->offs.data(), ((size_t)n + 1) * 8);
+        if (nb) memcpy(sl->h_bin.p + o_bytes, sl->bytes.data(), nb);
         std::lock_guard<std::recursive_mutex> g(mu);
         HIP_OK(hipSetDevice(R.device));
         tm_batch* b = &sl->b;
         const hipStream_t S = b->own;
         uint8_t* d_bin = nullptr;
-        HIP_OK(hipHostGetDevicePointer((void**)&d_bin, sl->h_bin, 0));
+        HIP_OK(hipHostGetDevicePointer((void**)&d_bin, sl->h_bin.p, 0));
         if ((rc = prepare_bounded(b, sl->bound, sl->bytes_cap, reinterpret_cast<const uint64_t*>(d_bin + o_offs),
                                   d_bin + o_bytes, reinterpret_cast<uint32_t*>(d_bin))))
             return rc;
@@ -259,24 +253,24 @@ int tm_engine::slot_launch(AsyncSlot* sl) {
                       [this, sl, x](hipStream_t st) { return slot_tail(sl, x, st); }};
         if ((rc = launch(b, false, &tail))) return rc;
         if (!tail.in_graph) HIP_OK(slot_tail(sl, x, S));
-        HIP_OK(hipEventRecord(sl->ev_done, S));
+        HIP_OK(hipEventRecord(sl->ev_done.e, S));
         return TM_OK;
     }
-    if ((rc = host_reserve(sl->h_in, sl->c_in, head + nb))) return rc;
-    memcpy(sl->h_in, sl->offs.data(), ((size_t)n + 1) * 8);
-    if (nb) memcpy(sl->h_in + head, sl->bytes.data(), nb);
+    if ((rc = sl->h_in.reserve(head + nb))) return rc;
+    memcpy(sl->h_in.p, sl->offs.data(), ((size_t)n + 1) * 8);
+    if (nb) memcpy(sl->h_in.p + head, sl->bytes.data(), nb);
     std::lock_guard<std::recursive_mutex> g(mu);
     HIP_OK(hipSetDevice(R.device));
     tm_batch* b = &sl->b;
     const hipStream_t S = b->own;
-    rc = dev_tok ? upload_packed(b, sl->h_in, n, nb)
-                 : prepare(b, sl->h_in + head, reinterpret_cast<const uint64_t*>(sl->h_in), n);
+    rc = dev_tok ? upload_packed(b, sl->h_in.p, n, nb)
+                 : prepare(b, sl->h_in.p + head, reinterpret_cast<const uint64_t*>(sl->h_in.p), n);
     if (rc) return rc;
     if ((rc = launch(b, false))) return rc;
     ExportArgs x{};
     if ((rc = slot_export_args(sl, x, n))) return rc;
     HIP_OK(slot_tail(sl, x, S));
-    HIP_OK(hipEventRecord(sl->ev_done, S));
+    HIP_OK(hipEventRecord(sl->ev_done.e, S));
     return TM_OK;
 }
 
@@ -286,27 +280,25 @@ int tm_engine::slot_export_args(AsyncSlot* sl, ExportArgs& x, uint32_t n) {
     int rc;
     tm_batch* b = &sl->b;
     const size_t hdr_bytes = tm_batch::HDR_FIXED + (size_t)n * 8;
-    if ((rc = host_reserve_coherent(sl->h_out, sl->c_out, hdr_bytes + (size_t)n * 4 + 8))) return rc;
-    uint8_t* rows8 = reinterpret_cast<uint8_t*>(sl->h_rows);
-    if ((rc = host_reserve_coherent(rows8, sl->c_rows, std::max<size_t>(b->c_sfids, 1) * 4))) return rc;
-    sl->h_rows = reinterpret_cast<uint32_t*>(rows8);
+    if ((rc = sl->h_out.reserve(hdr_bytes + (size_t)n * 4 + 8))) return rc;
+    if ((rc = sl->h_rows.reserve(std::max<size_t>(b->walk.d_sfids.cap, 1) * 4))) return rc;
     void *d_out = nullptr, *d_rows = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&d_out, sl->h_out, 0));
-    HIP_OK(hipHostGetDevicePointer(&d_rows, sl->h_rows, 0));
-    x.hdr = reinterpret_cast<const uint32_t*>(b->d_hdr);
+    HIP_OK(hipHostGetDevicePointer(&d_out, sl->h_out.p, 0));
+    HIP_OK(hipHostGetDevicePointer(&d_rows, sl->h_rows.p, 0));
+    x.hdr = reinterpret_cast<const uint32_t*>(b->walk.d_hdr.p);
     x.hdr_words = hdr_bytes / 4;
     x.h_hdr = reinterpret_cast<uint32_t*>(d_out);
-    x.count = b->d_count;
+    x.count = b->walk.d_count;
     x.h_count = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(d_out) + hdr_bytes);
     x.n = n;
-    x.rows = b->d_sfids;
+    x.rows = b->walk.d_sfids.p;
     x.h_rows = reinterpret_cast<uint32_t*>(d_rows);
-    x.rows_cap = std::min<uint64_t>(b->c_sfids, sl->c_rows / 4);
-    x.rcap = region_cap(std::min<uint64_t>(b->c_sfids, MAX_RESULT), b->one_region);
-    if (b->rep->a_spin_us && !sl->h_flag) {
-        HIP_OK(hipHostMalloc((void**)&sl->h_flag, 64, hipHostMallocCoherent | hipHostMallocMapped));
-        *sl->h_flag = 0;
-        HIP_OK(hipHostGetDevicePointer((void**)&sl->d_flag, sl->h_flag, 0));
+    x.rows_cap = std::min<uint64_t>(b->walk.d_sfids.cap, sl->h_rows.cap / 4);
+    x.rcap = region_cap(std::min<uint64_t>(b->walk.d_sfids.cap, MAX_RESULT), b->one_region);
+    if (b->rep->a_spin_us && !sl->h_flag.p) {
+        if ((rc = sl->h_flag.alloc(64))) return rc;
+        *reinterpret_cast<uint32_t*>(sl->h_flag.p) = 0;
+        HIP_OK(hipHostGetDevicePointer((void**)&sl->d_flag, sl->h_flag.p, 0));
     }
     return TM_OK;
 }
@@ -371,7 +363,7 @@ void tm_engine::completer_loop(Replica& R) {
         syncwake::in_batch = true;
         for (uint32_t i = lo; i < hi; ++i) {
             const uint32_t k = sl->d_count[i];
-            sl->calls[i].cb(sl->calls[i].ctx, TM_OK, k ? sl->h_rows + sl->d_src[i] : sl->h_rows, k);
+            sl->calls[i].cb(sl->calls[i].ctx, TM_OK, k ? sl->rows() + sl->d_src[i] : sl->rows(), k);
         }
         syncwake::in_batch = false;
         syncwake::flush();
@@ -410,8 +402,8 @@ bool tm_engine::slot_wait(AsyncSlot* sl, double& us_wait, bool& recovered) {
         return true;
     }
     const auto tw = std::chrono::steady_clock::now();
-    if (sl->h_flag && b->rep->a_spin_us) {   // poll the pinned flag first (no interrupt wake-up)
-        const volatile uint32_t* f = sl->h_flag;
+    if (sl->h_flag.p && b->rep->a_spin_us) {   // poll the pinned flag first (no interrupt wake-up)
+        const volatile uint32_t* f = reinterpret_cast<const uint32_t*>(sl->h_flag.p);
         const auto lim = tw + std::chrono::microseconds(b->rep->a_spin_us);
         for (uint32_t it = 0; *f != sl->seq; ++it) {
             __builtin_ia32_pause();
@@ -419,17 +411,17 @@ bool tm_engine::slot_wait(AsyncSlot* sl, double& us_wait, bool& recovered) {
         }
         // the flag follows the export in stream order; the event right after it
         if (*f == sl->seq)
-            while (hipEventQuery(sl->ev_done) == hipErrorNotReady && std::chrono::steady_clock::now() < lim)
+            while (hipEventQuery(sl->ev_done.e) == hipErrorNotReady && std::chrono::steady_clock::now() < lim)
                 __builtin_ia32_pause();
     }
-    if (hipEventSynchronize(sl->ev_done) != hipSuccess) {
+    if (hipEventSynchronize(sl->ev_done.e) != hipSuccess) {
         fail_all(TM_EIO);
         return true;
     }
     us_wait = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count();
     const size_t hdr_bytes = tm_batch::HDR_FIXED + (size_t)n * 8;
-    const uint32_t* ctrl = reinterpret_cast<const uint32_t*>(sl->h_out);
-    const unsigned long long* stats = reinterpret_cast<const unsigned long long*>(sl->h_out + CTRL_WORDS * 4);
+    const uint32_t* ctrl = reinterpret_cast<const uint32_t*>(sl->h_out.p);
+    const unsigned long long* stats = reinterpret_cast<const unsigned long long*>(sl->h_out.p + CTRL_WORDS * 4);
     uint32_t err = 0;
     uint64_t need = 0, staged = 0;
     int rc = check_ctrl(ctrl, stats, &err, &need, &staged);
@@ -438,7 +430,7 @@ bool tm_engine::slot_wait(AsyncSlot* sl, double& us_wait, bool& recovered) {
         return true;
     }
     if (b->one_region) need = staged;
-    if (!err && need > sl->c_rows / 4) err = ERR_STAGING;   // (cannot happen: rows hold the staging area)
+    if (!err && need > sl->h_rows.cap / 4) err = ERR_STAGING;   // (cannot happen: rows hold the staging area)
     if (err) {
         // capacity miss (staging, generic-path scratch): the CSR path grows
         // and re-runs, then the rows come from the CSR
@@ -449,11 +441,11 @@ bool tm_engine::slot_wait(AsyncSlot* sl, double& us_wait, bool& recovered) {
             (void)hipSetDevice(b->rep->device);
             if (b->bounded) {   // sized for its bound: re-run as a packed batch of exactly these calls
                 const size_t nb = sl->bytes.size(), head = packed_head(n);
-                rc = host_reserve(sl->h_in, sl->c_in, head + nb);
+                rc = sl->h_in.reserve(head + nb);
                 if (!rc) {
-                    memcpy(sl->h_in, sl->offs.data(), ((size_t)n + 1) * 8);
-                    if (nb) memcpy(sl->h_in + head, sl->bytes.data(), nb);
-                    rc = upload_packed(b, sl->h_in, n, nb);
+                    memcpy(sl->h_in.p, sl->offs.data(), ((size_t)n + 1) * 8);
+                    if (nb) memcpy(sl->h_in.p + head, sl->bytes.data(), nb);
+                    rc = upload_packed(b, sl->h_in.p, n, nb);
                 }
                 if (!rc) rc = grow_for(b, err, need, staged);
                 if (!rc) rc = launch(b);
@@ -475,7 +467,7 @@ bool tm_engine::slot_wait(AsyncSlot* sl, double& us_wait, bool& recovered) {
         syncwake::flush();
         return true;
     }
-    sl->d_src = reinterpret_cast<const unsigned long long*>(sl->h_out + tm_batch::HDR_FIXED);
-    sl->d_count = reinterpret_cast<const uint32_t*>(sl->h_out + hdr_bytes);
+    sl->d_src = reinterpret_cast<const unsigned long long*>(sl->h_out.p + tm_batch::HDR_FIXED);
+    sl->d_count = reinterpret_cast<const uint32_t*>(sl->h_out.p + hdr_bytes);
     return false;
 }

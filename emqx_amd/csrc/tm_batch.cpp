@@ -13,12 +13,12 @@ int tm_engine::ensure_slow_scratch(tm_batch* b) {
         b->s_waves = w;
     }
     const size_t q = (size_t)b->s_waves * b->s_qcap, o = (size_t)b->s_waves * b->s_ocap;
-    if ((rc = dev_reserve(b->d_sqpar, b->c_sq, q))) return rc;
-    if ((rc = dev_reserve(b->d_sqpw, b->c_sq2, q))) return rc;
-    if ((rc = dev_reserve(b->d_sqmeta, b->c_sq3, q))) return rc;
-    if ((rc = dev_reserve(b->d_sqkey, b->c_sq4, q))) return rc;
-    if ((rc = dev_reserve(b->d_sofid, b->c_so, o))) return rc;
-    if ((rc = dev_reserve(b->d_sokey, b->c_so2, o))) return rc;
+    if ((rc = b->gen.d_sqpar.reserve(q))) return rc;
+    if ((rc = b->gen.d_sqpw.reserve(q))) return rc;
+    if ((rc = b->gen.d_sqmeta.reserve(q))) return rc;
+    if ((rc = b->gen.d_sqkey.reserve(q))) return rc;
+    if ((rc = b->gen.d_sofid.reserve(o))) return rc;
+    if ((rc = b->gen.d_sokey.reserve(o))) return rc;
     return TM_OK;
 }
 
@@ -110,16 +110,16 @@ int tm_engine::tokenize_into(const uint8_t* bytes, const uint64_t* offs, uint32_
 int tm_engine::upload_batch(tm_batch* b) {
     int rc;
     const uint32_t n = b->n;
-    if ((rc = dev_reserve(b->d_words, b->c_words, b->h_words.size()))) return rc;
-    if ((rc = dev_reserve(b->d_toff, b->c_toff, (size_t)n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_tflags, b->c_tflags, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_slow, b->c_slow, std::max<size_t>(b->h_slow.size(), 1)))) return rc;
+    if ((rc = b->tok.d_words.reserve(b->h_words.size()))) return rc;
+    if ((rc = b->tok.d_toff.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_tflags.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_slow.reserve(std::max<size_t>(b->h_slow.size(), 1)))) return rc;
     const hipStream_t S = st(b);
-    HIP_OK(hipMemcpyAsync(b->d_words, b->h_words.data(), b->h_words.size() * 4, hipMemcpyHostToDevice, S));
-    HIP_OK(hipMemcpyAsync(b->d_toff, b->h_toff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, S));
-    if (n) HIP_OK(hipMemcpyAsync(b->d_tflags, b->h_tflags.data(), n, hipMemcpyHostToDevice, S));
+    HIP_OK(hipMemcpyAsync(b->tok.d_words.p, b->h_words.data(), b->h_words.size() * 4, hipMemcpyHostToDevice, S));
+    HIP_OK(hipMemcpyAsync(b->tok.d_toff.p, b->h_toff.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, S));
+    if (n) HIP_OK(hipMemcpyAsync(b->tok.d_tflags.p, b->h_tflags.data(), n, hipMemcpyHostToDevice, S));
     if (!b->h_slow.empty())
-        HIP_OK(hipMemcpyAsync(b->d_slow, b->h_slow.data(), b->h_slow.size() * 4, hipMemcpyHostToDevice, S));
+        HIP_OK(hipMemcpyAsync(b->tok.d_slow.p, b->h_slow.data(), b->h_slow.size() * 4, hipMemcpyHostToDevice, S));
     b->dev_slow = false;
     return reserve_outputs(b);
 }
@@ -135,13 +135,13 @@ int tm_engine::tokenize_device(const uint8_t* topics, const uint64_t* offsets, u
     const uint64_t base = st ? st_base : offsets[0], nbytes = st ? st_nbytes : offsets[n] - base;
     if (nbytes + n + 1 > 0xFFFFFFF0ull) return TM_EOVERFLOW;
     if ((rc = sync_device(&R))) return rc;
-    if ((rc = dev_reserve(b->d_bytes, b->c_bytes, nbytes + 16))) return rc;
-    if ((rc = dev_reserve(b->d_boffs, b->c_boffs, (size_t)n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_wcount, b->c_wcount, (size_t)n + 2))) return rc;   // per tile + total
-    if ((rc = dev_reserve(b->d_slow, b->c_slow, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_nslow, b->c_nslow, 2))) return rc;
-    if ((rc = dev_reserve(b->d_bsums, b->c_bsums, (size_t)scan_block_count(n) + 1))) return rc;
-    if ((rc = host_reserve(b->h_total, b->ch_total, 4))) return rc;
+    if ((rc = b->tok.d_bytes.reserve(nbytes + 16))) return rc;
+    if ((rc = b->tok.d_boffs.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_wcount.reserve((size_t)n + 2))) return rc;   // per tile + total
+    if ((rc = b->tok.d_slow.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_nslow.reserve(2))) return rc;
+    if ((rc = b->dcsr.d_bsums.reserve((size_t)scan_block_count(n) + 1))) return rc;
+    if ((rc = b->dcsr.h_total.reserve(4))) return rc;
     if (st) {
         // each staged chunk crosses as soon as it is in place; the chunks
         // are cut at the staging's own item bounds, so a chunk never waits
@@ -152,14 +152,14 @@ int tm_engine::tokenize_device(const uint8_t* topics, const uint64_t* offsets, u
         for (uint64_t lo = base; lo < base + nbytes;) {
             const uint64_t item = lo / st->chunk_bytes, hi = std::min(base + nbytes, (item + 1) * st->chunk_bytes);
             wait_item(item);
-            HIP_OK(hipMemcpyAsync(b->d_bytes + (lo - base), topics + lo, hi - lo, hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(b->tok.d_bytes.p + (lo - base), topics + lo, hi - lo, hipMemcpyHostToDevice, stream));
             lo = hi;
         }
         for (uint64_t lo = 0; lo <= n;) {
             const uint64_t g = off_item0 + lo, item = g / st->chunk_offs;
             const uint64_t hi = std::min<uint64_t>((uint64_t)n + 1, (item + 1) * st->chunk_offs - off_item0);
             wait_item(st->nbyte_items + item);
-            HIP_OK(hipMemcpyAsync(b->d_boffs + lo, offsets + lo, (hi - lo) * 8, hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(b->tok.d_boffs.p + lo, offsets + lo, (hi - lo) * 8, hipMemcpyHostToDevice, stream));
             lo = hi;
         }
         if (__atomic_load_n(st->bad, __ATOMIC_ACQUIRE)) {   // (checked before any kernel reads the offsets)
@@ -167,22 +167,22 @@ int tm_engine::tokenize_device(const uint8_t* topics, const uint64_t* offsets, u
             return TM_EINVAL;
         }
     } else {
-        if (nbytes) HIP_OK(hipMemcpyAsync(b->d_bytes, topics + base, nbytes, hipMemcpyHostToDevice, stream));
-        HIP_OK(hipMemcpyAsync(b->d_boffs, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, stream));
+        if (nbytes) HIP_OK(hipMemcpyAsync(b->tok.d_bytes.p, topics + base, nbytes, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(b->tok.d_boffs.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, stream));
     }
     if (!n) HIP_OK(hipMemsetAsync(d_toff, 0, 4, stream));
     TokArgs t{};
-    t.bytes = b->d_bytes; t.offs = b->d_boffs; t.base = base; t.n = n;
-    t.keys = R.d_dkey; t.tails = R.d_tail; t.dict_mask = R.d_dict_n - 1; t.arena = R.d_arena;
-    t.wcount = b->d_wcount; t.tflags = d_tflags; t.toff = d_toff; t.words = d_words; t.words_cap = cap;
-    t.slow_list = b->d_slow; t.d_nslow = b->d_nslow;
+    t.bytes = b->tok.d_bytes.p; t.offs = b->tok.d_boffs.p; t.base = base; t.n = n;
+    t.keys = R.tab.d_dkey.p; t.tails = R.tab.d_tail.p; t.dict_mask = R.d_dict_n - 1; t.arena = R.tab.d_arena.p;
+    t.wcount = b->tok.d_wcount.p; t.tflags = d_tflags; t.toff = d_toff; t.words = d_words; t.words_cap = cap;
+    t.slow_list = b->tok.d_slow.p; t.d_nslow = b->tok.d_nslow.p;
     t.tile_topics = tok_tile_topics(n, nbytes);
     ScanArgs ts{};
-    ts.block_sums = b->d_bsums;
-    HIP_OK(launch_tokenize(t, ts, b->d_nslow + 1, stream));
-    HIP_OK(hipMemcpyAsync(b->h_total, b->d_nslow + 1, 4, hipMemcpyDeviceToHost, stream));
+    ts.block_sums = b->dcsr.d_bsums.p;
+    HIP_OK(launch_tokenize(t, ts, b->tok.d_nslow.p + 1, stream));
+    HIP_OK(hipMemcpyAsync(b->dcsr.h_total.p, b->tok.d_nslow.p + 1, 4, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    *nwords = n ? b->h_total[0] : 0;
+    *nwords = n ? b->dcsr.h_total.p[0] : 0;
     return *nwords > cap ? TM_EOVERFLOW : TM_OK;
 }
 
@@ -216,24 +216,25 @@ int tm_engine::prepare_tokens(tm_batch* b, const uint32_t* words, const uint32_t
     }
     if (device < 0) return TM_ENODEV;
     b->h_words.clear(); b->h_toff.clear(); b->h_tflags.clear(); b->h_slow.clear();
-    if ((rc = dev_reserve(b->d_words, b->c_words, std::max<uint64_t>(nwords, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_toff, b->c_toff, (size_t)n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_tflags, b->c_tflags, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_slow, b->c_slow, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_nslow, b->c_nslow, 2))) return rc;
-    if ((rc = host_reserve(b->h_bad, b->ch_bad, 2))) return rc;
-    if (nwords) HIP_OK(hipMemcpyAsync(b->d_words, words, nwords * 4, hipMemcpyDeviceToDevice, stream));
-    HIP_OK(hipMemcpyAsync(b->d_toff, toff, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, stream));
-    if (n) HIP_OK(hipMemcpyAsync(b->d_tflags, tflags, n, hipMemcpyDeviceToDevice, stream));
-    HIP_OK(hipMemsetAsync(b->d_nslow, 0, 2 * 4, stream));
+    if ((rc = b->tok.d_words.reserve(std::max<uint64_t>(nwords, 1)))) return rc;
+    if ((rc = b->tok.d_toff.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_tflags.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_slow.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_nslow.reserve(2))) return rc;
+    if ((rc = b->tok.h_bad.reserve(2))) return rc;
+    if (nwords) HIP_OK(hipMemcpyAsync(b->tok.d_words.p, words, nwords * 4, hipMemcpyDeviceToDevice, stream));
+    HIP_OK(hipMemcpyAsync(b->tok.d_toff.p, toff, ((size_t)n + 1) * 4, hipMemcpyDeviceToDevice, stream));
+    if (n) HIP_OK(hipMemcpyAsync(b->tok.d_tflags.p, tflags, n, hipMemcpyDeviceToDevice, stream));
+    HIP_OK(hipMemsetAsync(b->tok.d_nslow.p, 0, 2 * 4, stream));
     // toff[0] and toff[n] checked with the rest: a walk must never read past words[]
-    HIP_OK(launch_token_check(b->d_toff, b->d_tflags, n, nwords, b->d_slow, b->d_nslow, b->d_nslow + 1, stream));
-    HIP_OK(hipMemcpyAsync(b->h_bad, b->d_nslow, 2 * 4, hipMemcpyDeviceToHost, stream));
+    HIP_OK(launch_token_check(b->tok.d_toff.p, b->tok.d_tflags.p, n, nwords, b->tok.d_slow.p, b->tok.d_nslow.p,
+                              b->tok.d_nslow.p + 1, stream));
+    HIP_OK(hipMemcpyAsync(b->tok.h_bad.p, b->tok.d_nslow.p, 2 * 4, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    if (b->h_bad[1] || (n == 0 && nwords != 0)) return TM_EINVAL;
+    if (b->tok.h_bad.p[1] || (n == 0 && nwords != 0)) return TM_EINVAL;
     if (n == 0) {   // no thread checked toff[0] == nwords == 0
         uint32_t t0 = 0;
-        HIP_OK(hipMemcpy(&t0, b->d_toff, 4, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(&t0, b->tok.d_toff.p, 4, hipMemcpyDeviceToHost));
         if (t0 != 0) return TM_EINVAL;
     }
     b->dev_slow = true;
@@ -252,19 +253,19 @@ int tm_engine::part_buffers(tm_batch* b, uint32_t n, uint64_t nwords, PartBuffer
     b->launched = b->done = false;
     b->bytes.clear(); b->offs.clear();
     b->h_words.clear(); b->h_toff.clear(); b->h_tflags.clear(); b->h_slow.clear();
-    if ((rc = dev_reserve(b->d_words, b->c_words, std::max<uint64_t>(nwords, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_toff, b->c_toff, (size_t)n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_tflags, b->c_tflags, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_slow, b->c_slow, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_nslow, b->c_nslow, 2))) return rc;
-    if ((rc = host_reserve(b->h_bad, b->ch_bad, 2))) return rc;
-    b->h_bad[0] = b->h_bad[1] = 0;
+    if ((rc = b->tok.d_words.reserve(std::max<uint64_t>(nwords, 1)))) return rc;
+    if ((rc = b->tok.d_toff.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_tflags.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_slow.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_nslow.reserve(2))) return rc;
+    if ((rc = b->tok.h_bad.reserve(2))) return rc;
+    b->tok.h_bad.p[0] = b->tok.h_bad.p[1] = 0;
     b->dev_slow = true;
     if ((rc = reserve_outputs(b))) return rc;
-    out->words = b->d_words;
-    out->toff = b->d_toff;
-    out->tflags = b->d_tflags;
-    out->words_cap = b->c_words;
+    out->words = b->tok.d_words.p;
+    out->toff = b->tok.d_toff.p;
+    out->tflags = b->tok.d_tflags.p;
+    out->words_cap = b->tok.d_words.cap;
     out->stream = st(b);
     out->device = b->rep->device;
     return TM_OK;
@@ -275,31 +276,30 @@ int tm_engine::export_batch(tm_batch* b, uint32_t* d_counts, uint32_t* d_ids, ui
     if (int rc = ensure_dense(b)) return rc;
     const uint64_t top = (uint64_t)(nd.size() ? nd.size() - 1 : 0) * mul + add;
     if (top > 0xFFFFFFFFull) return TM_EOVERFLOW;
-    HIP_OK(launch_export(b->d_rowoff, b->d_ids, b->n, b->total, d_counts, d_ids, mul, add, st(b)));
+    HIP_OK(launch_export(b->dcsr.d_rowoff.p, b->dcsr.d_ids.p, b->n, b->total, d_counts, d_ids, mul, add, st(b)));
     HIP_OK(hipStreamSynchronize(st(b)));
     return TM_OK;
 }
 
 int tm_engine::reserve_hdr(tm_batch* b, size_t cap) {
-    if (b->d_hdr && b->hdr_cap >= cap) return TM_OK;
+    if (b->walk.d_hdr.p && b->walk.hdr_cap >= cap) return TM_OK;
     cap = std::max<size_t>(cap + cap / 4, 1024);
-    uint8_t *d = nullptr, *h = nullptr;
-    HIP_OK(hipMalloc((void**)&d, tm_batch::hdr_bytes(cap)));
-    if (hipHostMalloc((void**)&h, tm_batch::hdr_bytes(cap), hipHostMallocDefault) != hipSuccess) {
-        (void)hipFree(d);
+    DevBuf<uint8_t> nd;   // both new blocks first, then the old ones go
+    PinBuf<uint8_t> nh;
+    if (int rc = nd.alloc(tm_batch::hdr_bytes(cap))) return rc;
+    if (nh.alloc(tm_batch::hdr_bytes(cap))) {
         snprintf(last_error(), 512, "hipHostMalloc of %zu bytes failed", tm_batch::hdr_bytes(cap));
         return TM_ENOMEM;
     }
-    dev_free(b->d_hdr);
-    if (b->h_hdr) (void)hipHostFree(b->h_hdr);
-    b->d_hdr = d;
-    b->h_hdr = h;
-    b->hdr_cap = cap;
+    b->walk.d_hdr = std::move(nd);
+    b->walk.h_hdr = std::move(nh);
+    uint8_t *d = b->walk.d_hdr.p, *h = b->walk.h_hdr.p;
+    b->walk.hdr_cap = cap;
     const size_t o_stats = CTRL_WORDS * 4, o_src = tm_batch::HDR_FIXED, o_count = o_src + cap * 8;
-    b->d_ctrl = (uint32_t*)d; b->h_ctrl = (uint32_t*)h;
-    b->d_stats = (unsigned long long*)(d + o_stats); b->h_stats = (unsigned long long*)(h + o_stats);
-    b->d_src = (unsigned long long*)(d + o_src); b->h_src = (unsigned long long*)(h + o_src);
-    b->d_count = (uint32_t*)(d + o_count); b->h_count = (uint32_t*)(h + o_count);
+    b->walk.d_ctrl = (uint32_t*)d; b->walk.h_ctrl = (uint32_t*)h;
+    b->walk.d_stats = (unsigned long long*)(d + o_stats); b->walk.h_stats = (unsigned long long*)(h + o_stats);
+    b->walk.d_src = (unsigned long long*)(d + o_src); b->walk.h_src = (unsigned long long*)(h + o_src);
+    b->walk.d_count = (uint32_t*)(d + o_count); b->walk.h_count = (uint32_t*)(h + o_count);
     return TM_OK;
 }
 
@@ -308,20 +308,20 @@ int tm_engine::reserve_outputs(tm_batch* b) {
     const uint32_t n = b->n;
     const size_t nn = std::max<size_t>(n, 1);
     if ((rc = reserve_hdr(b, nn))) return rc;
-    if ((rc = dev_reserve(b->d_rowoff, b->c_rowoff, nn + 1))) return rc;
-    if ((rc = dev_reserve(b->d_bsums, b->c_bsums, (size_t)scan_block_count(n) + 1))) return rc;
-    if ((rc = dev_reserve(b->d_ovf, b->c_ovf, nn))) return rc;
-    if ((rc = dev_reserve(b->d_total, b->c_total, 1))) return rc;
+    if ((rc = b->dcsr.d_rowoff.reserve(nn + 1))) return rc;
+    if ((rc = b->dcsr.d_bsums.reserve((size_t)scan_block_count(n) + 1))) return rc;
+    if ((rc = b->dcsr.d_ovf.reserve(nn))) return rc;
+    if ((rc = b->dcsr.d_total.reserve(1))) return rc;
     if ((rc = reserve_rows(b))) return rc;
-    if (!b->ev0) {
-        HIP_OK(hipEventCreate(&b->ev0));
-        HIP_OK(hipEventCreate(&b->ev1));
-        HIP_OK(hipEventCreate(&b->ev2));
-        HIP_OK(hipEventCreate(&b->evt));
-        HIP_OK(hipEventCreate(&b->evc0));
-        HIP_OK(hipEventCreate(&b->evc1));
-        HIP_OK(hipEventCreateWithFlags(&b->ev_end, hipEventDisableTiming));
-        HIP_OK(hipEventCreate(&b->evq));
+    if (!b->walk.ev0.e) {
+        if ((rc = b->walk.ev0.create())) return rc;
+        if ((rc = b->walk.ev1.create())) return rc;
+        if ((rc = b->walk.ev2.create())) return rc;
+        if ((rc = b->tok.evt.create())) return rc;
+        if ((rc = b->dcsr.evc0.create())) return rc;
+        if ((rc = b->dcsr.evc1.create())) return rc;
+        if ((rc = b->walk.ev_end.create(hipEventDisableTiming))) return rc;
+        if ((rc = b->walk.evq.create())) return rc;
     }
     return TM_OK;
 }
@@ -331,10 +331,10 @@ int tm_engine::reserve_rows(tm_batch* b) {
     const uint64_t fast =
         std::max<uint64_t>((uint64_t)match_waves(b->n, b->rep->device, qcap) * tile_topics(b->n) * row_cap, 1);
     // + a byte per entry past the rows: the emission-log variant's lanes (TM_EMIT_LOG)
-    if ((rc = dev_reserve(b->d_rows, b->c_rows, fast + fast / 8 + 8))) return rc;
-    if ((rc = dev_reserve(b->d_sfids, b->c_sfids, std::max<uint64_t>((uint64_t)b->n * 32, staging_min)))) return rc;
-    if ((rc = dev_reserve(b->d_ids, b->c_ids, std::max<uint64_t>((uint64_t)b->n * 32, 1u << 16)))) return rc;
-    if ((rc = host_reserve(b->h_total, b->ch_total, 4))) return rc;
+    if ((rc = b->walk.d_rows.reserve(fast + fast / 8 + 8))) return rc;
+    if ((rc = b->walk.d_sfids.reserve(std::max<uint64_t>((uint64_t)b->n * 32, staging_min)))) return rc;
+    if ((rc = b->dcsr.d_ids.reserve(std::max<uint64_t>((uint64_t)b->n * 32, 1u << 16)))) return rc;
+    if ((rc = b->dcsr.h_total.reserve(4))) return rc;
     return TM_OK;
 }
 
@@ -444,29 +444,29 @@ int tm_engine::upload_bytes(tm_batch* b, const uint8_t* topics, const uint64_t* 
     const uint64_t base = offsets[0], nbytes = offsets[n] - base;
     if (nbytes + n + 1 > 0xFFFFFFF0ull) return TM_EOVERFLOW;   // u32 word offsets
     b->tok_base = base;
-    if ((rc = dev_reserve(b->d_bytes, b->c_bytes, nbytes + 16))) return rc;   // +16: no tail reads past
-    if ((rc = dev_reserve(b->d_boffs, b->c_boffs, (size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_bytes.reserve(nbytes + 16))) return rc;   // +16: no tail reads past
+    if ((rc = b->tok.d_boffs.reserve((size_t)n + 1))) return rc;
     if ((rc = reserve_tokens(b, n, nbytes))) return rc;
-    if (nbytes) HIP_OK(hipMemcpyAsync(b->d_bytes, topics + base, nbytes, hipMemcpyHostToDevice, S));
-    HIP_OK(hipMemcpyAsync(b->d_boffs, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, S));
+    if (nbytes) HIP_OK(hipMemcpyAsync(b->tok.d_bytes.p, topics + base, nbytes, hipMemcpyHostToDevice, S));
+    HIP_OK(hipMemcpyAsync(b->tok.d_boffs.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, S));
     // the caller's buffers are only borrowed for the call; tm_match_batch
     // (and the async slots, whose inputs are their own pinned buffers)
     // wait for the whole pipeline later, so they skip this sync
     if (!upload_nosync && !b->own) HIP_OK(hipStreamSynchronize(S));
-    b->in_bytes = b->d_bytes;
-    b->in_offs = b->d_boffs;
+    b->tok.in_bytes = b->tok.d_bytes.p;
+    b->tok.in_offs = b->tok.d_boffs.p;
     return tokens_pending(b);
 }
 
 int tm_engine::reserve_tokens(tm_batch* b, uint32_t n, uint64_t nbytes) {
     int rc;
     b->nwords = nbytes + n;                  // bound: one word per byte + 1 per topic
-    if ((rc = dev_reserve(b->d_wcount, b->c_wcount, (size_t)n + 2))) return rc;   // per tile + total
-    if ((rc = dev_reserve(b->d_words, b->c_words, std::max<uint64_t>(b->nwords, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_toff, b->c_toff, (size_t)n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_tflags, b->c_tflags, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_slow, b->c_slow, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_nslow, b->c_nslow, 2))) return rc;
+    if ((rc = b->tok.d_wcount.reserve((size_t)n + 2))) return rc;   // per tile + total
+    if ((rc = b->tok.d_words.reserve(std::max<uint64_t>(b->nwords, 1)))) return rc;
+    if ((rc = b->tok.d_toff.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->tok.d_tflags.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_slow.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->tok.d_nslow.reserve(2))) return rc;
     return TM_OK;
 }
 
@@ -484,44 +484,45 @@ int tm_engine::reserve_dedup(tm_batch* b, uint64_t nbytes) {
     b->dd_bytes = nbytes;
     const size_t nblk = dedup_blocks((uint32_t)n);
     const size_t nb = scan_block_count((uint32_t)nblk) + 1;
-    void* old_tab = b->d_dtab;
-    if ((rc = dev_reserve(b->d_dtab, b->c_dtab, cap))) return rc;
-    if (b->d_dtab != old_tab || old_mask != b->dtab_mask) b->dtab_dirty = true;
-    if ((rc = dev_reserve(b->d_dsrow, b->c_dsrow, cap))) return rc;
-    if ((rc = dev_reserve(b->d_dsmeta, b->c_dsmeta, cap))) return rc;
-    if ((rc = dev_reserve(b->d_drrep, b->c_drrep, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_dbsum, b->c_dbsum, n / DD_EXPAND_TILE + 2))) return rc;   // (expansion blocks)
-    if ((rc = dev_reserve(b->d_dslot, b->c_dslot, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_dbits, b->c_dbits, std::max<size_t>(nblk, 1) * (DD_TILE / 64)))) return rc;
-    if ((rc = dev_reserve(b->d_dbc, b->c_dbc, nblk + 1))) return rc;
-    if ((rc = dev_reserve(b->d_dbb, b->c_dbb, nblk + 1))) return rc;
-    if ((rc = dev_reserve(b->d_drbs, b->c_drbs, nb))) return rc;
-    if ((rc = dev_reserve(b->d_dbbs, b->c_dbbs, nb))) return rc;
-    if ((rc = dev_reserve(b->d_rowof, b->c_rowof, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_cbytes, b->c_cbytes, nbytes + 32))) return rc;   // (the tokeniser's 16-B windows)
-    if ((rc = dev_reserve(b->d_coffs, b->c_coffs, n + 1))) return rc;
-    if ((rc = dev_reserve(b->d_dd, b->c_dd, 2))) return rc;
-    if ((rc = dev_reserve(b->d_pcount, b->c_pcount, std::max<size_t>(n, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_psrc, b->c_psrc, std::max<size_t>(n, 1)))) return rc;
-    if (!b->evd) {
-        HIP_OK(hipEventCreate(&b->evd));
-        HIP_OK(hipEventCreate(&b->evx0));
-        HIP_OK(hipEventCreate(&b->evx1));
+    void* old_tab = b->dd.d_dtab.p;
+    if ((rc = b->dd.d_dtab.reserve(cap))) return rc;
+    if (b->dd.d_dtab.p != old_tab || old_mask != b->dtab_mask) b->dtab_dirty = true;
+    if ((rc = b->dd.d_dsrow.reserve(cap))) return rc;
+    if ((rc = b->dd.d_dsmeta.reserve(cap))) return rc;
+    if ((rc = b->dd.d_drrep.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->dd.d_dbsum.reserve(n / DD_EXPAND_TILE + 2))) return rc;   // (expansion blocks)
+    if ((rc = b->dd.d_dslot.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->dd.d_dbits.reserve(std::max<size_t>(nblk, 1) * (DD_TILE / 64)))) return rc;
+    if ((rc = b->dd.d_dbc.reserve(nblk + 1))) return rc;
+    if ((rc = b->dd.d_dbb.reserve(nblk + 1))) return rc;
+    if ((rc = b->dd.d_drbs.reserve(nb))) return rc;
+    if ((rc = b->dd.d_dbbs.reserve(nb))) return rc;
+    if ((rc = b->dd.d_rowof.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->dd.d_cbytes.reserve(nbytes + 32))) return rc;   // (the tokeniser's 16-B windows)
+    if ((rc = b->dd.d_coffs.reserve(n + 1))) return rc;
+    if ((rc = b->dd.d_dd.reserve(2))) return rc;
+    if ((rc = b->dd.d_pcount.reserve(std::max<size_t>(n, 1)))) return rc;
+    if ((rc = b->dd.d_psrc.reserve(std::max<size_t>(n, 1)))) return rc;
+    if (!b->dd.evd.e) {
+        if ((rc = b->dd.evd.create())) return rc;
+        if ((rc = b->dd.evx0.create())) return rc;
+        if ((rc = b->dd.evx1.create())) return rc;
     }
     return TM_OK;
 }
 
 DedupArgs tm_engine::dedup_args(tm_batch* b) const {
     DedupArgs d{};
-    d.bytes = b->in_bytes; d.offs = b->in_offs; d.base = b->tok_base; d.n = b->n_pub;
-    d.table = b->d_dtab; d.mask = b->dtab_mask;
-    d.slot = b->d_dslot; d.repbits = b->d_dbits; d.bcount = b->d_dbc; d.bbytes = b->d_dbb;
-    d.rbs = b->d_drbs; d.bbs = b->d_dbbs; d.srow = b->d_dsrow; d.rrep = b->d_drrep;
-    d.smeta = b->d_dsmeta;
-    d.row_of = b->d_rowof; d.cbytes = b->d_cbytes; d.coffs = b->d_coffs; d.dd = b->d_dd;
-    d.ctrl = b->d_ctrl; d.count = b->d_count; d.src = b->d_src; d.pcount = b->d_pcount; d.psrc = b->d_psrc;
-    d.stats = b->d_stats;
-    d.bsum = b->d_dbsum;
+    d.bytes = b->tok.in_bytes; d.offs = b->tok.in_offs; d.base = b->tok_base; d.n = b->n_pub;
+    d.table = b->dd.d_dtab.p; d.mask = b->dtab_mask;
+    d.slot = b->dd.d_dslot.p; d.repbits = b->dd.d_dbits.p; d.bcount = b->dd.d_dbc.p; d.bbytes = b->dd.d_dbb.p;
+    d.rbs = b->dd.d_drbs.p; d.bbs = b->dd.d_dbbs.p; d.srow = b->dd.d_dsrow.p; d.rrep = b->dd.d_drrep.p;
+    d.smeta = b->dd.d_dsmeta.p;
+    d.row_of = b->dd.d_rowof.p; d.cbytes = b->dd.d_cbytes.p; d.coffs = b->dd.d_coffs.p; d.dd = b->dd.d_dd.p;
+    d.ctrl = b->walk.d_ctrl; d.count = b->walk.d_count; d.src = b->walk.d_src;
+    d.pcount = b->dd.d_pcount.p; d.psrc = b->dd.d_psrc.p;
+    d.stats = b->walk.d_stats;
+    d.bsum = b->dd.d_dbsum.p;
     d.weak_hash = kn.dedup_weak_hash ? 1u : 0u;
     return d;
 }
@@ -529,11 +530,11 @@ DedupArgs tm_engine::dedup_args(tm_batch* b) const {
 // the dedup passes (no table clear: clear_dedup_table, outside any capture)
 int tm_engine::enqueue_dedup(tm_batch* b, hipStream_t S) {
     const DedupArgs d = dedup_args(b);
-    if (!d.n) HIP_OK(hipMemsetAsync(b->d_dd, 0, 8, S));   // (no compact kernel: zero rows)
+    if (!d.n) HIP_OK(hipMemsetAsync(b->dd.d_dd.p, 0, 8, S));   // (no compact kernel: zero rows)
     const uint32_t nblk = dedup_blocks(d.n);
     ScanArgs rs{}, bs{};
-    rs.count = d.bcount; rs.row_off = d.bcount; rs.block_sums = b->d_drbs; rs.n = nblk;   // (in place)
-    bs.count = d.bbytes; bs.row_off = d.bbytes; bs.block_sums = b->d_dbbs; bs.n = nblk;
+    rs.count = d.bcount; rs.row_off = d.bcount; rs.block_sums = b->dd.d_drbs.p; rs.n = nblk;   // (in place)
+    bs.count = d.bbytes; bs.row_off = d.bbytes; bs.block_sums = b->dd.d_dbbs.p; bs.n = nblk;
     HIP_OK(launch_dedup(d, rs, bs, S));
     return TM_OK;
 }
@@ -541,7 +542,7 @@ int tm_engine::enqueue_dedup(tm_batch* b, hipStream_t S) {
 // a dirty table (new, or a pass whose expansion was not waited for) is
 // cleared before the next pass; a clean one is zero already
 int tm_engine::clear_dedup_table(tm_batch* b, hipStream_t S) {
-    if (b->dtab_dirty) HIP_OK(hipMemsetAsync(b->d_dtab, 0, (b->dtab_mask + 1) * 8, S));
+    if (b->dtab_dirty) HIP_OK(hipMemsetAsync(b->dd.d_dtab.p, 0, (b->dtab_mask + 1) * 8, S));
     b->dtab_dirty = true;   // until this pass's expansion has been waited for
     return TM_OK;
 }
@@ -569,10 +570,10 @@ int tm_engine::upload_packed(tm_batch* b, const uint8_t* blk, uint32_t n, uint64
     b->offs.clear();
     b->tok_base = 0;
     if ((rc = reserve_tokens(b, n, nbytes))) return rc;
-    if ((rc = dev_reserve(b->d_in, b->c_in, head + nbytes + 16))) return rc;   // +16: no tail reads past
-    HIP_OK(hipMemcpyAsync(b->d_in, blk, head + nbytes, hipMemcpyHostToDevice, b->own));
-    b->in_offs = reinterpret_cast<const uint64_t*>(b->d_in);
-    b->in_bytes = b->d_in + head;
+    if ((rc = b->tok.d_in.reserve(head + nbytes + 16))) return rc;   // +16: no tail reads past
+    HIP_OK(hipMemcpyAsync(b->tok.d_in.p, blk, head + nbytes, hipMemcpyHostToDevice, b->own));
+    b->tok.in_offs = reinterpret_cast<const uint64_t*>(b->tok.d_in.p);
+    b->tok.in_bytes = b->tok.d_in.p + head;
     return tokens_pending(b);
 }
 
@@ -595,8 +596,8 @@ int tm_engine::prepare_bounded(tm_batch* b, uint32_t bound, uint64_t bytes_cap, 
     b->offs.clear();
     b->tok_base = 0;
     if ((rc = reserve_tokens(b, bound, bytes_cap))) return rc;
-    b->in_offs = d_offs;
-    b->in_bytes = d_bytes;
+    b->tok.in_offs = d_offs;
+    b->tok.in_bytes = d_bytes;
     b->d_nb = d_n;
     b->bounded = true;
     return tokens_pending(b);
@@ -607,11 +608,11 @@ int tm_engine::prepare_bounded(tm_batch* b, uint32_t bound, uint64_t bytes_cap, 
 // by the runtime), so the replay's whole span is its walk time.
 hipError_t tm_engine::graph_replay(tm_batch* b, hipStream_t S) {
     hipError_t e;
-    if (b->dedup_timed && (e = hipEventRecord(b->evd, S)) != hipSuccess) return e;
-    if ((e = hipEventRecord(b->ev0, S)) != hipSuccess) return e;
+    if (b->dedup_timed && (e = hipEventRecord(b->dd.evd.e, S)) != hipSuccess) return e;
+    if ((e = hipEventRecord(b->walk.ev0.e, S)) != hipSuccess) return e;
     if ((e = hipGraphLaunch(b->graph.exec, S)) != hipSuccess) return e;
-    if ((e = hipEventRecord(b->ev1, S)) != hipSuccess) return e;
-    if ((e = hipEventRecord(b->ev2, S)) != hipSuccess) return e;
+    if ((e = hipEventRecord(b->walk.ev1.e, S)) != hipSuccess) return e;
+    if ((e = hipEventRecord(b->walk.ev2.e, S)) != hipSuccess) return e;
     ++graph_launches;
     return hipSuccess;
 }
@@ -650,17 +651,17 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
         if ((rc = tokenize(b))) return rc;
         if ((rc = upload_batch(b))) return rc;
     }
-    if (csr) HIP_OK(hipEventRecord(b->evq, S));   // (before the delta upload and the waits below)
+    if (csr) HIP_OK(hipEventRecord(b->walk.evq.e, S));   // (before the delta upload and the waits below)
     if ((rc = sync_device(&R))) return rc;
     if (b->own && b->seen_upload != R.upload_seq) {   // trie deltas still in flight on the replica stream land first
-        HIP_OK(hipStreamWaitEvent(S, R.ev_sync, 0));
+        HIP_OK(hipStreamWaitEvent(S, R.tab.ev_sync.e, 0));
         b->seen_upload = R.upload_seq;
     }
     if ((rc = ensure_slow_scratch(b))) return rc;
     if (checked) {
-        if ((rc = dev_reserve(R.d_dbg, R.c_dbg, 8))) return rc;
-        if ((rc = host_reserve(R.h_dbg, R.ch_dbg, 8))) return rc;
-        HIP_OK(hipMemsetAsync(R.d_dbg, 0, 8 * 4, S));
+        if ((rc = R.tab.d_dbg.reserve(8))) return rc;
+        if ((rc = R.tab.h_dbg.reserve(8))) return rc;
+        HIP_OK(hipMemsetAsync(R.tab.d_dbg.p, 0, 8 * 4, S));
     }
     // A device-deduplicated batch: fresh bytes are deduplicated first, and
     // only the rows are tokenised (again when the dictionary grew) and
@@ -683,23 +684,24 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     ScanArgs ts{};
     if (tokenize_now) {
         b->tok_dict = dict.size();
-        t.zero = reinterpret_cast<uint32_t*>(b->d_hdr);   // the tokeniser's first kernel clears ctrl + stats
+        t.zero = reinterpret_cast<uint32_t*>(b->walk.d_hdr.p);   // the tokeniser's first kernel clears ctrl + stats
         t.zero_words = tm_batch::HDR_FIXED / 4;
-        t.bytes = b->in_bytes; t.offs = b->in_offs; t.base = b->tok_base; t.n = b->n;
-        t.keys = R.d_dkey; t.tails = R.d_tail; t.dict_mask = R.d_dict_n - 1; t.arena = R.d_arena;
-        t.wcount = b->d_wcount; t.tflags = b->d_tflags; t.toff = b->d_toff; t.words = b->d_words;
-        t.words_cap = b->c_words;
-        t.slow_list = b->d_slow; t.d_nslow = b->d_nslow;
+        t.bytes = b->tok.in_bytes; t.offs = b->tok.in_offs; t.base = b->tok_base; t.n = b->n;
+        t.keys = R.tab.d_dkey.p; t.tails = R.tab.d_tail.p; t.dict_mask = R.d_dict_n - 1; t.arena = R.tab.d_arena.p;
+        t.wcount = b->tok.d_wcount.p; t.tflags = b->tok.d_tflags.p;
+        t.toff = b->tok.d_toff.p; t.words = b->tok.d_words.p;
+        t.words_cap = b->tok.d_words.cap;
+        t.slow_list = b->tok.d_slow.p; t.d_nslow = b->tok.d_nslow.p;
         t.tile_topics = tok_tile_topics(b->n, b->nwords - b->n);   // nwords = bytes + topics (reserve_tokens)
         t.d_n = nullptr;
         if (b->dedup_dev) {   // the rows' bytes, compacted by the dedup pass
-            t.bytes = b->d_cbytes; t.offs = b->d_coffs; t.base = 0; t.d_n = b->d_dd;
+            t.bytes = b->dd.d_cbytes.p; t.offs = b->dd.d_coffs.p; t.base = 0; t.d_n = b->dd.d_dd.p;
         }
         if (b->bounded) t.d_n = b->d_nb;   // (sized for the bound, counted in pinned memory)
-        ts.block_sums = b->d_bsums;
+        ts.block_sums = b->dcsr.d_bsums.p;
     }
     MatchArgs a{};
-    a.slots = R.d_slots;
+    a.slots = R.tab.d_slots.p;
     a.nbuckets = nbuckets();
     // (a bound on the probe run, not the exact max_disp: a longer run stops
     // at its first bucket with a free last slot all the same, and a value
@@ -707,12 +709,12 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     // churned batches valid)
     a.max_probe = max_disp <= 4 ? 4 : max_disp <= 8 ? 8 : max_disp <= 16 ? 16 : max_disp <= 48 ? 48 : max_disp;
     a.root = root_rec();
-    a.foff = R.d_foff; a.flen = R.d_flen; a.fbytes = R.d_fbytes;
-    a.words = b->d_words; a.toff = b->d_toff; a.tflags = b->d_tflags; a.n = b->n;
-    a.slow_list = b->d_slow; a.n_slow = b->dev_slow ? 0u : (uint32_t)b->h_slow.size();
-    a.d_nslow = b->dev_slow ? b->d_nslow : nullptr;
-    a.d_n = b->dedup_dev ? b->d_dd : b->bounded ? b->d_nb : nullptr;   // the rows, counted by the dedup pass
-    a.count = b->d_count; a.src = b->d_src; a.rows = b->d_rows; a.row_cap = row_cap;
+    a.foff = R.tab.d_foff.p; a.flen = R.tab.d_flen.p; a.fbytes = R.tab.d_fbytes.p;
+    a.words = b->tok.d_words.p; a.toff = b->tok.d_toff.p; a.tflags = b->tok.d_tflags.p; a.n = b->n;
+    a.slow_list = b->tok.d_slow.p; a.n_slow = b->dev_slow ? 0u : (uint32_t)b->h_slow.size();
+    a.d_nslow = b->dev_slow ? b->tok.d_nslow.p : nullptr;
+    a.d_n = b->dedup_dev ? b->dd.d_dd.p : b->bounded ? b->d_nb : nullptr;   // the rows, counted by the dedup pass
+    a.count = b->walk.d_count; a.src = b->walk.d_src; a.rows = b->walk.d_rows.p; a.row_cap = row_cap;
     a.grid = match_waves(b->n, R.device, qcap);
     a.tile_topics = tile_topics(b->n);
     a.qcap = qcap;
@@ -720,25 +722,27 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
         const uint64_t ntiles = ((uint64_t)b->n + a.tile_topics - 1) / a.tile_topics;
         a.static_rounds = std::max<uint32_t>(1, (uint32_t)(static_frac * (double)ntiles / std::max(a.grid, 1u)));
     }
-    if ((uint64_t)a.grid * a.tile_topics * row_cap > b->c_rows) {
+    if ((uint64_t)a.grid * a.tile_topics * row_cap > b->walk.d_rows.cap) {
         snprintf(last_error(), 512, "emission rows sized for fewer waves than the launch");
         return TM_EIO;
     }
-    a.sfids = b->d_sfids; a.sfids_cap = std::min<uint64_t>(b->c_sfids, MAX_RESULT);
+    a.sfids = b->walk.d_sfids.p; a.sfids_cap = std::min<uint64_t>(b->walk.d_sfids.cap, MAX_RESULT);
     a.rcap = region_cap(a.sfids_cap, b->one_region);
     a.sgmask = b->one_region ? 0u : TICKET_GROUPS - 1;
-    a.xg = b->d_ctrl + XG_WORD;
-    a.ctrl = b->d_ctrl; a.ovf_list = b->d_ovf; a.ovf_cap = (uint32_t)std::min<size_t>(b->c_ovf, 0xFFFFFFF0ull);
-    a.stats = b->d_stats;
+    a.xg = b->walk.d_ctrl + XG_WORD;
+    a.ctrl = b->walk.d_ctrl; a.ovf_list = b->dcsr.d_ovf.p;
+    a.ovf_cap = (uint32_t)std::min<size_t>(b->dcsr.d_ovf.cap, 0xFFFFFFF0ull);
+    a.stats = b->walk.d_stats;
     // a walk of many waves writes per-wave sums (one reduce kernel after it);
     // a small one adds them atomically -- a few dozen same-line atomics cost
     // less than one more launch on the per-publish path
     if (a.grid >= WSTATS_MIN_WAVES) {
-        if ((rc = dev_reserve(b->d_wstats, b->c_wstats, (size_t)a.grid * WSTATS))) return rc;
-        a.wstats = b->d_wstats;
+        if ((rc = b->walk.d_wstats.reserve((size_t)a.grid * WSTATS))) return rc;
+        a.wstats = b->walk.d_wstats.p;
     }
-    a.s_qparent = b->d_sqpar; a.s_qpw = b->d_sqpw; a.s_qmeta = b->d_sqmeta; a.s_qkey = b->d_sqkey;
-    a.s_ofid = b->d_sofid; a.s_okey = b->d_sokey;
+    a.s_qparent = b->gen.d_sqpar.p; a.s_qpw = b->gen.d_sqpw.p;
+    a.s_qmeta = b->gen.d_sqmeta.p; a.s_qkey = b->gen.d_sqkey.p;
+    a.s_ofid = b->gen.d_sofid.p; a.s_okey = b->gen.d_sokey.p;
     a.s_qcap = b->s_qcap; a.s_ocap = b->s_ocap; a.s_waves = b->s_waves; a.s_lcap = kn.slow_lds;
     a.nwords = (uint32_t)std::max<uint64_t>(b->nwords, 1);
     a.nslots = (uint32_t)slots.size();
@@ -746,13 +750,13 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     // change the launch's arguments and a captured graph stays valid)
     a.nnodes = checked ? (uint32_t)nd.size() : 0u;
     a.nfbytes = checked ? fbytes.size() : 0u;
-    a.dbg = checked ? R.d_dbg : nullptr;
+    a.dbg = checked ? R.tab.d_dbg.p : nullptr;
     ScanArgs s{};
-    s.count = b->d_count; s.src = b->d_src;
-    s.sfids = b->d_sfids; s.sfids_cap = std::min<uint64_t>(b->c_sfids, MAX_RESULT);
-    s.row_off = b->d_rowoff; s.ids = b->d_ids; s.block_sums = b->d_bsums;
-    s.n = b->n; s.ids_cap = (uint32_t)std::min<size_t>(b->c_ids, 0xFFFFFFF0ull); s.ctrl = b->d_ctrl;
-    s.dbg = checked ? R.d_dbg : nullptr;
+    s.count = b->walk.d_count; s.src = b->walk.d_src;
+    s.sfids = b->walk.d_sfids.p; s.sfids_cap = std::min<uint64_t>(b->walk.d_sfids.cap, MAX_RESULT);
+    s.row_off = b->dcsr.d_rowoff.p; s.ids = b->dcsr.d_ids.p; s.block_sums = b->dcsr.d_bsums.p;
+    s.n = b->n; s.ids_cap = (uint32_t)std::min<size_t>(b->dcsr.d_ids.cap, 0xFFFFFFF0ull); s.ctrl = b->walk.d_ctrl;
+    s.dbg = checked ? R.tab.d_dbg.p : nullptr;
     b->end_recorded = false;
     b->graphed = false;
     b->dense_enq = false;
@@ -762,28 +766,29 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     // the read-back of ctrl + stats as well)
     auto enqueue = [&](bool cap, bool csr_too) -> hipError_t {
         hipError_t e;
-        if (!tokenize_now && (e = hipMemsetAsync(b->d_hdr, 0, tm_batch::HDR_FIXED, S)) != hipSuccess) return e;
+        if (!tokenize_now && (e = hipMemsetAsync(b->walk.d_hdr.p, 0, tm_batch::HDR_FIXED, S)) != hipSuccess) return e;
         if (dedup_now) {
-            if (b->dedup_timed && !cap && (e = hipEventRecord(b->evd, S)) != hipSuccess) return e;
+            if (b->dedup_timed && !cap && (e = hipEventRecord(b->dd.evd.e, S)) != hipSuccess) return e;
             if (enqueue_dedup(b, S) != TM_OK) return hipErrorUnknown;
         }
-        if (b->tok_timed && !cap && (e = hipEventRecord(b->evt, S)) != hipSuccess) return e;
-        if (tokenize_now && (e = launch_tokenize(t, ts, b->d_nslow + 1, S)) != hipSuccess) return e;
+        if (b->tok_timed && !cap && (e = hipEventRecord(b->tok.evt.e, S)) != hipSuccess) return e;
+        if (tokenize_now && (e = launch_tokenize(t, ts, b->tok.d_nslow.p + 1, S)) != hipSuccess) return e;
         if (b->check_tokens && b->n) {
-            if ((e = hipMemsetAsync(b->d_nslow, 0, 2 * 4, S)) != hipSuccess) return e;
-            if ((e = launch_token_check(b->d_toff, b->d_tflags, b->n, b->nwords, b->d_slow, b->d_nslow,
-                                        b->d_nslow + 1, S)) != hipSuccess)
+            if ((e = hipMemsetAsync(b->tok.d_nslow.p, 0, 2 * 4, S)) != hipSuccess) return e;
+            if ((e = launch_token_check(b->tok.d_toff.p, b->tok.d_tflags.p, b->n, b->nwords, b->tok.d_slow.p,
+                                        b->tok.d_nslow.p, b->tok.d_nslow.p + 1, S)) != hipSuccess)
                 return e;
         }
-        e = launch_match(a, S, csr && !cap ? b->ev0 : nullptr, csr && !cap ? b->ev1 : nullptr, checked, 0u);
+        e = launch_match(a, S, csr && !cap ? b->walk.ev0.e : nullptr, csr && !cap ? b->walk.ev1.e : nullptr, checked,
+                         0u);
         if (e != hipSuccess) return e;
         if (b->dedup_dev) {   // every publish's row (count, start) + the delivered matches
-            if (!cap && (e = hipEventRecord(b->evx0, S)) != hipSuccess) return e;
+            if (!cap && (e = hipEventRecord(b->dd.evx0.e, S)) != hipSuccess) return e;
             if ((e = launch_dedup_expand(dedup_args(b), S)) != hipSuccess) return e;
-            if (!cap && (e = hipEventRecord(b->evx1, S)) != hipSuccess) return e;
+            if (!cap && (e = hipEventRecord(b->dd.evx1.e, S)) != hipSuccess) return e;
         }
         if (cap && csr_too)   // (ev2 is recorded after the graph's launch)
-            return hipMemcpyAsync(b->h_hdr, b->d_hdr, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S);
+            return hipMemcpyAsync(b->walk.h_hdr.p, b->walk.d_hdr.p, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S);
         return csr_too ? enqueue_csr(b, S) : hipSuccess;
     };
     // At most one of the three captured forms applies (graph_ready decides
@@ -792,9 +797,9 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     if (graph) {   // a repeated tokenised batch: memset + walk + read-back replayed
         std::vector<uint8_t> key = graph_key({}, a, s);
         auto record = [&] {
-            hipError_t e = hipMemsetAsync(b->d_hdr, 0, tm_batch::HDR_FIXED, S);
+            hipError_t e = hipMemsetAsync(b->walk.d_hdr.p, 0, tm_batch::HDR_FIXED, S);
             // timing events as external nodes: every replay re-records them
-            if (e == hipSuccess) e = launch_match(a, S, b->ev0, b->ev1, false, hipEventRecordExternal);
+            if (e == hipSuccess) e = launch_match(a, S, b->walk.ev0.e, b->walk.ev1.e, false, hipEventRecordExternal);
             if (e == hipSuccess) e = enqueue_csr(b, S, hipEventRecordExternal);
             return e;
         };
@@ -868,21 +873,22 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     if (!csr) return TM_OK;   // the async slot enqueues its read-back and event
     if (grc == 1 && !csr_done) HIP_OK(enqueue_csr(b, S));   // (a graph holds it)
     b->scan_args = s;
-    if (b->check_tokens) HIP_OK(hipMemcpyAsync(b->h_bad, b->d_nslow, 2 * 4, hipMemcpyDeviceToHost, S));
-    if (checked) HIP_OK(hipMemcpyAsync(R.h_dbg, R.d_dbg, 8 * 4, hipMemcpyDeviceToHost, S));
+    if (b->check_tokens) HIP_OK(hipMemcpyAsync(b->tok.h_bad.p, b->tok.d_nslow.p, 2 * 4, hipMemcpyDeviceToHost, S));
+    if (checked) HIP_OK(hipMemcpyAsync(R.tab.h_dbg.p, R.tab.d_dbg.p, 8 * 4, hipMemcpyDeviceToHost, S));
     if (b->oneshot || b->eager_dense) {
         if ((rc = enqueue_dense_tail(b, S))) return rc;
         b->dense_enq = true;
     }
-    HIP_OK(hipEventRecord(b->ev_end, S));
+    HIP_OK(hipEventRecord(b->walk.ev_end.e, S));
     b->end_recorded = true;
     return TM_OK;
 }
 
 hipError_t tm_engine::enqueue_csr(tm_batch* b, hipStream_t S, unsigned ev_flags) {
     hipError_t e;
-    if ((e = hipEventRecordWithFlags(b->ev2, S, ev_flags)) != hipSuccess) return e;
-    if ((e = hipMemcpyAsync(b->h_hdr, b->d_hdr, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S)) != hipSuccess)
+    if ((e = hipEventRecordWithFlags(b->walk.ev2.e, S, ev_flags)) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(b->walk.h_hdr.p, b->walk.d_hdr.p, tm_batch::HDR_FIXED, hipMemcpyDeviceToHost, S)) !=
+        hipSuccess)
         return e;   // ctrl + stats
     return hipSuccess;
 }
@@ -890,42 +896,42 @@ hipError_t tm_engine::enqueue_csr(tm_batch* b, hipStream_t S, unsigned ev_flags)
 int tm_engine::enqueue_dense_tail(tm_batch* b, hipStream_t S) {
     int rc;
     ScanArgs s = b->scan_args;
-    s.ids = b->d_ids;
-    s.ids_cap = (uint32_t)std::min<size_t>(b->c_ids, 0xFFFFFFF0ull);
+    s.ids = b->dcsr.d_ids.p;
+    s.ids_cap = (uint32_t)std::min<size_t>(b->dcsr.d_ids.cap, 0xFFFFFFF0ull);
     b->dense_cap = s.ids_cap;
     if (!b->oneshot) {   // the dense CSR only (the pipelined tm_match_batch copies it by DMA)
-        HIP_OK(hipEventRecord(b->evc0, S));
-        HIP_OK(launch_scan(s, S, b->d_total));
+        HIP_OK(hipEventRecord(b->dcsr.evc0.e, S));
+        HIP_OK(launch_scan(s, S, b->dcsr.d_total.p));
         HIP_OK(launch_finalize(s, S, false));
-        HIP_OK(hipEventRecord(b->evc1, S));
+        HIP_OK(hipEventRecord(b->dcsr.evc1.e, S));
         return TM_OK;
     }
-    if ((rc = host_reserve_coherent(b->h_xrow, b->c_xrow, ((size_t)b->n + 1) * 4))) return rc;
-    if ((rc = host_reserve_coherent(b->h_xids, b->c_xids, std::max<size_t>(b->c_ids, 1) * 4))) return rc;
+    if ((rc = b->dcsr.h_xrow.reserve(((size_t)b->n + 1) * 4))) return rc;
+    if ((rc = b->dcsr.h_xids.reserve(std::max<size_t>(b->dcsr.d_ids.cap, 1) * 4))) return rc;
     void *d_row = nullptr, *d_ids = nullptr;
-    HIP_OK(hipHostGetDevicePointer(&d_row, b->h_xrow, 0));
-    HIP_OK(hipHostGetDevicePointer(&d_ids, b->h_xids, 0));
-    b->x_cap = std::min<uint64_t>(s.ids_cap, b->c_xids / 4);
-    HIP_OK(hipEventRecord(b->evc0, S));
-    HIP_OK(launch_scan(s, S, b->d_total));
+    HIP_OK(hipHostGetDevicePointer(&d_row, b->dcsr.h_xrow.p, 0));
+    HIP_OK(hipHostGetDevicePointer(&d_ids, b->dcsr.h_xids.p, 0));
+    b->x_cap = std::min<uint64_t>(s.ids_cap, b->dcsr.h_xids.cap / 4);
+    HIP_OK(hipEventRecord(b->dcsr.evc0.e, S));
+    HIP_OK(launch_scan(s, S, b->dcsr.d_total.p));
     HIP_OK(launch_finalize(s, S, false));
-    HIP_OK(hipEventRecord(b->evc1, S));
-    HIP_OK(launch_csr_to_host(b->d_rowoff, b->d_ids, b->n, b->d_total, b->x_cap, static_cast<uint32_t*>(d_row),
-                              static_cast<uint32_t*>(d_ids), S));
+    HIP_OK(hipEventRecord(b->dcsr.evc1.e, S));
+    HIP_OK(launch_csr_to_host(b->dcsr.d_rowoff.p, b->dcsr.d_ids.p, b->n, b->dcsr.d_total.p, b->x_cap,
+                              static_cast<uint32_t*>(d_row), static_cast<uint32_t*>(d_ids), S));
     return TM_OK;
 }
 
 int tm_engine::oneshot_result(tm_batch* b, tm_result* out) {
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(b->h_xrow);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(b->dcsr.h_xrow.p);
     if (!b->oneshot || !b->done || b->total > b->x_cap || row[b->n] != b->total || row[0] != 0) return 1;
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, b->evc0, b->evc1);
+    (void)hipEventElapsedTime(&ms, b->dcsr.evc0.e, b->dcsr.evc1.e);
     b->st.ms_csr = ms;
     b->dense = true;
     out->n_topics = b->n;
     out->n_matches = b->total;
     out->row_offsets = row;
-    out->filter_ids = reinterpret_cast<const uint32_t*>(b->h_xids);
+    out->filter_ids = reinterpret_cast<const uint32_t*>(b->dcsr.h_xids.p);
     return TM_OK;
 }
 
@@ -934,24 +940,24 @@ int tm_engine::ensure_dense(tm_batch* b) {
     if (b->dense) return TM_OK;
     const hipStream_t S = st(b);
     int rc;
-    if (b->total > b->c_ids) {
-        if ((rc = dev_reserve(b->d_ids, b->c_ids, (size_t)b->total + b->total / 4))) return rc;
+    if (b->total > b->dcsr.d_ids.cap) {
+        if ((rc = b->dcsr.d_ids.reserve((size_t)b->total + b->total / 4))) return rc;
     }
-    b->scan_args.ids = b->d_ids;
-    b->scan_args.ids_cap = (uint32_t)std::min<size_t>(b->c_ids, 0xFFFFFFF0ull);
-    HIP_OK(hipEventRecord(b->evc0, S));
-    HIP_OK(launch_scan(b->scan_args, S, b->d_total));
+    b->scan_args.ids = b->dcsr.d_ids.p;
+    b->scan_args.ids_cap = (uint32_t)std::min<size_t>(b->dcsr.d_ids.cap, 0xFFFFFFF0ull);
+    HIP_OK(hipEventRecord(b->dcsr.evc0.e, S));
+    HIP_OK(launch_scan(b->scan_args, S, b->dcsr.d_total.p));
     HIP_OK(launch_finalize(b->scan_args, S, checked));
-    HIP_OK(hipEventRecord(b->evc1, S));
-    HIP_OK(hipMemcpyAsync(b->h_total, b->d_total, 4, hipMemcpyDeviceToHost, S));
+    HIP_OK(hipEventRecord(b->dcsr.evc1.e, S));
+    HIP_OK(hipMemcpyAsync(b->dcsr.h_total.p, b->dcsr.d_total.p, 4, hipMemcpyDeviceToHost, S));
     HIP_OK(hipStreamSynchronize(S));
-    if (b->h_total[0] != b->total) {
-        snprintf(last_error(), 512, "inconsistent CSR: scanned %u entries, kernel count %llu", b->h_total[0],
+    if (b->dcsr.h_total.p[0] != b->total) {
+        snprintf(last_error(), 512, "inconsistent CSR: scanned %u entries, kernel count %llu", b->dcsr.h_total.p[0],
                  (unsigned long long)b->total);
         return TM_EIO;
     }
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, b->evc0, b->evc1);
+    (void)hipEventElapsedTime(&ms, b->dcsr.evc0.e, b->dcsr.evc1.e);
     b->st.ms_csr = ms;
     b->dense = true;
     return TM_OK;
@@ -986,7 +992,7 @@ int tm_engine::grow_for(tm_batch* b, uint32_t err, uint64_t need, uint64_t stage
         const uint64_t limit = std::min<uint64_t>(MAX_RESULT, result_limit + 1024);
         if (!b->one_region && need + need / 4 + 1024 > limit && staged <= result_limit) b->one_region = true;
         if (b->one_region) need = staged;
-        int rc = dev_reserve(b->d_sfids, b->c_sfids, std::min<uint64_t>(need + need / 4 + 1024, limit));
+        int rc = b->walk.d_sfids.reserve(std::min<uint64_t>(need + need / 4 + 1024, limit));
         if (rc) return rc;
     }
     if (err & ERR_SLOW_SCRATCH) {
@@ -998,32 +1004,33 @@ int tm_engine::grow_for(tm_batch* b, uint32_t err, uint64_t need, uint64_t stage
 
 void tm_engine::fill_stats(tm_batch* b) {
     float ms_match = 0, ms_total = 0, ms_tok = 0, ms_dd = 0, ms_x = 0;
-    (void)hipEventElapsedTime(&ms_match, b->ev0, b->ev1);
-    (void)hipEventElapsedTime(&ms_total, b->ev0, b->ev2);
-    if (b->tok_timed) (void)hipEventElapsedTime(&ms_tok, b->evt, b->ev0);
-    if (b->dedup_timed) (void)hipEventElapsedTime(&ms_dd, b->evd, b->tok_timed ? b->evt : b->ev0);
-    if (b->dedup_dev && !b->graphed) (void)hipEventElapsedTime(&ms_x, b->evx0, b->evx1);
+    (void)hipEventElapsedTime(&ms_match, b->walk.ev0.e, b->walk.ev1.e);
+    (void)hipEventElapsedTime(&ms_total, b->walk.ev0.e, b->walk.ev2.e);
+    if (b->tok_timed) (void)hipEventElapsedTime(&ms_tok, b->tok.evt.e, b->walk.ev0.e);
+    if (b->dedup_timed) (void)hipEventElapsedTime(&ms_dd, b->dd.evd.e, b->tok_timed ? b->tok.evt.e : b->walk.ev0.e);
+    if (b->dedup_dev && !b->graphed) (void)hipEventElapsedTime(&ms_x, b->dd.evx0.e, b->dd.evx1.e);
     b->st.ms_tokenize = ms_tok;
     b->st.ms_dedup = ms_dd;
     b->st.ms_expand = ms_x;
     b->st.publishes = b->dedup ? b->n_pub : b->n;
     float ms_q = 0;
-    (void)hipEventElapsedTime(&ms_q, b->evq, b->dedup_timed ? b->evd : b->tok_timed ? b->evt : b->ev0);
+    (void)hipEventElapsedTime(&ms_q, b->walk.evq.e,
+                              b->dedup_timed ? b->dd.evd.e : b->tok_timed ? b->tok.evt.e : b->walk.ev0.e);
     b->st.ms_queue = ms_q;
     b->st.ms_csr = 0;   // set by ensure_dense
     b->st.topics = b->n;
-    b->st.visits = b->h_stats[ST_VISITS];
-    b->st.hash_hits = b->h_stats[ST_HASH];
-    b->st.words = b->h_stats[ST_WORDS];
-    b->st.matches = b->h_stats[ST_MATCHES];
-    b->st.slow_topics = b->h_stats[ST_SLOW];
-    b->st.probes = b->h_stats[ST_PROBES];
-    b->st.iterations = b->h_stats[ST_ITERS];
-    b->st.overflow_tiles = b->h_ctrl[CTRL_NOVF];
+    b->st.visits = b->walk.h_stats[ST_VISITS];
+    b->st.hash_hits = b->walk.h_stats[ST_HASH];
+    b->st.words = b->walk.h_stats[ST_WORDS];
+    b->st.matches = b->walk.h_stats[ST_MATCHES];
+    b->st.slow_topics = b->walk.h_stats[ST_SLOW];
+    b->st.probes = b->walk.h_stats[ST_PROBES];
+    b->st.iterations = b->walk.h_stats[ST_ITERS];
+    b->st.overflow_tiles = b->walk.h_ctrl[CTRL_NOVF];
     b->st.ms_match = ms_match;
     b->st.ms_total = ms_total;
     b->total = b->st.matches;
-    b->st.delivered = b->dedup_dev ? b->h_stats[ST_DELIVERED] : b->st.matches;
+    b->st.delivered = b->dedup_dev ? b->walk.h_stats[ST_DELIVERED] : b->st.matches;
 #if TM_PHASE_CYCLES
     // dev build: the tile walk's cycle sums over all waves, one line per batch
     fprintf(stderr, "tm_phase_cycles prologue=%llu loop=%llu readback=%llu sort=%llu ms_match=%.4f\n",
@@ -1042,19 +1049,19 @@ int tm_engine::wait(tm_batch* b, bool drained, uint32_t* relaunched) {
     }
     for (int attempt = 0;; ++attempt) {
         if (!drained || attempt) {
-            if (b->end_recorded) HIP_OK(hipEventSynchronize(b->ev_end));
+            if (b->end_recorded) HIP_OK(hipEventSynchronize(b->walk.ev_end.e));
             else HIP_OK(hipStreamSynchronize(S));
         }
         if (attempt && relaunched) ++*relaunched;
         if (b->dedup_dev) {   // the walk's rows: the distinct publishes counted by the dedup pass
-            b->n = b->h_ctrl[CTRL_NROWS];
+            b->n = b->walk.h_ctrl[CTRL_NROWS];
             b->scan_args.n = b->n;
         }
-        if (b->check_tokens && b->n && b->h_bad[1]) {
+        if (b->check_tokens && b->n && b->tok.h_bad.p[1]) {
             snprintf(last_error(), 512, "token batch failed the device check (word offsets or flags)");
             return TM_EINVAL;
         }
-        const uint32_t* h_dbg = b->rep->h_dbg;
+        const uint32_t* h_dbg = b->rep->tab.h_dbg.p;
         if (checked && h_dbg[0]) {
             snprintf(last_error(), 512, "bounds check %u failed: index %u bound %u (count %u, extra %u)",
                      h_dbg[0], h_dbg[1], h_dbg[2], h_dbg[3], h_dbg[4]);
@@ -1062,7 +1069,7 @@ int tm_engine::wait(tm_batch* b, bool drained, uint32_t* relaunched) {
         }
         uint32_t err;
         uint64_t need, staged;
-        int rc = check_ctrl(b->h_ctrl, b->h_stats, &err, &need, &staged);
+        int rc = check_ctrl(b->walk.h_ctrl, b->walk.h_stats, &err, &need, &staged);
         if (rc) return rc;
         if (!err) break;
         if (attempt >= 6) {
@@ -1081,7 +1088,7 @@ int tm_engine::wait(tm_batch* b, bool drained, uint32_t* relaunched) {
     b->dense = b->dense_enq && !b->oneshot && b->total <= b->dense_cap;
     if (b->dense) {
         float ms = 0;
-        (void)hipEventElapsedTime(&ms, b->evc0, b->evc1);
+        (void)hipEventElapsedTime(&ms, b->dcsr.evc0.e, b->dcsr.evc1.e);
         b->st.ms_csr = ms;
     }
     return TM_OK;
@@ -1094,25 +1101,25 @@ int tm_engine::result(tm_batch* b, tm_result* out) {
     const hipStream_t S = st(b);
     // the match count is known since wait(): both copies go out behind one sync
     const uint64_t total = b->total;
-    if (total > b->c_ids) {
+    if (total > b->dcsr.d_ids.cap) {
         snprintf(last_error(), 512, "inconsistent CSR: kernel count %llu, capacity %zu",
-                 (unsigned long long)total, b->c_ids);
+                 (unsigned long long)total, b->dcsr.d_ids.cap);
         return TM_EIO;
     }
-    if ((rc = host_reserve(b->h_rowoff, b->ch_rowoff, (size_t)b->n + 1))) return rc;
-    if ((rc = host_reserve(b->h_ids, b->ch_ids, std::max<uint64_t>(total, 1)))) return rc;
-    HIP_OK(hipMemcpyAsync(b->h_rowoff, b->d_rowoff, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, S));
-    if (total) HIP_OK(hipMemcpyAsync(b->h_ids, b->d_ids, total * 4, hipMemcpyDeviceToHost, S));
+    if ((rc = b->dcsr.h_rowoff.reserve((size_t)b->n + 1))) return rc;
+    if ((rc = b->dcsr.h_ids.reserve(std::max<uint64_t>(total, 1)))) return rc;
+    HIP_OK(hipMemcpyAsync(b->dcsr.h_rowoff.p, b->dcsr.d_rowoff.p, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, S));
+    if (total) HIP_OK(hipMemcpyAsync(b->dcsr.h_ids.p, b->dcsr.d_ids.p, total * 4, hipMemcpyDeviceToHost, S));
     HIP_OK(hipStreamSynchronize(S));
-    if (b->h_rowoff[b->n] != total) {
+    if (b->dcsr.h_rowoff.p[b->n] != total) {
         snprintf(last_error(), 512, "inconsistent CSR: row offsets end at %u, kernel count %llu",
-                 b->h_rowoff[b->n], (unsigned long long)total);
+                 b->dcsr.h_rowoff.p[b->n], (unsigned long long)total);
         return TM_EIO;
     }
     out->n_topics = b->n;
     out->n_matches = total;
-    out->row_offsets = b->h_rowoff;
-    out->filter_ids = b->h_ids;
+    out->row_offsets = b->dcsr.h_rowoff.p;
+    out->filter_ids = b->dcsr.h_ids.p;
     return TM_OK;
 }
 
@@ -1136,30 +1143,30 @@ int tm_engine::result_packed(tm_batch* b, tm_result_packed* out) {
     if ((rc = ensure_dense(b))) return rc;
     const hipStream_t S = st(b);
     const uint64_t total = b->total;
-    if (total > b->c_ids) {
+    if (total > b->dcsr.d_ids.cap) {
         snprintf(last_error(), 512, "inconsistent CSR: kernel count %llu, capacity %zu",
-                 (unsigned long long)total, b->c_ids);
+                 (unsigned long long)total, b->dcsr.d_ids.cap);
         return TM_EIO;
     }
-    if ((rc = host_reserve(b->h_rowoff, b->ch_rowoff, (size_t)b->n + 1))) return rc;
-    if ((rc = host_reserve(b->h_ids8, b->ch_ids8, (size_t)total * 3 + 16))) return rc;
-    HIP_OK(hipMemcpyAsync(b->h_rowoff, b->d_rowoff, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, S));
+    if ((rc = b->dcsr.h_rowoff.reserve((size_t)b->n + 1))) return rc;
+    if ((rc = b->dcsr.h_ids8.reserve((size_t)total * 3 + 16))) return rc;
+    HIP_OK(hipMemcpyAsync(b->dcsr.h_rowoff.p, b->dcsr.d_rowoff.p, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, S));
     if (total) {
-        if ((rc = dev_reserve(b->d_pack, b->c_pack, total * 3 + 16))) return rc;
-        HIP_OK(launch_pack_ids(b->d_ids, total, b->d_pack, S));
-        HIP_OK(hipMemcpyAsync(b->h_ids8, b->d_pack, total * 3, hipMemcpyDeviceToHost, S));
+        if ((rc = b->dcsr.d_pack.reserve(total * 3 + 16))) return rc;
+        HIP_OK(launch_pack_ids(b->dcsr.d_ids.p, total, b->dcsr.d_pack.p, S));
+        HIP_OK(hipMemcpyAsync(b->dcsr.h_ids8.p, b->dcsr.d_pack.p, total * 3, hipMemcpyDeviceToHost, S));
     }
     HIP_OK(hipStreamSynchronize(S));
-    if (b->h_rowoff[b->n] != total) {
+    if (b->dcsr.h_rowoff.p[b->n] != total) {
         snprintf(last_error(), 512, "inconsistent CSR: row offsets end at %u, kernel count %llu",
-                 b->h_rowoff[b->n], (unsigned long long)total);
+                 b->dcsr.h_rowoff.p[b->n], (unsigned long long)total);
         return TM_EIO;
     }
     out->n_topics = b->n;
     out->id_bytes = 3;
     out->n_matches = total;
-    out->row_offsets = b->h_rowoff;
-    out->ids = b->h_ids8;
+    out->row_offsets = b->dcsr.h_rowoff.p;
+    out->ids = b->dcsr.h_ids8.p;
     return TM_OK;
 }
 
@@ -1174,15 +1181,15 @@ int tm_engine::sample(tm_batch* b, const uint32_t* rows, uint32_t k, tm_result* 
         int rc;
         // [rows u32 k | cnt u32 k | pad | src u64 k | off u64 k + 1], batch-owned
         const size_t o_src = (((size_t)k * 8) + 15) & ~(size_t)15, o_off = o_src + (size_t)k * 8;
-        if ((rc = dev_reserve(b->d_smp_meta, b->c_smp_meta, o_off + ((size_t)k + 1) * 8))) return rc;
-        uint8_t* m = b->d_smp_meta;
+        if ((rc = b->smp.d_smp_meta.reserve(o_off + ((size_t)k + 1) * 8))) return rc;
+        uint8_t* m = b->smp.d_smp_meta.p;
         uint32_t* d_rows = reinterpret_cast<uint32_t*>(m);
         uint32_t* d_cnt = d_rows + k;
         unsigned long long* d_src = reinterpret_cast<unsigned long long*>(m + o_src);
         uint64_t* d_off = reinterpret_cast<uint64_t*>(m + o_off);
         std::vector<uint32_t> cnt(k);
         HIP_OK(hipMemcpyAsync(d_rows, rows, (size_t)k * 4, hipMemcpyHostToDevice, S));
-        HIP_OK(launch_sample_meta(b->d_count, b->d_src, d_rows, k, d_cnt, d_src, S));
+        HIP_OK(launch_sample_meta(b->walk.d_count, b->walk.d_src, d_rows, k, d_cnt, d_src, S));
         HIP_OK(hipMemcpyAsync(cnt.data(), d_cnt, (size_t)k * 4, hipMemcpyDeviceToHost, S));
         HIP_OK(hipStreamSynchronize(S));
         std::vector<uint64_t> off((size_t)k + 1, 0);
@@ -1191,10 +1198,10 @@ int tm_engine::sample(tm_batch* b, const uint32_t* rows, uint32_t k, tm_result* 
         for (uint32_t i = 0; i <= k; ++i) b->h_smp_off[i] = (uint32_t)off[i];
         b->h_smp_ids.resize(off[k]);
         if (off[k]) {
-            if ((rc = dev_reserve(b->d_smp_ids, b->c_smp_ids, off[k]))) return rc;
+            if ((rc = b->smp.d_smp_ids.reserve(off[k]))) return rc;
             HIP_OK(hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, S));
-            HIP_OK(launch_sample_ids(b->d_sfids, d_cnt, d_src, d_off, k, b->d_smp_ids, S));
-            HIP_OK(hipMemcpyAsync(b->h_smp_ids.data(), b->d_smp_ids, off[k] * 4, hipMemcpyDeviceToHost, S));
+            HIP_OK(launch_sample_ids(b->walk.d_sfids.p, d_cnt, d_src, d_off, k, b->smp.d_smp_ids.p, S));
+            HIP_OK(hipMemcpyAsync(b->h_smp_ids.data(), b->smp.d_smp_ids.p, off[k] * 4, hipMemcpyDeviceToHost, S));
             HIP_OK(hipStreamSynchronize(S));
         }
     }

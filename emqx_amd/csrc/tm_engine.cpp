@@ -109,7 +109,7 @@ int tm_stats(tm_engine* e, tm_engine_stats* o) {
     o->slots = e->slots.size();
     if (!e->reps.empty()) {   // per replica (each device holds the same)
         const Replica& R = *e->reps[0];
-        o->device_bytes = R.d_nslots * sizeof(Slot) + R.c_foff * 8 + R.c_flen * 4 + R.c_fbytes;
+        o->device_bytes = R.d_nslots * sizeof(Slot) + R.tab.d_foff.cap * 8 + R.tab.d_flen.cap * 4 + R.tab.d_fbytes.cap;
     } else {
         o->device_bytes = 0;
     }
@@ -207,7 +207,7 @@ int tm_match_batch_packed(tm_engine* e, const uint8_t* topics, const uint64_t* o
     out->id_bytes = pack;
     out->n_matches = r.n_matches;
     out->row_offsets = r.row_offsets;
-    out->ids = pack == 3 ? R.h_pids8 : reinterpret_cast<const uint8_t*>(r.filter_ids);
+    out->ids = pack == 3 ? R.pl.h_pids8.p : reinterpret_cast<const uint8_t*>(r.filter_ids);
     return TM_OK;
 }
 
@@ -466,7 +466,7 @@ int tm_batch_row_map(tm_engine* e, tm_batch* b, const uint32_t** row_of, uint32_
             b->row_of.resize(b->n_pub);
             if (b->n_pub) {
                 HIP_OK(launch_dedup_rowof(e->dedup_args(b), e->st(b)));
-                HIP_OK(hipMemcpyAsync(b->row_of.data(), b->d_rowof, (size_t)b->n_pub * 4, hipMemcpyDeviceToHost,
+                HIP_OK(hipMemcpyAsync(b->row_of.data(), b->dd.d_rowof.p, (size_t)b->n_pub * 4, hipMemcpyDeviceToHost,
                                       e->st(b)));
                 HIP_OK(hipStreamSynchronize(e->st(b)));
             }
@@ -510,7 +510,7 @@ int tm_batch_wait(tm_engine* e, tm_batch* b) {
     // (in wait()).  wait() then finds the work done: its own sync is a check.
     if (b->launched && !b->done && (b->end_recorded || b->own)) {
         HIP_OK(hipSetDevice(b->rep->device));
-        if (b->end_recorded) HIP_OK(hipEventSynchronize(b->ev_end));
+        if (b->end_recorded) HIP_OK(hipEventSynchronize(b->walk.ev_end.e));
         else HIP_OK(hipStreamSynchronize(b->own));
     }
     std::lock_guard<std::recursive_mutex> g(e->mu);
@@ -568,8 +568,8 @@ int tm_batch_device_csr(tm_engine* e, tm_batch* b, const uint32_t** d_row, const
         if (rc) return rc;
         if ((rc = e->ensure_dense(b))) return rc;
     }
-    if (d_row) *d_row = b->d_rowoff;
-    if (d_ids) *d_ids = b->d_ids;
+    if (d_row) *d_row = b->dcsr.d_rowoff.p;
+    if (d_ids) *d_ids = b->dcsr.d_ids.p;
     if (n) *n = b->total;
     return TM_OK;
 }
@@ -577,9 +577,9 @@ int tm_batch_device_csr(tm_engine* e, tm_batch* b, const uint32_t** d_row, const
 int tm_batch_rows(tm_engine* e, tm_batch* b, const uint32_t** d_count, const uint64_t** d_start,
                   const uint32_t** d_ids, uint64_t* n_matches) {
     if (!e || !b || !b->done || !b->csr) return TM_EINVAL;
-    if (d_count) *d_count = b->d_count;
-    if (d_start) *d_start = reinterpret_cast<const uint64_t*>(b->d_src);
-    if (d_ids) *d_ids = b->d_sfids;
+    if (d_count) *d_count = b->walk.d_count;
+    if (d_start) *d_start = reinterpret_cast<const uint64_t*>(b->walk.d_src);
+    if (d_ids) *d_ids = b->walk.d_sfids.p;
     if (n_matches) *n_matches = b->total;
     return TM_OK;
 }
@@ -588,9 +588,9 @@ int tm_batch_publish_rows(tm_engine* e, tm_batch* b, const uint32_t** d_count, c
                           const uint32_t** d_ids, uint64_t* n_delivered) {
     if (!e || !b || !b->done || !b->csr) return TM_EINVAL;
     if (b->dedup && !b->dedup_dev) return TM_EINVAL;   // host-deduplicated: rows per distinct topic only
-    if (d_count) *d_count = b->dedup_dev ? b->d_pcount : b->d_count;
-    if (d_start) *d_start = reinterpret_cast<const uint64_t*>(b->dedup_dev ? b->d_psrc : b->d_src);
-    if (d_ids) *d_ids = b->d_sfids;
+    if (d_count) *d_count = b->dedup_dev ? b->dd.d_pcount.p : b->walk.d_count;
+    if (d_start) *d_start = reinterpret_cast<const uint64_t*>(b->dedup_dev ? b->dd.d_psrc.p : b->walk.d_src);
+    if (d_ids) *d_ids = b->walk.d_sfids.p;
     if (n_delivered) *n_delivered = b->st.delivered;
     return TM_OK;
 }

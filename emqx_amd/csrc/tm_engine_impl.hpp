@@ -52,6 +52,7 @@
 
 #include "../../include/emqx_tm.h"
 #include "tm_internal.hpp"
+#include "tm_buffers.hpp"
 
 using namespace etm;
 
@@ -267,49 +268,6 @@ inline uint32_t word_class(const TWord& w, bool& irregular) {
     return C_ABOVE;
 }
 
-template <class T>
-void dev_free(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-template <class T>
-int dev_reserve(T*& p, size_t& cap, size_t n, bool keep = false, size_t keep_n = 0) {
-    if (n <= cap && p) return TM_OK;
-    size_t nc = std::max<size_t>(n + n / 4, 1024);
-    T* np = nullptr;
-    HIP_OK(hipMalloc((void**)&np, nc * sizeof(T)));
-    if (keep && p && keep_n) HIP_OK(hipMemcpy(np, p, keep_n * sizeof(T), hipMemcpyDeviceToDevice));
-    dev_free(p);
-    p = np;
-    cap = nc;
-    return TM_OK;
-}
-
-template <class T>
-int host_reserve(T*& p, size_t& cap, size_t n) {
-    if (n <= cap && p) return TM_OK;
-    size_t nc = std::max<size_t>(n + n / 4, 1024);
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    HIP_OK(hipHostMalloc((void**)&p, nc * sizeof(T), hipHostMallocDefault));
-    cap = nc;
-    return TM_OK;
-}
-
-// pinned host memory the device writes directly (tm_export_host): coherent,
-// so a kernel's stores are visible to the host once its completion is
-inline int host_reserve_coherent(uint8_t*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap && p) return TM_OK;
-    const size_t nc = std::max<size_t>(bytes + bytes / 4, 4096);
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_OK(hipHostMalloc((void**)&p, nc, hipHostMallocCoherent | hipHostMallocMapped));
-    cap = nc;
-    return TM_OK;
-}
-
 // Allocator of the host mirror's big random-access tables (edge hash, node
 // records): blocks of 4 MB and more are mapped 2-MB aligned with
 // MADV_HUGEPAGE before first touch, so a churn delta's random lines do not
@@ -433,43 +391,144 @@ struct tm_batch {
     uint32_t n_pub = 0;
     std::vector<uint32_t> row_of;
     std::vector<uint8_t> h_tflags;
-    // device inputs
-    uint32_t *d_words = nullptr, *d_toff = nullptr, *d_slow = nullptr;
-    uint8_t* d_tflags = nullptr;
-    size_t c_words = 0, c_toff = 0, c_slow = 0, c_tflags = 0;
-    // device outputs
-    uint32_t *d_sfids = nullptr, *d_rowoff = nullptr, *d_ids = nullptr;
-    unsigned long long* d_rows = nullptr;
-    unsigned long long* d_wstats = nullptr;   // the walk waves' partial stats
-    size_t c_wstats = 0;
-    uint8_t* d_pack = nullptr;                // the dense ids packed 3 bytes each (tm_match_batch_packed)
-    size_t c_pack = 0;
-    uint32_t *d_bsums = nullptr, *d_ovf = nullptr, *d_total = nullptr;
-    size_t c_sfids = 0, c_rows = 0, c_rowoff = 0, c_ids = 0, c_bsums = 0, c_ovf = 0;
-    uint32_t* h_total = nullptr;
-    size_t ch_total = 0;
-    size_t c_total = 0;
-    // Per-topic outputs in ONE block, [ctrl CTRL_WORDS u32 | stats ST_N u64 |
-    // src cap u64 | count cap u32], mirrored in pinned memory: the async path
-    // reads a whole batch's control words and row descriptors back in one copy.
-    uint8_t *d_hdr = nullptr, *h_hdr = nullptr;
-    size_t hdr_cap = 0;   // topics the block holds
-    uint32_t *d_count = nullptr, *d_ctrl = nullptr, *h_ctrl = nullptr, *h_count = nullptr;
-    unsigned long long *d_src = nullptr, *d_stats = nullptr, *h_src = nullptr, *h_stats = nullptr;
+    // The batch's device memory, pinned memory and events, by feature.  Each
+    // group is a value: release() gives a group back by assigning it a fresh
+    // one.  Everything lives on the replica's device (rep).
+
+    // per-entry counts scanned into per-row totals (tm_batch_routes,
+    // tm_batch_dispatch_shared): counts, their exclusive scan, the scan's
+    // block sums, the rows' offsets and the grand total
+    struct EntryScan {
+        DevBuf<uint32_t> count, eoff, bsums, row, total;
+        // sized for m match entries of nn rows; sa: the arguments of the scan over them
+        int reserve(uint32_t m, size_t nn, ScanArgs& sa) {
+            int rc;
+            if ((rc = count.reserve((size_t)m + 1))) return rc;
+            if ((rc = eoff.reserve((size_t)m + 1))) return rc;
+            if ((rc = row.reserve(nn + 1))) return rc;
+            if ((rc = bsums.reserve((size_t)scan_block_count(m) + 1))) return rc;
+            if ((rc = total.reserve(1))) return rc;
+            sa = ScanArgs{};
+            sa.count = count.p;
+            sa.row_off = eoff.p;
+            sa.block_sums = bsums.p;
+            sa.n = m;
+            return TM_OK;
+        }
+    };
+
+    // tokens and the tokeniser's input
+    struct Tokens {
+        DevBuf<uint32_t> d_words, d_toff, d_slow;
+        DevBuf<uint8_t> d_tflags;
+        // device tokenisation: the topic bytes are uploaded by prepare and
+        // tokenised on the engine stream by the first launch
+        DevBuf<uint8_t> d_bytes;
+        DevBuf<uint64_t> d_boffs;
+        // the tokeniser's inputs: d_bytes / d_boffs, or both inside d_in when the
+        // batch came as one packed [offs | bytes] block (async slots: one H2D)
+        DevBuf<uint8_t> d_in;
+        const uint8_t* in_bytes = nullptr;    // views into d_bytes / d_boffs, d_in or
+        const uint64_t* in_offs = nullptr;    //  (bounded batches) the slot's h_bin
+        DevBuf<uint32_t> d_wcount, d_nslow;
+        PinBuf<uint32_t> h_bad;
+        Event evt;   // before the device tokeniser (fresh launches)
+    } tok;
+
+    // the walk's output and the per-topic header
+    struct Walk {
+        DevBuf<uint32_t> d_sfids;
+        DevBuf<unsigned long long> d_rows;
+        DevBuf<unsigned long long> d_wstats;   // the walk waves' partial stats
+        // Per-topic outputs in ONE block, [ctrl CTRL_WORDS u32 | stats ST_N u64 |
+        // src cap u64 | count cap u32], mirrored in pinned memory: the async path
+        // reads a whole batch's control words and row descriptors back in one copy.
+        DevBuf<uint8_t> d_hdr;
+        PinBuf<uint8_t> h_hdr;
+        size_t hdr_cap = 0;   // topics the block holds
+        // views into d_hdr / h_hdr (ensure_hdr sets them)
+        uint32_t *d_count = nullptr, *d_ctrl = nullptr, *h_ctrl = nullptr, *h_count = nullptr;
+        unsigned long long *d_src = nullptr, *d_stats = nullptr, *h_src = nullptr, *h_stats = nullptr;
+        Event ev_read;   // own-stream batches: marks their walk for the replica's next upload
+        Event ev0, ev1, ev2;
+        // after the launch's last read-back: wait() syncs on it, not on the stream,
+        // so work queued behind the batch (a trie delta upload) does not hold it
+        Event ev_end;
+        Event evq;   // at the launch call: evq..ev0 (or evt) is the queueing ahead of it
+    } walk;
+
+    // generic-path scratch, per batch (batches on different streams run concurrently)
+    struct Generic {
+        DevBuf<uint32_t> d_sqpar, d_sqpw, d_sqmeta, d_sofid;
+        DevBuf<unsigned long long> d_sqkey, d_sokey;
+    } gen;
+
+    // the dense CSR and its packed and host forms
+    struct Dense {
+        DevBuf<uint32_t> d_rowoff, d_ids, d_bsums, d_ovf, d_total;
+        PinBuf<uint32_t> h_total;
+        DevBuf<uint8_t> d_pack;            // the dense ids packed 3 bytes each (tm_match_batch_packed)
+        PinBuf<uint32_t> h_rowoff, h_ids;  // pinned host results
+        PinBuf<uint8_t> h_ids8;            // the ids 3 bytes each (tm_batch_result_packed)
+        CoherentBuf h_xrow, h_xids;        // the one-shot copy's target (byte sizes)
+        Event evc0, evc1;                  // around the dense-CSR pass (ensure_dense)
+    } dcsr;
+
+    // tm_batch_sample's device scratch, kept (a hipFree per call would
+    // synchronise the device under the other streams)
+    struct Sample {
+        DevBuf<uint8_t> d_smp_meta;
+        DevBuf<uint32_t> d_smp_ids;
+    } smp;
+
+    // TM_BATCH_DEDUP on the device (device-tokenised batches, etm::DedupArgs)
+    struct Dedup {
+        DevBuf<unsigned long long> d_dtab, d_psrc, d_dbits, d_dbsum;
+        DevBuf<uint32_t> d_dslot, d_dbc, d_dbb, d_drbs, d_dbbs, d_dsrow, d_drrep, d_rowof, d_dd, d_pcount;
+        DevBuf<uint4> d_dsmeta;
+        DevBuf<uint8_t> d_cbytes;
+        DevBuf<uint64_t> d_coffs;
+        Event evd, evx0, evx1;   // before the dedup pass; around the expand
+    } dd;
+
+    // route resolution (tm_batch_routes)
+    struct Routes {
+        EntryScan es;   // over match entries
+        DevBuf<uint32_t> d_rfid, d_rdest;
+        PinBuf<uint32_t> h_rtotal, h_rrow, h_rfid, h_rdest;
+    } rt;
+
+    // subscriber fan-out (tm_batch_dispatch)
+    struct Fanout {
+        DevBuf<uint64_t> d_moff, d_fbsums, d_ftotal, d_drow, d_ftile;
+        DevBuf<uint32_t> d_moff32;
+        DevBuf<uint8_t> d_fbig;
+        DevBuf<uint32_t> d_dcount;   // TM_DISPATCH_ROWS: deliveries of each row
+        DevBuf<uint64_t> d_fmeta;    // TM_DISPATCH_ROWS: staging regions (vb, rtop)
+        PinBuf<uint64_t> h_fmeta;
+        PinBuf<uint64_t> h_ftotal, h_drow, h_moff;
+        DevBuf<uint32_t> d_fout;
+        PinBuf<uint32_t> h_fout;
+        Event fev0, fev1;
+    } fan;
+
+    // shared-subscription dispatch (tm_batch_dispatch_shared)
+    struct Shared {
+        EntryScan es;
+        DevBuf<uint32_t> d_gkeys, d_gfid, d_ggrp, d_gsub;
+        DevBuf<unsigned long long> d_gtot64;
+        PinBuf<unsigned long long> h_gtot64;
+        PinBuf<uint32_t> h_gkeys, h_grow, h_gfid, h_ggrp, h_gsub;
+        Event gev[4];   // around count + scan + rows, around the pick
+    } sh;
+
     static constexpr size_t HDR_FIXED = ((size_t)XG_WORD + TICKET_GROUPS * TICKET_STRIDE) * 4;
     static size_t hdr_bytes(size_t n) { return HDR_FIXED + n * 12; }
-    // pinned host results
-    uint32_t* h_rowoff = nullptr;
-    uint32_t* h_ids = nullptr;
-    size_t ch_rowoff = 0, ch_ids = 0;
-    uint8_t* h_ids8 = nullptr;                // the ids 3 bytes each (tm_batch_result_packed)
-    size_t ch_ids8 = 0;
     // the replica (device copy of the trie) the batch runs on; fixed for the
     // batch's life: its buffers live on that replica's device
     struct Replica* rep = nullptr;
     // the stream the batch runs on: async slots own one, other batches use the replica's
     hipStream_t own = nullptr;
-    hipEvent_t ev_read = nullptr;   // own-stream batches: marks their walk for the replica's next upload
     // the batch's own captured launch (tm_engine::graph_ready): a repeated
     // tokenised batch's header clear, walk, generic path and read-back of the
     // control words, or a fresh deduplicated batch's whole sequence, replayed
@@ -484,20 +543,10 @@ struct tm_batch {
     // graph of the slot's (SlotTail): tokeniser, walk, generic path and the
     // slot's export.
     bool bounded = false;
-    uint32_t* d_nb = nullptr;
+    uint32_t* d_nb = nullptr;   // (in the slot's h_bin)
     bool own_user = false;   // TM_BATCH_STREAM: a caller's batch on a stream of its own (async slots: false)
-    // generic-path scratch, per batch (batches on different streams run concurrently)
-    uint32_t s_waves = 0, s_qcap = 1u << 13, s_ocap = 1u << 14;
-    uint32_t *d_sqpar = nullptr, *d_sqpw = nullptr, *d_sqmeta = nullptr, *d_sofid = nullptr;
-    unsigned long long *d_sqkey = nullptr, *d_sokey = nullptr;
-    size_t c_sq = 0, c_so = 0, c_sq2 = 0, c_sq3 = 0, c_so2 = 0, c_sq4 = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    hipEvent_t evt = nullptr;   // before the device tokeniser (fresh launches)
-    hipEvent_t evc0 = nullptr, evc1 = nullptr;   // around the dense-CSR pass (ensure_dense)
-    // after the launch's last read-back: wait() syncs on it, not on the stream,
-    // so work queued behind the batch (a trie delta upload) does not hold it
-    hipEvent_t ev_end = nullptr;
-    bool end_recorded = false;
+    uint32_t s_waves = 0, s_qcap = 1u << 13, s_ocap = 1u << 14;   // the generic path's sizes
+    bool end_recorded = false;      // walk.ev_end
     // one-shot launch (tm_match_batch): the dense CSR is built and copied into
     // mapped host memory behind the walk, so the batch costs one host wait
     bool oneshot = false;
@@ -505,41 +554,19 @@ struct tm_batch {
     uint64_t dense_cap = 0;         // ids the enqueued finalize could hold
     bool dense_enq = false;         // the LAST launch enqueued scan + finalize (set by launch, read by wait)
     std::vector<uint32_t> h_smp_off, h_smp_ids;   // tm_batch_sample's last result (host CSR)
-    uint8_t* d_smp_meta = nullptr;   // tm_batch_sample's device scratch, kept (a hipFree per call
-    uint32_t* d_smp_ids = nullptr;   //  would synchronise the device under the other streams)
-    size_t c_smp_meta = 0, c_smp_ids = 0;
-    // TM_BATCH_DEDUP on the device (device-tokenised batches, etm::DedupArgs):
-    // the n_pub publishes are deduplicated by their bytes, and only the rows
-    // (distinct topics) are tokenised and walked; n becomes the row count once
-    // a launch has been waited
+    // device dedup: the n_pub publishes are deduplicated by their bytes, and
+    // only the rows (distinct topics) are tokenised and walked; n becomes the
+    // row count once a launch has been waited
     bool dedup_dev = false;
     bool dedup_stale = false;       // fresh bytes (prepare / retokenize): the next launch deduplicates
     bool dedup_timed = false;       // the last launch deduplicated: evd.. is its time
     bool rowof_host = false;        // row_of holds the device map of the last dedup pass
-    unsigned long long *d_dtab = nullptr, *d_psrc = nullptr, *d_dbits = nullptr;
-    uint32_t *d_dslot = nullptr, *d_dbc = nullptr, *d_dbb = nullptr, *d_drbs = nullptr, *d_dbbs = nullptr;
-    uint32_t *d_dsrow = nullptr, *d_drrep = nullptr;
-    uint4* d_dsmeta = nullptr;
-    size_t c_dsmeta = 0;
-    unsigned long long* d_dbsum = nullptr;
-    size_t c_dbsum = 0;
-    uint32_t *d_rowof = nullptr, *d_dd = nullptr, *d_pcount = nullptr;
-    uint8_t* d_cbytes = nullptr;
-    uint64_t* d_coffs = nullptr;
-    size_t c_drrep = 0;
-    size_t c_dtab = 0, c_psrc = 0, c_dsrow = 0, c_dbits = 0, c_dslot = 0, c_dbc = 0, c_dbb = 0, c_drbs = 0,
-           c_dbbs = 0, c_rowof = 0;
-    size_t c_dd = 0, c_pcount = 0, c_cbytes = 0, c_coffs = 0;
     uint64_t dtab_mask = 0, dd_bytes = 0;
     // the table is zero between passes (the expansion clears the claimed
     // slots); dirty: a pass was enqueued and its expansion not yet waited
     // for, or the table is new -- the next pass clears it first
     bool dtab_dirty = true;
-    hipEvent_t evd = nullptr, evx0 = nullptr, evx1 = nullptr;   // before the dedup pass; around the expand
     uint64_t x_cap = 0;             // ids the last one-shot copy could hold
-    uint8_t *h_xrow = nullptr, *h_xids = nullptr;
-    size_t c_xrow = 0, c_xids = 0;
-    hipEvent_t evq = nullptr;   // at the launch call: evq..ev0 (or evt) is the queueing ahead of it
     // the waited result is the walk's own: row i = sfids[src[i] .. + count[i]);
     // dense = the CSR (row_off, ids) has been built from it since the last launch
     bool dense = false;
@@ -562,143 +589,27 @@ struct tm_batch {
     // written by the group's copies, checked on the device by every launch
     // (tm_token_check) and the verdict read back with the header
     bool check_tokens = false;
-    // device tokenisation: the topic bytes are uploaded by prepare and tokenised
-    // on the engine stream by the first launch, after the dictionary deltas; a
-    // later launch re-tokenises only if the dictionary grew meanwhile (ids of
-    // existing words never change), like the host path's re-tokenise
+    // device tokenisation: a later launch re-tokenises only if the dictionary
+    // grew meanwhile (ids of existing words never change), like the host
+    // path's re-tokenise
     bool dev_tok = false;
     uint64_t tok_dict = ~0ull;   // dict.size() the device tokens were made with
-    uint8_t* d_bytes = nullptr;
-    uint64_t* d_boffs = nullptr;
-    // the tokeniser's inputs: d_bytes / d_boffs, or both inside d_in when the
-    // batch came as one packed [offs | bytes] block (async slots: one H2D)
-    uint8_t* d_in = nullptr;
-    size_t c_in = 0;
-    const uint8_t* in_bytes = nullptr;
-    const uint64_t* in_offs = nullptr;
     uint64_t seen_upload = 0;   // own-stream batches: the last trie upload this batch's stream waited for
-    uint32_t* d_wcount = nullptr;
-    size_t c_bytes = 0, c_boffs = 0, c_wcount = 0;
     uint64_t tok_base = 0;
-    uint32_t *d_nslow = nullptr, *h_bad = nullptr;
-    size_t c_nslow = 0, ch_bad = 0;
-    // route resolution (tm_batch_routes)
-    uint32_t *d_rcount = nullptr, *d_rrow = nullptr, *d_rbsums = nullptr, *d_rfid = nullptr, *d_rdest = nullptr;
-    uint32_t* d_reoff = nullptr;   // route scan over match entries
-    size_t c_reoff = 0;
-    uint32_t *d_rtotal = nullptr, *h_rtotal = nullptr, *h_rrow = nullptr, *h_rfid = nullptr, *h_rdest = nullptr;
-    size_t c_rcount = 0, c_rrow = 0, c_rbsums = 0, c_rfid = 0, c_rdest = 0, c_rtotal = 0;
-    size_t ch_rtotal = 0, ch_rrow = 0, ch_rfid = 0, ch_rdest = 0;
-    // subscriber fan-out (tm_batch_dispatch)
-    uint64_t *d_moff = nullptr, *d_fbsums = nullptr, *d_ftotal = nullptr, *d_drow = nullptr, *d_ftile = nullptr;
-    uint32_t* d_moff32 = nullptr;
-    uint8_t* d_fbig = nullptr;
-    size_t c_moff32 = 0, c_fbig = 0;
-    uint32_t* d_dcount = nullptr;   // TM_DISPATCH_ROWS: deliveries of each row
-    size_t c_dcount = 0;
-    uint64_t *d_fmeta = nullptr, *h_fmeta = nullptr;   // TM_DISPATCH_ROWS: staging regions (vb, rtop)
-    size_t c_fmeta = 0, ch_fmeta = 0;
-    uint64_t *h_ftotal = nullptr, *h_drow = nullptr, *h_moff = nullptr;
-    uint32_t *d_fout = nullptr, *h_fout = nullptr;
-    size_t c_moff = 0, c_fbsums = 0, c_ftotal = 0, c_drow = 0, c_fout = 0, c_ftile = 0;
-    size_t ch_ftotal = 0, ch_drow = 0, ch_moff = 0, ch_fout = 0;
-    hipEvent_t fev0 = nullptr, fev1 = nullptr;
-    // shared-subscription dispatch (tm_batch_dispatch_shared)
-    uint32_t *d_gcount = nullptr, *d_geoff = nullptr, *d_gbsums = nullptr, *d_grow = nullptr, *d_gtotal = nullptr;
-    uint32_t *d_gkeys = nullptr, *d_gfid = nullptr, *d_ggrp = nullptr, *d_gsub = nullptr;
-    unsigned long long *d_gtot64 = nullptr, *h_gtot64 = nullptr;
-    uint32_t *h_gkeys = nullptr, *h_grow = nullptr, *h_gfid = nullptr, *h_ggrp = nullptr, *h_gsub = nullptr;
-    size_t c_gcount = 0, c_geoff = 0, c_gbsums = 0, c_grow = 0, c_gtotal = 0, c_gkeys = 0, c_gfid = 0, c_ggrp = 0;
-    size_t c_gsub = 0, c_gtot64 = 0, ch_gtot64 = 0, ch_gkeys = 0, ch_grow = 0, ch_gfid = 0, ch_ggrp = 0, ch_gsub = 0;
-    hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};   // around count + scan + rows, around the pick
 
+    // Gives back every buffer and event.  The caller has made the replica's
+    // device current and synchronised the batch's stream.
     void release() {
-        dev_free(d_gcount); dev_free(d_geoff); dev_free(d_gbsums); dev_free(d_grow); dev_free(d_gtotal);
-        dev_free(d_gkeys); dev_free(d_gfid); dev_free(d_ggrp); dev_free(d_gsub); dev_free(d_gtot64);
-        for (uint32_t** h : {&h_gkeys, &h_grow, &h_gfid, &h_ggrp, &h_gsub}) {
-            if (*h) (void)hipHostFree(*h);
-            *h = nullptr;
-        }
-        if (h_gtot64) (void)hipHostFree(h_gtot64);
-        h_gtot64 = nullptr;
-        for (hipEvent_t& ev : gev) {
-            if (ev) (void)hipEventDestroy(ev);
-            ev = nullptr;
-        }
-        dev_free(d_moff); dev_free(d_moff32); dev_free(d_fbig); dev_free(d_dcount); dev_free(d_fmeta);
-        if (h_fmeta) (void)hipHostFree(h_fmeta);
-        h_fmeta = nullptr; dev_free(d_fbsums); dev_free(d_ftotal); dev_free(d_drow); dev_free(d_fout);
-        dev_free(d_ftile);
-        for (uint64_t** h : {&h_ftotal, &h_drow, &h_moff}) {
-            if (*h) (void)hipHostFree(*h);
-            *h = nullptr;
-        }
-        if (h_fout) (void)hipHostFree(h_fout);
-        h_fout = nullptr;
-        if (fev0) (void)hipEventDestroy(fev0);
-        if (fev1) (void)hipEventDestroy(fev1);
-        fev0 = fev1 = nullptr;
-        dev_free(d_reoff);
-        dev_free(d_rcount); dev_free(d_rrow); dev_free(d_rbsums); dev_free(d_rfid); dev_free(d_rdest); dev_free(d_rtotal);
-        for (uint32_t** h : {&h_rtotal, &h_rrow, &h_rfid, &h_rdest}) {
-            if (*h) (void)hipHostFree(*h);
-            *h = nullptr;
-        }
-        dev_free(d_nslow);
-        dev_free(d_drrep); dev_free(d_dbsum); dev_free(d_dsmeta);
-        c_drrep = c_dbsum = c_dsmeta = 0;
-        dev_free(d_dtab); dev_free(d_psrc); dev_free(d_dsrow); dev_free(d_dbits); dev_free(d_dslot); dev_free(d_dbc);
-        dev_free(d_dbb); dev_free(d_drbs); dev_free(d_dbbs); dev_free(d_rowof); dev_free(d_dd); dev_free(d_pcount);
-        dev_free(d_cbytes); dev_free(d_coffs);
+        tok = {};
+        walk = {};
+        gen = {};
+        dcsr = {};
+        smp = {};
+        dd = {};
+        rt = {};
+        fan = {};
+        sh = {};
         dtab_dirty = true;
-        dev_free(d_smp_meta); dev_free(d_smp_ids);
-        c_smp_meta = c_smp_ids = 0;
-        c_dtab = c_psrc = c_dsrow = c_dbits = c_dslot = c_dbc = c_dbb = c_drbs = c_dbbs = c_rowof = 0;
-        c_dd = c_pcount = c_cbytes = c_coffs = 0;
-        for (hipEvent_t* ev : {&evd, &evx0, &evx1}) {
-            if (*ev) (void)hipEventDestroy(*ev);
-            *ev = nullptr;
-        }
-        dev_free(d_bytes); dev_free(d_boffs); dev_free(d_wcount); dev_free(d_in);
-        in_bytes = nullptr;
-        in_offs = nullptr;
-        if (h_bad) (void)hipHostFree(h_bad);
-        h_bad = nullptr;
-        dev_free(d_words); dev_free(d_toff); dev_free(d_slow); dev_free(d_tflags);
-        dev_free(d_sfids); dev_free(d_rows); dev_free(d_rowoff); dev_free(d_ids);
-        dev_free(d_wstats); dev_free(d_pack);
-        c_wstats = c_pack = 0;
-        if (h_total) (void)hipHostFree(h_total);
-        h_total = nullptr;
-        dev_free(d_bsums); dev_free(d_ovf); dev_free(d_total);
-        dev_free(d_hdr);
-        if (h_hdr) (void)hipHostFree(h_hdr);
-        h_hdr = nullptr;
-        hdr_cap = 0;
-        d_count = d_ctrl = h_ctrl = h_count = nullptr;
-        d_src = d_stats = h_src = h_stats = nullptr;
-        dev_free(d_sqpar); dev_free(d_sqpw); dev_free(d_sqmeta); dev_free(d_sqkey); dev_free(d_sofid); dev_free(d_sokey);
-        c_sq = c_so = c_sq2 = c_sq3 = c_so2 = c_sq4 = 0;
-        if (h_rowoff) (void)hipHostFree(h_rowoff);
-        if (h_ids) (void)hipHostFree(h_ids);
-        h_rowoff = h_ids = nullptr;
-        if (h_ids8) (void)hipHostFree(h_ids8);
-        h_ids8 = nullptr;
-        ch_ids8 = 0;
-        if (h_xrow) (void)hipHostFree(h_xrow);
-        if (h_xids) (void)hipHostFree(h_xids);
-        h_xrow = h_xids = nullptr;
-        c_xrow = c_xids = 0;
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (ev2) (void)hipEventDestroy(ev2);
-        if (evt) (void)hipEventDestroy(evt);
-        if (ev_read) (void)hipEventDestroy(ev_read);
-        if (evc0) (void)hipEventDestroy(evc0);
-        if (evc1) (void)hipEventDestroy(evc1);
-        if (ev_end) (void)hipEventDestroy(ev_end);
-        if (evq) (void)hipEventDestroy(evq);
-        ev0 = ev1 = ev2 = evt = ev_read = evc0 = evc1 = ev_end = evq = nullptr;
         end_recorded = false;
         graph.reset();
     }
@@ -720,11 +631,9 @@ struct AsyncSlot {
     std::vector<uint8_t> bytes;          // the calls' topics, concatenated
     std::vector<uint64_t> offs;
     std::vector<AsyncCall> calls;
-    uint8_t* h_in = nullptr;             // pinned [offs (n+1) u64 | bytes] (H2D source)
-    size_t c_in = 0;
+    PinBuf<uint8_t> h_in;                // pinned [offs (n+1) u64 | bytes] (H2D source)
     // the bounded batch's input, mapped and coherent: [n | pad | offs (bound + 1) u64 | bytes]
-    uint8_t* h_bin = nullptr;
-    size_t c_bin = 0;
+    CoherentBuf h_bin;
     uint32_t bound = 0;                  // topics the bounded batch is sized for (0: not set up)
     uint64_t bytes_cap = 0;
     // the bounded batch's captured graphs, one per size class (a batch of n
@@ -734,16 +643,15 @@ struct AsyncSlot {
     static constexpr uint32_t NCLASS = 4;
     GraphCache gc[NCLASS];
     // written by tm_export_host: [ctrl | stats | src n u64 | count n u32] and the rows
-    uint8_t* h_out = nullptr;
-    size_t c_out = 0;
-    uint32_t* h_rows = nullptr;
-    size_t c_rows = 0;
-    hipEvent_t ev_done = nullptr;
+    CoherentBuf h_out;
+    CoherentBuf h_rows;                  // (u32 ids; sized in bytes)
+    const uint32_t* rows() const { return reinterpret_cast<const uint32_t*>(h_rows.p); }
+    Event ev_done;
     // polled completion (TM_ASYNC_SPIN_US): the stream writes seq into this
     // pinned word after the export, the completer spins on it before it
     // falls back to the event
-    uint32_t* h_flag = nullptr;
-    uint32_t* d_flag = nullptr;
+    CoherentBuf h_flag;
+    uint32_t* d_flag = nullptr;          // h_flag's device address
     uint32_t seq = 0;
     int rc = TM_OK;                      // launch failure (delivered to every call)
     bool claimed = false;                // a completer waits for it / it is being delivered
@@ -785,8 +693,6 @@ struct Replica {
     uint32_t index = 0;
     int device = -1;
     hipStream_t stream = nullptr;
-    hipEvent_t ev_delta = nullptr;       // end of the last async delta upload (staging reusable after it)
-    hipEvent_t ev_sync = nullptr;        // end of the delta uploads, waited for by own-stream batches
     bool delta_inflight = false;
     uint64_t upload_seq = 0;             // async trie uploads recorded on ev_sync
     // batches on streams of their own (async slots, TM_BATCH_STREAM) read the
@@ -800,70 +706,64 @@ struct Replica {
     tm_batch pipe[2];
     bool pipe_ready = false;
     hipStream_t pipe_copy = nullptr;                      // the results' copies to the host
-    hipEvent_t pipe_h2d[2] = {nullptr, nullptr};          // staging k uploaded
-    hipEvent_t pipe_cp[2] = {nullptr, nullptr};           // pipe[k]'s last result copied out
-    hipEvent_t pipe_pk[2] = {nullptr, nullptr};           // pipe[k]'s ids packed (tm_match_batch_packed)
-    uint8_t* h_stage[2] = {nullptr, nullptr};             // pinned packed chunk (offsets | bytes)
-    size_t ch_stage[2] = {0, 0};
-    uint32_t *h_prow = nullptr, *h_pids = nullptr;
-    uint8_t* h_pids8 = nullptr;                             // the merged ids packed 3 bytes each
-    size_t ch_pids8 = 0;
-    size_t ch_prow = 0, ch_pids = 0;
+    // the pipeline's events and pinned memory (pipe_teardown gives the group back)
+    struct Pipe {
+        Event h2d[2];                       // staging k uploaded
+        Event cp[2];                        // pipe[k]'s last result copied out
+        Event pk[2];                        // pipe[k]'s ids packed (tm_match_batch_packed)
+        PinBuf<uint8_t> h_stage[2];         // pinned packed chunk (offsets | bytes)
+        PinBuf<uint32_t> h_prow, h_pids;    // the merged CSR
+        PinBuf<uint8_t> h_pids8;            // the merged ids packed 3 bytes each
+    } pl;
 
-    // trie tables
-    Slot* d_slots = nullptr;
+    // The replica's tables on the device, their staging and the events of
+    // their uploads (destroy gives the group back).
+    struct Tables {
+        Event ev_delta;       // end of the last async delta upload (staging reusable after it)
+        Event ev_sync;        // end of the delta uploads, waited for by own-stream batches
+        // trie tables
+        DevBuf<Slot> d_slots;
+        DevBuf<uint64_t> d_foff;
+        DevBuf<uint32_t> d_flen;
+        DevBuf<uint8_t> d_fbytes;
+        DevBuf<uint8_t> d_dblob;   // the engine's delta blob (h_dblob), uploaded in one copy
+        // word dictionary mirror (device tokeniser): cuckoo key table, tails, arena
+        DevBuf<DictKey> d_dkey;
+        DevBuf<DictTail> d_tail;
+        DevBuf<uint8_t> d_arena;
+        DevBuf<uint32_t> d_dxidx;
+        DevBuf<DictKey> d_dxval;
+        // bounds-checked variant's report
+        DevBuf<uint32_t> d_dbg;
+        PinBuf<uint32_t> h_dbg;
+        // pinned staging of the appended tails (filter bytes, dictionary tails and
+        // arena) of one delta upload: small appends go out asynchronously instead
+        // of as pageable copies the host must wait for
+        PinBuf<uint8_t> h_app;
+        // routes: dests CSR by node id
+        DevBuf<uint32_t> d_roff, d_rdest;
+        // subscribers: soff / subs / scnt / sone by node id
+        DevBuf<uint64_t> d_soff;
+        DevBuf<uint32_t> d_subs, d_sone;
+        DevBuf<uint8_t> d_scnt;
+        // shared subscriptions: gcnt / goff by node id, runs, members; the run
+        // slots' cursors stay here across uploads
+        DevBuf<uint8_t> d_gcnt;
+        DevBuf<uint32_t> d_goff, d_gmem;
+        DevBuf<uint4> d_gruns;
+        DevBuf<uint2> d_gupd;
+        DevBuf<SharedSlot> d_gslots;
+        // tm_rules_match
+        DevBuf<uint32_t> d_rl;
+    } tab;
     size_t d_nslots = 0;
-    uint64_t* d_foff = nullptr;
-    uint32_t* d_flen = nullptr;
-    size_t c_foff = 0, c_flen = 0;
-    uint8_t* d_fbytes = nullptr;
-    size_t c_fbytes = 0;
     uint64_t fbytes_uploaded = 0;
-    uint8_t* d_dblob = nullptr;   // the engine's delta blob (h_dblob), uploaded in one copy
-    size_t cd_dblob = 0;
-    // word dictionary mirror (device tokeniser): cuckoo key table, tails, arena
-    DictKey* d_dkey = nullptr;
     size_t d_dict_n = 0;            // cuckoo slots on the device
     uint64_t d_dict_gen = ~0ull;    // dict.gen() of the device table
-    DictTail* d_tail = nullptr;
-    size_t c_tail = 0, tails_uploaded = 0;
-    uint8_t* d_arena = nullptr;
-    size_t c_arena = 0, arena_uploaded = 0;
-    uint32_t* d_dxidx = nullptr;
-    DictKey* d_dxval = nullptr;
-    size_t cd_dxidx = 0, cd_dxval = 0;
-    // bounds-checked variant's report
-    uint32_t* d_dbg = nullptr;
-    uint32_t* h_dbg = nullptr;
-    size_t c_dbg = 0, ch_dbg = 0;
-    // pinned staging of the appended tails (filter bytes, dictionary tails and
-    // arena) of one delta upload: small appends go out asynchronously instead
-    // of as pageable copies the host must wait for
-    uint8_t* h_app = nullptr;
-    size_t ch_app = 0;
-    // routes: dests CSR by node id (engine routes_gen when uploaded)
-    uint32_t *d_roff = nullptr, *d_rdest = nullptr;
-    size_t c_roff = 0, c_rdest = 0;
-    uint64_t routes_gen = ~0ull;
-    // subscribers: soff / subs / scnt / sone by node id (engine subs_gen when uploaded)
-    uint64_t* d_soff = nullptr;
-    uint32_t* d_subs = nullptr;
-    uint8_t* d_scnt = nullptr;
-    uint32_t* d_sone = nullptr;
-    size_t c_soff = 0, c_subs = 0, c_scnt = 0, c_sone = 0;
+    size_t tails_uploaded = 0, arena_uploaded = 0;
+    uint64_t routes_gen = ~0ull;    // engine routes_gen / subs_gen / shared_gen when uploaded
     uint64_t subs_gen = ~0ull;
-    // shared subscriptions: gcnt / goff by node id, runs, members (engine
-    // shared_gen when uploaded); the run slots' cursors stay here across uploads
-    uint8_t* d_gcnt = nullptr;
-    uint32_t *d_goff = nullptr, *d_gmem = nullptr;
-    uint4* d_gruns = nullptr;
-    uint2* d_gupd = nullptr;
-    SharedSlot* d_gslots = nullptr;
-    size_t c_gcnt = 0, c_goff = 0, c_gmem = 0, c_gruns = 0, c_gupd = 0, c_gslots = 0;
     uint64_t shared_gen = ~0ull;
-    // tm_rules_match
-    uint32_t* d_rl = nullptr;
-    size_t c_rl = 0;
 
     // async pipeline (tm_match_async / tm_match_coalesced): calls queue on amu;
     // the launcher thread turns the queue into a device batch on a free slot
@@ -1219,17 +1119,16 @@ struct tm_engine {
     // the gathered slot and filter-metadata deltas: one pinned blob, so a
     // replica's delta upload is one copy (six used to cost ~0.1 ms of device
     // time per upload in H2D setup gaps); the arrays point into it
-    uint8_t* h_dblob = nullptr;
-    size_t ch_dblob = 0, blob_bytes = 0;
+    PinBuf<uint8_t> h_dblob;
+    size_t blob_bytes = 0;
     size_t blob_off[5] = {0, 0, 0, 0, 0};   // didx | dval | fidx | foffv | flenv
     uint32_t* h_didx = nullptr;
     Slot* h_dval = nullptr;
     uint32_t* h_fidx = nullptr;
     uint64_t* h_foffv = nullptr;
     uint32_t* h_flenv = nullptr;
-    uint32_t* h_dxidx = nullptr;
-    DictKey* h_dxval = nullptr;
-    size_t ch_dxidx = 0, ch_dxval = 0;
+    PinBuf<uint32_t> h_dxidx;
+    PinBuf<DictKey> h_dxval;
     bool dev_tok = true;            // TM_CFG_HOST_TOKENIZE / TM_HOST_TOKENIZE=1: tokenise on the host
 
 
@@ -2041,39 +1940,39 @@ struct tm_engine {
         const std::vector<uint8_t>& ar = dict.arena();
         const std::vector<uint32_t>& dx = dict.dirty();
         if (R.d_dict_n != tab.size()) {
-            dev_free(R.d_dkey);
-            HIP_OK(hipMalloc((void**)&R.d_dkey, tab.size() * sizeof(DictKey)));
+            R.tab.d_dkey.reset();
+            if ((rc = R.tab.d_dkey.alloc(tab.size()))) return rc;
             R.d_dict_n = tab.size();
             R.d_dict_gen = ~0ull;
         }
         if (R.d_dict_gen != dict.gen() || keys_full) {
             pageable_used = true;
-            HIP_OK(hipMemcpyAsync(R.d_dkey, tab.data(), tab.size() * sizeof(DictKey), hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(R.tab.d_dkey.p, tab.data(), tab.size() * sizeof(DictKey), hipMemcpyHostToDevice, stream));
             R.d_dict_gen = dict.gen();
         } else if (!dx.empty()) {
             const size_t k = dx.size();
-            if ((rc = dev_reserve(R.d_dxidx, R.cd_dxidx, k))) return rc;
-            if ((rc = dev_reserve(R.d_dxval, R.cd_dxval, k))) return rc;
-            HIP_OK(hipMemcpyAsync(R.d_dxidx, h_dxidx, k * 4, hipMemcpyHostToDevice, stream));
-            HIP_OK(hipMemcpyAsync(R.d_dxval, h_dxval, k * sizeof(DictKey), hipMemcpyHostToDevice, stream));
-            HIP_OK(launch_scatter_keys(R.d_dkey, R.d_dxidx, R.d_dxval, (uint32_t)k, stream));
+            if ((rc = R.tab.d_dxidx.reserve(k))) return rc;
+            if ((rc = R.tab.d_dxval.reserve(k))) return rc;
+            HIP_OK(hipMemcpyAsync(R.tab.d_dxidx.p, h_dxidx.p, k * 4, hipMemcpyHostToDevice, stream));
+            HIP_OK(hipMemcpyAsync(R.tab.d_dxval.p, h_dxval.p, k * sizeof(DictKey), hipMemcpyHostToDevice, stream));
+            HIP_OK(launch_scatter_keys(R.tab.d_dkey.p, R.tab.d_dxidx.p, R.tab.d_dxval.p, (uint32_t)k, stream));
             async_used = true;
         }
-        if (R.c_tail < tl.size() + 1) {
-            if ((rc = dev_reserve(R.d_tail, R.c_tail, tl.size() + tl.size() / 2 + 64))) return rc;
+        if (R.tab.d_tail.cap < tl.size() + 1) {
+            if ((rc = R.tab.d_tail.reserve(tl.size() + tl.size() / 2 + 64))) return rc;
             R.tails_uploaded = 0;
         }
         if (tl.size() > R.tails_uploaded) {
-            HIP_OK(h2d_tail(R.d_tail + R.tails_uploaded, tl.data() + R.tails_uploaded,
+            HIP_OK(h2d_tail(R.tab.d_tail.p + R.tails_uploaded, tl.data() + R.tails_uploaded,
                             (tl.size() - R.tails_uploaded) * sizeof(DictTail)));
             R.tails_uploaded = tl.size();
         }
-        if (R.c_arena < ar.size() + 1) {
-            if ((rc = dev_reserve(R.d_arena, R.c_arena, ar.size() + 1))) return rc;
+        if (R.tab.d_arena.cap < ar.size() + 1) {
+            if ((rc = R.tab.d_arena.reserve(ar.size() + 1))) return rc;
             R.arena_uploaded = 0;
         }
         if (ar.size() > R.arena_uploaded) {
-            HIP_OK(h2d_tail(R.d_arena + R.arena_uploaded, ar.data() + R.arena_uploaded, ar.size() - R.arena_uploaded));
+            HIP_OK(h2d_tail(R.tab.d_arena.p + R.arena_uploaded, ar.data() + R.arena_uploaded, ar.size() - R.arena_uploaded));
             R.arena_uploaded = ar.size();
         }
         return TM_OK;

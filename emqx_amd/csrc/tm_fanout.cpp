@@ -64,11 +64,11 @@ int tm_engine::sync_routes(Replica& R) {
     if (R.routes_gen == routes_gen) return TM_OK;
     const size_t nn = h_roff.size() - 1;
     int rc;
-    if ((rc = dev_reserve(R.d_roff, R.c_roff, nn + 1))) return rc;
-    if ((rc = dev_reserve(R.d_rdest, R.c_rdest, std::max<size_t>(h_rdest.size(), 1)))) return rc;
-    HIP_OK(hipMemcpyAsync(R.d_roff, h_roff.data(), (nn + 1) * 4, hipMemcpyHostToDevice, R.stream));
+    if ((rc = R.tab.d_roff.reserve(nn + 1))) return rc;
+    if ((rc = R.tab.d_rdest.reserve(std::max<size_t>(h_rdest.size(), 1)))) return rc;
+    HIP_OK(hipMemcpyAsync(R.tab.d_roff.p, h_roff.data(), (nn + 1) * 4, hipMemcpyHostToDevice, R.stream));
     if (!h_rdest.empty())
-        HIP_OK(hipMemcpyAsync(R.d_rdest, h_rdest.data(), h_rdest.size() * 4, hipMemcpyHostToDevice, R.stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_rdest.p, h_rdest.data(), h_rdest.size() * 4, hipMemcpyHostToDevice, R.stream));
     HIP_OK(hipStreamSynchronize(R.stream));
     R.routes_gen = routes_gen;
     return TM_OK;
@@ -86,51 +86,46 @@ int tm_engine::batch_routes(tm_batch* b, tm_routes* out) {
     const uint64_t m64 = b->total;   // match entries (< 2^32: u32 result CSR)
     if (m64 > 0xFFFFFFF0ull) return TM_EOVERFLOW;
     const uint32_t m = (uint32_t)m64;
-    if ((rc = dev_reserve(b->d_rcount, b->c_rcount, (size_t)m + 1))) return rc;    // per-entry counts
-    if ((rc = dev_reserve(b->d_reoff, b->c_reoff, (size_t)m + 1))) return rc;
-    if ((rc = dev_reserve(b->d_rrow, b->c_rrow, nn + 1))) return rc;
-    if ((rc = dev_reserve(b->d_rbsums, b->c_rbsums, (size_t)scan_block_count(m) + 1))) return rc;
-    if ((rc = dev_reserve(b->d_rtotal, b->c_rtotal, 1))) return rc;
-    if ((rc = host_reserve(b->h_rtotal, b->ch_rtotal, 1))) return rc;
-    RouteArgs r{};
-    r.row_off = b->d_rowoff; r.ids = b->d_ids; r.n = n; r.m = m;
-    r.roff = R.d_roff; r.rdest = R.d_rdest; r.nnodes = (uint32_t)(h_roff.size() - 1);
-    r.ecount = b->d_rcount; r.eoff = b->d_reoff; r.bsums = b->d_rbsums; r.total = b->d_rtotal;
-    r.r_rowoff = b->d_rrow;
-    HIP_OK(launch_route_count(r, stream));
     ScanArgs sa{};
-    sa.count = b->d_rcount; sa.row_off = b->d_reoff; sa.block_sums = b->d_rbsums; sa.n = m;
+    if ((rc = b->rt.es.reserve(m, nn, sa))) return rc;
+    if ((rc = b->rt.h_rtotal.reserve(1))) return rc;
+    RouteArgs r{};
+    r.row_off = b->dcsr.d_rowoff.p; r.ids = b->dcsr.d_ids.p; r.n = n; r.m = m;
+    r.roff = R.tab.d_roff.p; r.rdest = R.tab.d_rdest.p; r.nnodes = (uint32_t)(h_roff.size() - 1);
+    r.ecount = b->rt.es.count.p; r.eoff = b->rt.es.eoff.p; r.bsums = b->rt.es.bsums.p; r.total = b->rt.es.total.p;
+    r.r_rowoff = b->rt.es.row.p;
+    HIP_OK(launch_route_count(r, stream));
     if (m) {
-        HIP_OK(launch_scan(sa, stream, b->d_rtotal));
+        HIP_OK(launch_scan(sa, stream, b->rt.es.total.p));
     } else {
-        HIP_OK(hipMemsetAsync(b->d_rtotal, 0, 4, stream));
+        HIP_OK(hipMemsetAsync(b->rt.es.total.p, 0, 4, stream));
     }
     HIP_OK(launch_route_rows(r, stream));
-    HIP_OK(hipMemcpyAsync(b->h_rtotal, b->d_rtotal, 4, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(b->rt.h_rtotal.p, b->rt.es.total.p, 4, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->h_rtotal[0];
-    if ((rc = dev_reserve(b->d_rfid, b->c_rfid, std::max<uint64_t>(total, 1)))) return rc;
-    if ((rc = dev_reserve(b->d_rdest, b->c_rdest, std::max<uint64_t>(total, 1)))) return rc;
-    r.out_fid = b->d_rfid; r.out_dest = b->d_rdest; r.cap = total;
+    const uint64_t total = b->rt.h_rtotal.p[0];
+    if ((rc = b->rt.d_rfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
+    if ((rc = b->rt.d_rdest.reserve(std::max<uint64_t>(total, 1)))) return rc;
+    r.out_fid = b->rt.d_rfid.p; r.out_dest = b->rt.d_rdest.p; r.cap = total;
     HIP_OK(launch_route_fill(r, stream));
-    if ((rc = host_reserve(b->h_rrow, b->ch_rrow, nn + 1))) return rc;
-    if ((rc = host_reserve(b->h_rfid, b->ch_rfid, std::max<uint64_t>(total, 1)))) return rc;
-    if ((rc = host_reserve(b->h_rdest, b->ch_rdest, std::max<uint64_t>(total, 1)))) return rc;
-    HIP_OK(hipMemcpyAsync(b->h_rrow, b->d_rrow, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+    if ((rc = b->rt.h_rrow.reserve(nn + 1))) return rc;
+    if ((rc = b->rt.h_rfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
+    if ((rc = b->rt.h_rdest.reserve(std::max<uint64_t>(total, 1)))) return rc;
+    HIP_OK(hipMemcpyAsync(b->rt.h_rrow.p, b->rt.es.row.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
     if (total) {
-        HIP_OK(hipMemcpyAsync(b->h_rfid, b->d_rfid, total * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(b->h_rdest, b->d_rdest, total * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(b->rt.h_rfid.p, b->rt.d_rfid.p, total * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(b->rt.h_rdest.p, b->rt.d_rdest.p, total * 4, hipMemcpyDeviceToHost, stream));
     }
     HIP_OK(hipStreamSynchronize(stream));
-    if (b->h_rrow[n] != total) {
-        snprintf(last_error(), 512, "inconsistent route CSR: %u vs %llu", b->h_rrow[n], (unsigned long long)total);
+    if (b->rt.h_rrow.p[n] != total) {
+        snprintf(last_error(), 512, "inconsistent route CSR: %u vs %llu", b->rt.h_rrow.p[n], (unsigned long long)total);
         return TM_EIO;
     }
     out->n_topics = n;
     out->n_routes = total;
-    out->row_offsets = b->h_rrow;
-    out->filter_ids = b->h_rfid;
-    out->dests = b->h_rdest;
+    out->row_offsets = b->rt.h_rrow.p;
+    out->filter_ids = b->rt.h_rfid.p;
+    out->dests = b->rt.h_rdest.p;
     return TM_OK;
 }
 
@@ -220,15 +215,15 @@ int tm_engine::sync_subs(Replica& R) {
     if (R.subs_gen == subs_gen) return TM_OK;
     const size_t sn = subs_nn;
     int rc;
-    if ((rc = dev_reserve(R.d_soff, R.c_soff, sn + 1))) return rc;
-    if ((rc = dev_reserve(R.d_scnt, R.c_scnt, std::max<size_t>(sn, 1)))) return rc;
-    if ((rc = dev_reserve(R.d_sone, R.c_sone, std::max<size_t>(sn, 1)))) return rc;
-    if ((rc = dev_reserve(R.d_subs, R.c_subs, std::max<size_t>(h_subs.size(), 1)))) return rc;
-    HIP_OK(hipMemcpyAsync(R.d_soff, h_soff.data(), (sn + 1) * 8, hipMemcpyHostToDevice, R.stream));
-    if (sn) HIP_OK(hipMemcpyAsync(R.d_scnt, h_scnt.data(), sn, hipMemcpyHostToDevice, R.stream));
-    if (sn) HIP_OK(hipMemcpyAsync(R.d_sone, h_sone.data(), sn * 4, hipMemcpyHostToDevice, R.stream));
+    if ((rc = R.tab.d_soff.reserve(sn + 1))) return rc;
+    if ((rc = R.tab.d_scnt.reserve(std::max<size_t>(sn, 1)))) return rc;
+    if ((rc = R.tab.d_sone.reserve(std::max<size_t>(sn, 1)))) return rc;
+    if ((rc = R.tab.d_subs.reserve(std::max<size_t>(h_subs.size(), 1)))) return rc;
+    HIP_OK(hipMemcpyAsync(R.tab.d_soff.p, h_soff.data(), (sn + 1) * 8, hipMemcpyHostToDevice, R.stream));
+    if (sn) HIP_OK(hipMemcpyAsync(R.tab.d_scnt.p, h_scnt.data(), sn, hipMemcpyHostToDevice, R.stream));
+    if (sn) HIP_OK(hipMemcpyAsync(R.tab.d_sone.p, h_sone.data(), sn * 4, hipMemcpyHostToDevice, R.stream));
     if (!h_subs.empty())
-        HIP_OK(hipMemcpyAsync(R.d_subs, h_subs.data(), h_subs.size() * 4, hipMemcpyHostToDevice, R.stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_subs.p, h_subs.data(), h_subs.size() * 4, hipMemcpyHostToDevice, R.stream));
     HIP_OK(hipStreamSynchronize(R.stream));
     R.subs_gen = subs_gen;
     return TM_OK;
@@ -248,67 +243,68 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out) {
     FanArgs fa{};
     uint64_t nm = b->total;
     if (rows) {   // the walk's staging regions as one virtual entry space (FanArgs)
-        const uint64_t cap = std::min<uint64_t>(b->c_sfids, MAX_RESULT);
+        const uint64_t cap = std::min<uint64_t>(b->walk.d_sfids.cap, MAX_RESULT);
         fa.nreg = b->one_region ? 1u : TICKET_GROUPS;
         fa.rcap = region_cap(cap, b->one_region);
         // [vb: TICKET_GROUPS + 1 | rtop: TICKET_GROUPS] in pinned memory -> HBM
         constexpr size_t FM = 2 * TICKET_GROUPS + 1;
-        if ((rc = host_reserve(b->h_fmeta, b->ch_fmeta, FM))) return rc;
-        if ((rc = dev_reserve(b->d_fmeta, b->c_fmeta, FM))) return rc;
-        uint64_t* vb = b->h_fmeta;
-        uint64_t* rtop = b->h_fmeta + TICKET_GROUPS + 1;
-        std::fill(b->h_fmeta, b->h_fmeta + FM, 0ull);
+        if ((rc = b->fan.h_fmeta.reserve(FM))) return rc;
+        if ((rc = b->fan.d_fmeta.reserve(FM))) return rc;
+        uint64_t* vb = b->fan.h_fmeta.p;
+        uint64_t* rtop = b->fan.h_fmeta.p + TICKET_GROUPS + 1;
+        std::fill(b->fan.h_fmeta.p, b->fan.h_fmeta.p + FM, 0ull);
         uint64_t v = 0, staged = 0;
         for (uint32_t g = 0; g < fa.nreg; ++g) {
             vb[g] = v;
-            rtop[g] = xg_top_read(b->h_ctrl, g);
+            rtop[g] = xg_top_read(b->walk.h_ctrl, g);
             staged += rtop[g];
             v += (rtop[g] + 15) & ~15ull;
         }
         for (uint32_t g = fa.nreg; g <= TICKET_GROUPS; ++g) vb[g] = v;
-        HIP_OK(hipMemcpyAsync(b->d_fmeta, b->h_fmeta, FM * 8, hipMemcpyHostToDevice, stream));
-        fa.vb = b->d_fmeta;
-        fa.rtop = b->d_fmeta + TICKET_GROUPS + 1;
+        HIP_OK(hipMemcpyAsync(b->fan.d_fmeta.p, b->fan.h_fmeta.p, FM * 8, hipMemcpyHostToDevice, stream));
+        fa.vb = b->fan.d_fmeta.p;
+        fa.rtop = b->fan.d_fmeta.p + TICKET_GROUPS + 1;
         if (staged != b->total) {
             snprintf(last_error(), 512, "staging holds %llu entries, the walk matched %llu",
                      (unsigned long long)staged, (unsigned long long)b->total);
             return TM_EIO;
         }
         nm = v;
-        if ((rc = dev_reserve(b->d_dcount, b->c_dcount, std::max<size_t>(n, 1)))) return rc;
-        fa.rcount = b->d_count;
-        fa.rsrc = b->d_src;
-        fa.dcount = b->d_dcount;
+        if ((rc = b->fan.d_dcount.reserve(std::max<size_t>(n, 1)))) return rc;
+        fa.rcount = b->walk.d_count;
+        fa.rsrc = b->walk.d_src;
+        fa.dcount = b->fan.d_dcount.p;
     }
     const uint32_t nb = (uint32_t)((nm + 1 + fan_scan_tile() - 1) / fan_scan_tile());
-    if ((rc = dev_reserve(b->d_moff, b->c_moff, nm + 1))) return rc;
-    if ((rc = dev_reserve(b->d_fbsums, b->c_fbsums, nb))) return rc;
-    if ((rc = dev_reserve(b->d_moff32, b->c_moff32, nm + 1))) return rc;
-    if ((rc = dev_reserve(b->d_fbig, b->c_fbig, nb))) return rc;
-    if ((rc = dev_reserve(b->d_ftotal, b->c_ftotal, 1))) return rc;
-    if ((rc = dev_reserve(b->d_drow, b->c_drow, (size_t)n + 1))) return rc;
-    if ((rc = host_reserve(b->h_ftotal, b->ch_ftotal, 1))) return rc;
+    if ((rc = b->fan.d_moff.reserve(nm + 1))) return rc;
+    if ((rc = b->fan.d_fbsums.reserve(nb))) return rc;
+    if ((rc = b->fan.d_moff32.reserve(nm + 1))) return rc;
+    if ((rc = b->fan.d_fbig.reserve(nb))) return rc;
+    if ((rc = b->fan.d_ftotal.reserve(1))) return rc;
+    if ((rc = b->fan.d_drow.reserve((size_t)n + 1))) return rc;
+    if ((rc = b->fan.h_ftotal.reserve(1))) return rc;
     const bool counts_only = flags & TM_DISPATCH_COUNT_ONLY;
-    if (!b->fev0) {
-        HIP_OK(hipEventCreate(&b->fev0));
-        HIP_OK(hipEventCreate(&b->fev1));
+    if (!b->fan.fev0.e) {
+        if ((rc = b->fan.fev0.create())) return rc;
+        if ((rc = b->fan.fev1.create())) return rc;
     }
-    fa.row_off = b->d_rowoff; fa.ids = rows ? b->d_sfids : b->d_ids; fa.n = n; fa.n_matches = nm;
-    fa.soff = R.d_soff; fa.scnt = R.d_scnt; fa.sone = R.d_sone; fa.subs = R.d_subs; fa.nnodes = subs_nn;
-    fa.moff = b->d_moff; fa.moff32 = b->d_moff32; fa.bbig = b->d_fbig; fa.bsums = b->d_fbsums;
-    fa.big_limit = fan_big_limit; fa.d_total = b->d_ftotal; fa.drow = b->d_drow;
+    fa.row_off = b->dcsr.d_rowoff.p; fa.ids = rows ? b->walk.d_sfids.p : b->dcsr.d_ids.p; fa.n = n; fa.n_matches = nm;
+    fa.soff = R.tab.d_soff.p; fa.scnt = R.tab.d_scnt.p; fa.sone = R.tab.d_sone.p; fa.subs = R.tab.d_subs.p;
+    fa.nnodes = subs_nn;
+    fa.moff = b->fan.d_moff.p; fa.moff32 = b->fan.d_moff32.p; fa.bbig = b->fan.d_fbig.p; fa.bsums = b->fan.d_fbsums.p;
+    fa.big_limit = fan_big_limit; fa.d_total = b->fan.d_ftotal.p; fa.drow = b->fan.d_drow.p;
     HIP_OK(launch_fan_scan(fa, stream));
-    HIP_OK(hipMemcpyAsync(b->h_ftotal, b->d_ftotal, 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(b->fan.h_ftotal.p, b->fan.d_ftotal.p, 8, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->h_ftotal[0];
+    const uint64_t total = b->fan.h_ftotal.p[0];
     float fill_ms = 0.f;
     if (!counts_only) {
-        if ((rc = dev_reserve(b->d_fout, b->c_fout, std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = dev_reserve(b->d_ftile, b->c_ftile, (size_t)(total / fan_fill_tile()) + 2))) return rc;
-        fa.out = b->d_fout; fa.total = total; fa.tile_j = b->d_ftile;
-        HIP_OK(hipEventRecord(b->fev0, stream));
+        if ((rc = b->fan.d_fout.reserve(std::max<uint64_t>(total, 1)))) return rc;
+        if ((rc = b->fan.d_ftile.reserve((size_t)(total / fan_fill_tile()) + 2))) return rc;
+        fa.out = b->fan.d_fout.p; fa.total = total; fa.tile_j = b->fan.d_ftile.p;
+        HIP_OK(hipEventRecord(b->fan.fev0.e, stream));
         HIP_OK(launch_fan_fill(fa, stream));
-        HIP_OK(hipEventRecord(b->fev1, stream));
+        HIP_OK(hipEventRecord(b->fan.fev1.e, stream));
     }
     const bool want_moff = flags & TM_DISPATCH_MATCH_OFFSETS;
     if (want_moff) HIP_OK(launch_fan_globalize(fa, stream));   // moff is block-relative until now
@@ -318,34 +314,34 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out) {
     out->row_counts = nullptr;
     if (flags & TM_DISPATCH_DEVICE) {
         HIP_OK(hipStreamSynchronize(stream));
-        if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fev0, b->fev1));
-        out->row_offsets = b->d_drow;
-        out->match_offsets = want_moff ? b->d_moff : nullptr;
-        out->subscribers = counts_only ? nullptr : b->d_fout;
+        if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fan.fev0.e, b->fan.fev1.e));
+        out->row_offsets = b->fan.d_drow.p;
+        out->match_offsets = want_moff ? b->fan.d_moff.p : nullptr;
+        out->subscribers = counts_only ? nullptr : b->fan.d_fout.p;
         out->fill_ms = fill_ms;
-        out->row_counts = rows ? b->d_dcount : nullptr;
+        out->row_counts = rows ? b->fan.d_dcount.p : nullptr;
         return TM_OK;
     }
-    if ((rc = host_reserve(b->h_drow, b->ch_drow, (size_t)n + 1))) return rc;
-    HIP_OK(hipMemcpyAsync(b->h_drow, b->d_drow, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+    if ((rc = b->fan.h_drow.reserve((size_t)n + 1))) return rc;
+    HIP_OK(hipMemcpyAsync(b->fan.h_drow.p, b->fan.d_drow.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
     if (want_moff) {
-        if ((rc = host_reserve(b->h_moff, b->ch_moff, nm + 1))) return rc;
-        HIP_OK(hipMemcpyAsync(b->h_moff, b->d_moff, (nm + 1) * 8, hipMemcpyDeviceToHost, stream));
+        if ((rc = b->fan.h_moff.reserve(nm + 1))) return rc;
+        HIP_OK(hipMemcpyAsync(b->fan.h_moff.p, b->fan.d_moff.p, (nm + 1) * 8, hipMemcpyDeviceToHost, stream));
     }
     if (!counts_only) {
-        if ((rc = host_reserve(b->h_fout, b->ch_fout, std::max<uint64_t>(total, 1)))) return rc;
-        if (total) HIP_OK(hipMemcpyAsync(b->h_fout, b->d_fout, total * 4, hipMemcpyDeviceToHost, stream));
+        if ((rc = b->fan.h_fout.reserve(std::max<uint64_t>(total, 1)))) return rc;
+        if (total) HIP_OK(hipMemcpyAsync(b->fan.h_fout.p, b->fan.d_fout.p, total * 4, hipMemcpyDeviceToHost, stream));
     }
     HIP_OK(hipStreamSynchronize(stream));
-    if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fev0, b->fev1));
-    if (b->h_drow[n] != total) {
-        snprintf(last_error(), 512, "inconsistent delivery CSR: %llu vs %llu", (unsigned long long)b->h_drow[n],
+    if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fan.fev0.e, b->fan.fev1.e));
+    if (b->fan.h_drow.p[n] != total) {
+        snprintf(last_error(), 512, "inconsistent delivery CSR: %llu vs %llu", (unsigned long long)b->fan.h_drow.p[n],
                  (unsigned long long)total);
         return TM_EIO;
     }
-    out->row_offsets = b->h_drow;
-    out->match_offsets = want_moff ? b->h_moff : nullptr;
-    out->subscribers = counts_only ? nullptr : b->h_fout;
+    out->row_offsets = b->fan.h_drow.p;
+    out->match_offsets = want_moff ? b->fan.h_moff.p : nullptr;
+    out->subscribers = counts_only ? nullptr : b->fan.h_fout.p;
     out->fill_ms = fill_ms;
     return TM_OK;
 }
@@ -390,8 +386,8 @@ int tm_engine::rules_match(Replica& R, const uint8_t* names, const uint64_t* nof
     const size_t nbits = (size_t)n * wpr;
     const size_t words = rw.size() + ro.size() + nw.size() + no.size() + nbits + (r + n + 3) / 4 + 4;
     int rc;
-    if ((rc = dev_reserve(R.d_rl, R.c_rl, words))) return rc;
-    uint32_t* d = R.d_rl;
+    if ((rc = R.tab.d_rl.reserve(words))) return rc;
+    uint32_t* d = R.tab.d_rl.p;
     uint32_t *d_rw = d, *d_ro = d_rw + rw.size(), *d_nw = d_ro + ro.size(), *d_no = d_nw + nw.size();
     uint32_t* d_bits = d_no + no.size();
     uint8_t* d_rf = reinterpret_cast<uint8_t*>(d_bits + nbits);

@@ -38,8 +38,8 @@ int tm_engine::init(const tm_config* cfg, const int32_t* devices, uint32_t ndev)
             reps.push_back(R);
             HIP_OK(hipSetDevice(R->device));
             HIP_OK(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&R->ev_delta, hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&R->ev_sync, hipEventDisableTiming));
+            if (int rc = R->tab.ev_delta.create(hipEventDisableTiming)) return rc;
+            if (int rc = R->tab.ev_sync.create(hipEventDisableTiming)) return rc;
         }
         HIP_OK(hipSetDevice(device));
     }
@@ -54,24 +54,14 @@ void tm_engine::destroy() {
         pipe_teardown(*R);
         R->scratch.release();
         R->tokb.release();
-        dev_free(R->d_slots); dev_free(R->d_foff); dev_free(R->d_flen); dev_free(R->d_fbytes);
-        dev_free(R->d_dkey); dev_free(R->d_tail); dev_free(R->d_arena); dev_free(R->d_dxidx); dev_free(R->d_dxval);
-        dev_free(R->d_dblob);
-        dev_free(R->d_dbg); dev_free(R->d_roff); dev_free(R->d_rdest); dev_free(R->d_rl);
-        dev_free(R->d_soff); dev_free(R->d_subs); dev_free(R->d_scnt); dev_free(R->d_sone);
-        dev_free(R->d_gcnt); dev_free(R->d_goff); dev_free(R->d_gmem); dev_free(R->d_gruns); dev_free(R->d_gupd);
-        dev_free(R->d_gslots);
-        if (R->h_dbg) (void)hipHostFree(R->h_dbg);
-        if (R->h_app) (void)hipHostFree(R->h_app);
-        if (R->ev_delta) (void)hipEventDestroy(R->ev_delta);
-        if (R->ev_sync) (void)hipEventDestroy(R->ev_sync);
+        R->tab = {};
         if (R->stream) (void)hipStreamDestroy(R->stream);
         delete R;
     }
     reps.clear();
-    for (void* h : {(void*)h_dxidx, (void*)h_dxval, (void*)h_dblob})
-        if (h) (void)hipHostFree(h);
-    h_dxidx = nullptr; h_dxval = nullptr; h_dblob = nullptr;
+    h_dxidx.reset();
+    h_dxval.reset();
+    h_dblob.reset();
     h_didx = nullptr; h_dval = nullptr; h_fidx = nullptr; h_foffv = nullptr; h_flenv = nullptr;
 }
 
@@ -100,15 +90,16 @@ int tm_engine::run_slices(const uint8_t* topics, const uint64_t* offsets, uint32
 
 int tm_engine::pipe_setup(Replica& R) {
     if (R.pipe_ready) return TM_OK;
+    int rc;
     for (int k = 0; k < 2; ++k) {
         tm_batch& b = R.pipe[k];
         b.rep = &R;
         HIP_OK(hipStreamCreateWithFlags(&b.own, hipStreamNonBlocking));
         b.own_user = true;   // (kept out of async_stop's sweep of slot batches)
         R.readers.push_back(&b);
-        HIP_OK(hipEventCreateWithFlags(&R.pipe_h2d[k], hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&R.pipe_cp[k], hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&R.pipe_pk[k], hipEventDisableTiming));
+        if ((rc = R.pl.h2d[k].create(hipEventDisableTiming))) return rc;
+        if ((rc = R.pl.cp[k].create(hipEventDisableTiming))) return rc;
+        if ((rc = R.pl.pk[k].create(hipEventDisableTiming))) return rc;
     }
     HIP_OK(hipStreamCreateWithFlags(&R.pipe_copy, hipStreamNonBlocking));
     R.pipe_ready = true;
@@ -124,22 +115,10 @@ void tm_engine::pipe_teardown(Replica& R) {
         forget_launch(&b);
         b.release();
         drop_user_stream(&b);
-        if (R.pipe_h2d[k]) (void)hipEventDestroy(R.pipe_h2d[k]);
-        if (R.pipe_cp[k]) (void)hipEventDestroy(R.pipe_cp[k]);
-        if (R.pipe_pk[k]) (void)hipEventDestroy(R.pipe_pk[k]);
-        R.pipe_h2d[k] = R.pipe_cp[k] = R.pipe_pk[k] = nullptr;
-        if (R.h_stage[k]) (void)hipHostFree(R.h_stage[k]);
-        R.h_stage[k] = nullptr;
-        R.ch_stage[k] = 0;
     }
     if (R.pipe_copy) (void)hipStreamDestroy(R.pipe_copy);
     R.pipe_copy = nullptr;
-    if (R.h_prow) (void)hipHostFree(R.h_prow);
-    if (R.h_pids) (void)hipHostFree(R.h_pids);
-    if (R.h_pids8) (void)hipHostFree(R.h_pids8);
-    R.h_prow = R.h_pids = nullptr;
-    R.h_pids8 = nullptr;
-    R.ch_prow = R.ch_pids = R.ch_pids8 = 0;
+    R.pl = {};
     R.pipe_ready = false;
 }
 
@@ -148,7 +127,7 @@ int tm_engine::match_batch_pipelined(Replica& R, const uint8_t* topics, const ui
     int rc;
     if ((rc = pipe_setup(R))) return rc;
     const uint32_t nch = (n + PIPE_CHUNK - 1) / PIPE_CHUNK;
-    if ((rc = host_reserve(R.h_prow, R.ch_prow, (size_t)n + 1))) return rc;
+    if ((rc = R.pl.h_prow.reserve((size_t)n + 1))) return rc;
     bool h2d_pending[2] = {false, false}, cp_pending[2] = {false, false};
     std::vector<uint64_t> cbase(nch + 1, 0);
     // every stream is drained before returning: staging and results stay consistent
@@ -167,24 +146,24 @@ int tm_engine::match_batch_pipelined(Replica& R, const uint8_t* topics, const ui
             const uint32_t lo = j * PIPE_CHUNK, cnt = std::min(n - lo, PIPE_CHUNK);
             const uint64_t b0 = offsets[lo], nb = offsets[lo + cnt] - b0;
             const size_t head = packed_head(cnt);
-            if (h2d_pending[k]) HIP_OK(hipEventSynchronize(R.pipe_h2d[k]));   // staging k is free again
-            if ((rc = host_reserve(R.h_stage[k], R.ch_stage[k], head + nb))) return rc;
-            uint64_t* so = reinterpret_cast<uint64_t*>(R.h_stage[k]);
-            uint8_t* sb = R.h_stage[k] + head;
+            if (h2d_pending[k]) HIP_OK(hipEventSynchronize(R.pl.h2d[k].e));   // staging k is free again
+            if ((rc = R.pl.h_stage[k].reserve(head + nb))) return rc;
+            uint64_t* so = reinterpret_cast<uint64_t*>(R.pl.h_stage[k].p);
+            uint8_t* sb = R.pl.h_stage[k].p + head;
             par_chunks((size_t)cnt + 1, [&](size_t i0, size_t i1) {
                 for (size_t i = i0; i < i1; ++i) so[i] = offsets[lo + i] - b0;
             });
             par_chunks(nb, [&](size_t i0, size_t i1) { memcpy(sb + i0, topics + b0 + i0, i1 - i0); });
-            if (cp_pending[k]) HIP_OK(hipStreamWaitEvent(X->own, R.pipe_cp[k], 0));   // its last ids were copied out
+            if (cp_pending[k]) HIP_OK(hipStreamWaitEvent(X->own, R.pl.cp[k].e, 0));   // its last ids were copied out
             if (dev_tok) {
-                rc = upload_packed(X, R.h_stage[k], cnt, nb);
+                rc = upload_packed(X, R.pl.h_stage[k].p, cnt, nb);
             } else {
                 upload_nosync = true;
                 rc = prepare(X, sb, so, cnt);
                 upload_nosync = false;
             }
             if (rc) return rc;
-            HIP_OK(hipEventRecord(R.pipe_h2d[k], X->own));
+            HIP_OK(hipEventRecord(R.pl.h2d[k].e, X->own));
             h2d_pending[k] = true;
             X->eager_dense = true;
             rc = launch(X);
@@ -200,50 +179,48 @@ int tm_engine::match_batch_pipelined(Replica& R, const uint8_t* topics, const ui
             const uint64_t base = cbase[j - 1], total = Y->total;
             if (base + total > MAX_RESULT) return TM_EOVERFLOW;   // u32 CSR offsets
             if (pack == 3) {   // ids packed to 3 bytes on the device, copied packed (h_pids8)
-                if (base + total > R.ch_pids8 / 3) {
+                if (base + total > R.pl.h_pids8.cap / 3) {
                     HIP_OK(hipStreamSynchronize(R.pipe_copy));
                     const size_t want = (size_t)(base + total) +
                                         (size_t)((double)(total + 1) / cnt * (n - lo - cnt) * 1.25) + 1024;
-                    uint8_t* np = nullptr;
-                    HIP_OK(hipHostMalloc((void**)&np, want * 3 + 16, hipHostMallocDefault));
-                    if (base) memcpy(np, R.h_pids8, base * 3);
-                    if (R.h_pids8) (void)hipHostFree(R.h_pids8);
-                    R.h_pids8 = np;
-                    R.ch_pids8 = want * 3 + 16;
+                    PinBuf<uint8_t> np;
+                    if ((rc = np.alloc(want * 3 + 16))) return rc;
+                    if (base) memcpy(np.p, R.pl.h_pids8.p, base * 3);
+                    R.pl.h_pids8 = std::move(np);
                 }
                 if (total) {
-                    if ((rc = dev_reserve(Y->d_pack, Y->c_pack, total * 3 + 16))) return rc;
-                    HIP_OK(launch_pack_ids(Y->d_ids, total, Y->d_pack, Y->own));
+                    if ((rc = Y->dcsr.d_pack.reserve(total * 3 + 16))) return rc;
+                    HIP_OK(launch_pack_ids(Y->dcsr.d_ids.p, total, Y->dcsr.d_pack.p, Y->own));
                 }
-                HIP_OK(hipEventRecord(R.pipe_pk[k], Y->own));
-                HIP_OK(hipStreamWaitEvent(R.pipe_copy, R.pipe_pk[k], 0));
+                HIP_OK(hipEventRecord(R.pl.pk[k].e, Y->own));
+                HIP_OK(hipStreamWaitEvent(R.pipe_copy, R.pl.pk[k].e, 0));
                 if (total)
-                    HIP_OK(hipMemcpyAsync(R.h_pids8 + base * 3, Y->d_pack, total * 3, hipMemcpyDeviceToHost,
+                    HIP_OK(hipMemcpyAsync(R.pl.h_pids8.p + base * 3, Y->dcsr.d_pack.p, total * 3, hipMemcpyDeviceToHost,
                                           R.pipe_copy));
-                HIP_OK(hipMemcpyAsync(R.h_prow + lo, Y->d_rowoff, (size_t)cnt * 4, hipMemcpyDeviceToHost,
+                HIP_OK(hipMemcpyAsync(R.pl.h_prow.p + lo, Y->dcsr.d_rowoff.p, (size_t)cnt * 4, hipMemcpyDeviceToHost,
                                       R.pipe_copy));
-                HIP_OK(hipEventRecord(R.pipe_cp[k], R.pipe_copy));
+                HIP_OK(hipEventRecord(R.pl.cp[k].e, R.pipe_copy));
                 cp_pending[k] = true;
                 cbase[j] = base + total;
                 continue;
             }
-            if (base + total > R.ch_pids) {
+            if (base + total > R.pl.h_pids.cap) {
                 // grow the merged ids (earlier copies land first): room for the rest at this chunk's rate
                 HIP_OK(hipStreamSynchronize(R.pipe_copy));
                 const size_t want = (size_t)(base + total) +
                                     (size_t)((double)(total + 1) / cnt * (n - lo - cnt) * 1.25) + 1024;
-                uint32_t* np = nullptr;
-                HIP_OK(hipHostMalloc((void**)&np, want * sizeof(uint32_t), hipHostMallocDefault));
-                if (base) memcpy(np, R.h_pids, base * sizeof(uint32_t));
-                if (R.h_pids) (void)hipHostFree(R.h_pids);
-                R.h_pids = np;
-                R.ch_pids = want;
+                PinBuf<uint32_t> np;
+                if ((rc = np.alloc(want))) return rc;
+                if (base) memcpy(np.p, R.pl.h_pids.p, base * sizeof(uint32_t));
+                R.pl.h_pids = std::move(np);
             }
-            HIP_OK(hipStreamWaitEvent(R.pipe_copy, Y->ev_end, 0));
+            HIP_OK(hipStreamWaitEvent(R.pipe_copy, Y->walk.ev_end.e, 0));
             if (total)
-                HIP_OK(hipMemcpyAsync(R.h_pids + base, Y->d_ids, total * 4, hipMemcpyDeviceToHost, R.pipe_copy));
-            HIP_OK(hipMemcpyAsync(R.h_prow + lo, Y->d_rowoff, (size_t)cnt * 4, hipMemcpyDeviceToHost, R.pipe_copy));
-            HIP_OK(hipEventRecord(R.pipe_cp[k], R.pipe_copy));
+                HIP_OK(hipMemcpyAsync(R.pl.h_pids.p + base, Y->dcsr.d_ids.p, total * 4, hipMemcpyDeviceToHost,
+                                      R.pipe_copy));
+            HIP_OK(hipMemcpyAsync(R.pl.h_prow.p + lo, Y->dcsr.d_rowoff.p, (size_t)cnt * 4, hipMemcpyDeviceToHost,
+                                  R.pipe_copy));
+            HIP_OK(hipEventRecord(R.pl.cp[k].e, R.pipe_copy));
             cp_pending[k] = true;
             cbase[j] = base + total;
         }
@@ -253,15 +230,15 @@ int tm_engine::match_batch_pipelined(Replica& R, const uint8_t* topics, const ui
     for (uint32_t j = 1; j < nch; ++j) {
         const uint32_t lo = j * PIPE_CHUNK, cnt = std::min(n - lo, PIPE_CHUNK), add = (uint32_t)cbase[j];
         par_chunks(cnt, [&](size_t i0, size_t i1) {
-            for (size_t i = i0; i < i1; ++i) R.h_prow[lo + i] += add;
+            for (size_t i = i0; i < i1; ++i) R.pl.h_prow.p[lo + i] += add;
         });
     }
     const uint64_t total = cbase[nch];
-    R.h_prow[n] = (uint32_t)total;
+    R.pl.h_prow.p[n] = (uint32_t)total;
     out->n_topics = n;
     out->n_matches = total;
-    out->row_offsets = R.h_prow;
-    out->filter_ids = total ? R.h_pids : R.h_prow;
+    out->row_offsets = R.pl.h_prow.p;
+    out->filter_ids = total ? R.pl.h_pids.p : R.pl.h_prow.p;
     return TM_OK;
 }
 

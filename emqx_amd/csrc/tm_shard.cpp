@@ -57,6 +57,7 @@
 
 #include "../../include/emqx_tm.h"
 #include "tm_internal.hpp"
+#include "tm_buffers.hpp"
 
 using namespace etm;
 
@@ -71,44 +72,9 @@ namespace {
         }                                                                            \
     } while (0)
 
-// device buffer on a fixed device, growing only
+// device buffer on a fixed device (dev), growing only
 template <class T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-    int reserve(size_t n) {
-        if (n <= cap && p) return TM_OK;
-        const size_t nc = std::max<size_t>(n + n / 4, 256);
-        SH_HIP(hipSetDevice(dev));
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        SH_HIP(hipMalloc((void**)&p, nc * sizeof(T)));
-        cap = nc;
-        return TM_OK;
-    }
-    void release() {
-        if (p) {
-            (void)hipSetDevice(dev);
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        cap = 0;
-    }
-};
-
-template <class T>
-int host_pinned(T*& p, size_t& cap, size_t n) {
-    if (n <= cap && p) return TM_OK;
-    const size_t nc = std::max<size_t>(n + n / 4, 1024);
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    SH_HIP(hipHostMalloc((void**)&p, nc * sizeof(T), hipHostMallocPortable));
-    cap = nc;
-    return TM_OK;
-}
+using ShardBuf = DevBuf<T, 256>;
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -156,27 +122,16 @@ uint8_t open_link(int a, int b, const std::string& mode) {
 struct Slice {
     uint32_t lo = 0, n = 0;        // publishes [lo, lo + n) of the batch
     uint64_t nwords = 0;
-    DBuf<uint32_t> words, toff, owner, cnt, wcnt, cnt_off, cnt_bs, w_off, w_bs, segs, order, ptoff, pwords;
-    DBuf<uint8_t> tflags, ptflags;
-    uint32_t* h_segs = nullptr;    // the last step's partition counts (read back with its wait)
-    size_t ch_segs = 0;
+    ShardBuf<uint32_t> words, toff, owner, cnt, wcnt, cnt_off, cnt_bs, w_off, w_bs, segs, order, ptoff, pwords;
+    ShardBuf<uint8_t> tflags, ptflags;
+    PortableBuf<uint32_t> h_segs;   // the last step's partition counts (read back with its wait)
     std::vector<uint32_t> seg;     // the plan: [0..G] first publish of each owner's part, [G+1..2G+1] first word
 
     void on(int d) {
-        for (DBuf<uint32_t>* x : {&words, &toff, &owner, &cnt, &wcnt, &cnt_off, &cnt_bs, &w_off, &w_bs, &segs, &order,
-                                  &ptoff, &pwords})
+        for (ShardBuf<uint32_t>* x : {&words, &toff, &owner, &cnt, &wcnt, &cnt_off, &cnt_bs, &w_off, &w_bs, &segs,
+                                      &order, &ptoff, &pwords})
             x->dev = d;
         tflags.dev = ptflags.dev = d;
-    }
-    void release() {
-        for (DBuf<uint32_t>* x : {&words, &toff, &owner, &cnt, &wcnt, &cnt_off, &cnt_bs, &w_off, &w_bs, &segs, &order,
-                                  &ptoff, &pwords})
-            x->release();
-        tflags.release();
-        ptflags.release();
-        if (h_segs) (void)hipHostFree(h_segs);
-        h_segs = nullptr;
-        ch_segs = 0;
     }
     uint32_t part_n(uint32_t j) const { return seg[j + 1] - seg[j]; }
     uint32_t part_w(uint32_t G, uint32_t j) const { return seg[G + 2 + j] - seg[G + 1 + j]; }
@@ -188,52 +143,29 @@ struct tm_sharded_batch {
     // the publishes, rebased (re-planned if the dictionary grew), in pinned
     // memory: the tokenisers' uploads run at the DMA's rate, not through the
     // runtime's staging of pageable memory
-    uint8_t* bytes = nullptr;
-    uint64_t* offs = nullptr;
-    size_t c_bytes = 0, c_offs = 0;
+    PortableBuf<uint8_t> bytes;
+    PortableBuf<uint64_t> offs;
     std::vector<Slice> src;               // G slices (G > 1)
     std::vector<tm_batch*> part;          // shard j's part batch (its engine)
     std::vector<PartBuffers> pb;
     std::vector<uint32_t> pn;             // shard j: publishes it walks
     std::vector<uint64_t> pw;             //          their words
     std::vector<uint32_t> R, W;           // [i * G + j]: where slice i's part lands in shard j's batch
-    uint32_t* h_close = nullptr;          // pinned: shard j's closing word offset
-    size_t ch_close = 0;
-    std::vector<uint8_t*> bounce;         // staged links: [i * G + j] pinned [toff | words | tflags]
-    std::vector<size_t> cbounce;
+    PortableBuf<uint32_t> h_close;      // pinned: shard j's closing word offset
+    std::vector<PortableBuf<uint8_t>> bounce;   // staged links: [i * G + j] pinned [toff | words | tflags]
     // publish-order CSR with global ids on the home device (built on request)
-    DBuf<uint32_t> counts_p, ids_p, gorder, counts_o, src_off, src_bs, dst_off, dst_bs, rowg, out;
-    std::vector<DBuf<uint32_t>> xcnt, xids;
+    ShardBuf<uint32_t> counts_p, ids_p, gorder, counts_o, src_off, src_bs, dst_off, dst_bs, rowg, out;
+    std::vector<ShardBuf<uint32_t>> xcnt, xids;
     std::vector<uint64_t> mseg;           // first match of each part (+ total), in shard order
     uint64_t total = 0;
     bool done = false;
     bool ordered = false;
-    uint32_t *h_row = nullptr, *h_ids = nullptr;
-    size_t ch_row = 0, ch_ids = 0;
+    PortableBuf<uint32_t> h_row, h_ids;
     tm_batch_stats st{};
     float ms_partition = 0, ms_exchange = 0, ms_step = 0, ms_unpartition = 0;
     float ms_stage = 0, ms_plan = 0;      // the last prepare: bytes into pinned memory; the plan (uploads, tokenisers)
     uint32_t host_waits = 0;
-
-    void release() {
-        for (auto& sl : src) sl.release();
-        for (DBuf<uint32_t>* b : {&counts_p, &ids_p, &gorder, &counts_o, &src_off, &src_bs, &dst_off, &dst_bs, &rowg,
-                                  &out})
-            b->release();
-        for (auto& x : xcnt) x.release();
-        for (auto& x : xids) x.release();
-        for (uint8_t* p : bounce)
-            if (p) (void)hipHostFree(p);
-        bounce.clear();
-        for (uint32_t* h : {h_row, h_ids, h_close})
-            if (h) (void)hipHostFree(h);
-        h_row = h_ids = h_close = nullptr;
-        if (bytes) (void)hipHostFree(bytes);
-        if (offs) (void)hipHostFree(offs);
-        bytes = nullptr;
-        offs = nullptr;
-        c_bytes = c_offs = 0;
-    }
+    // (a batch is deleted whole: its buffers go with it, each on its device)
 };
 
 struct tm_sharded {
@@ -243,7 +175,7 @@ struct tm_sharded {
     int home = -1;
     hipStream_t s = nullptr;                 // home device: the step's join, the on-request reorder
     std::vector<hipStream_t> ss;             // shard g's device: its slice's partition
-    std::vector<hipEvent_t> ev_p0, ev_p1, ev_x0, ev_x1, ev_done;   // per shard, on its device
+    std::vector<Event> ev_p0, ev_p1, ev_x0, ev_x1, ev_done;   // per shard, on its device
     std::vector<uint8_t> link;               // [i * G + j]: TM_LINK_*
     std::mutex mu;                           // one step (and one mutation) at a time
     tm_sharded_batch* last = nullptr;
@@ -318,18 +250,18 @@ struct tm_sharded {
     int plan(tm_sharded_batch* b, const uint64_t* uoffs = nullptr, const TokStaged* st = nullptr) {
         int rc;
         const uint32_t n = b->n;
-        const uint8_t* bytes = b->bytes;
+        const uint8_t* bytes = b->bytes.p;
         // the bytes of topics [lo, hi) and where they start in b->bytes
         auto span = [&](uint32_t lo, uint32_t hi, uint64_t& at) -> uint64_t {
-            at = st ? uoffs[lo] - uoffs[0] : b->offs[lo];
-            return (st ? uoffs[hi] - uoffs[0] : b->offs[hi]) - at;
+            at = st ? uoffs[lo] - uoffs[0] : b->offs.p[lo];
+            return (st ? uoffs[hi] - uoffs[0] : b->offs.p[hi]) - at;
         };
         auto tokenize = [&](uint32_t i, uint32_t lo, uint32_t cnt, uint32_t* w, uint64_t wcap, uint32_t* toff,
                             uint8_t* tfl, uint64_t* nw) {
-            if (!st) return tm_tokenize_device(sh[i], bytes, b->offs + lo, cnt, w, wcap, toff, tfl, nw);
+            if (!st) return tm_tokenize_device(sh[i], bytes, b->offs.p + lo, cnt, w, wcap, toff, tfl, nw);
             uint64_t at;
             const uint64_t nb = span(lo, lo + cnt, at);
-            return tokenize_device_staged(sh[i], bytes, b->offs + lo, cnt, at, nb, lo, *st, w, wcap, toff, tfl, nw);
+            return tokenize_device_staged(sh[i], bytes, b->offs.p + lo, cnt, at, nb, lo, *st, w, wcap, toff, tfl, nw);
         };
         b->dict_words = dict_words();
         b->done = b->ordered = false;
@@ -369,7 +301,7 @@ struct tm_sharded {
                 (r = S.w_bs.reserve(scan_block_count(gb) + 1)) || (r = S.segs.reserve(2 * ((size_t)G + 1))) ||
                 (r = S.order.reserve(std::max<size_t>(S.n, 1))) || (r = S.ptoff.reserve((size_t)S.n + G)) ||
                 (r = S.ptflags.reserve(std::max<size_t>(S.n, 1))) ||
-                (r = host_pinned(S.h_segs, S.ch_segs, 2 * ((size_t)G + 1)))) {
+                (r = S.h_segs.reserve(2 * ((size_t)G + 1)))) {
                 rcs[i] = r;
                 return;
             }
@@ -384,14 +316,14 @@ struct tm_sharded {
             if (hipSetDevice(dev[i]) != hipSuccess) { rcs[i] = TM_EIO; return; }
             const PartArgs a = part_args(S);
             if ((r = enqueue_counts(S, a, ss[i]))) { rcs[i] = r; return; }
-            if (hipMemcpyAsync(S.h_segs, S.segs.p, 2 * ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, ss[i]) !=
+            if (hipMemcpyAsync(S.h_segs.p, S.segs.p, 2 * ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, ss[i]) !=
                     hipSuccess ||
                 hipStreamSynchronize(ss[i]) != hipSuccess) {
                 snprintf(error_buf(), 512, "partition plan of slice %u failed", i);
                 rcs[i] = TM_EIO;
                 return;
             }
-            S.seg.assign(S.h_segs, S.h_segs + 2 * ((size_t)G + 1));
+            S.seg.assign(S.h_segs.p, S.h_segs.p + 2 * ((size_t)G + 1));
             if (S.seg[G] != S.n || S.seg[2 * G + 1] != nw) {
                 snprintf(error_buf(), 512, "partition of slice %u lost publishes: %u of %u, %u of %llu words", i,
                          S.seg[G], S.n, S.seg[2 * G + 1], (unsigned long long)nw);
@@ -422,20 +354,19 @@ struct tm_sharded {
             b->pn[j] = (uint32_t)rn;
             b->pw[j] = rw;
         }
-        if ((rc = host_pinned(b->h_close, b->ch_close, G))) return rc;
+        if ((rc = b->h_close.reserve(G))) return rc;
         for (uint32_t j = 0; j < G; ++j) {
-            b->h_close[j] = (uint32_t)b->pw[j];
+            b->h_close.p[j] = (uint32_t)b->pw[j];
             if ((rc = part_batch_buffers(sh[j], &b->part[j], b->pn[j], b->pw[j], &b->pb[j]))) return rc;
         }
         // staged links bounce through pinned host memory: [toff | words | tflags]
-        b->bounce.resize((size_t)G * G, nullptr);
-        b->cbounce.resize((size_t)G * G, 0);
+        b->bounce.resize((size_t)G * G);
         for (uint32_t i = 0; i < G; ++i)
             for (uint32_t j = 0; j < G; ++j) {
                 if (link[i * G + j] != TM_LINK_STAGED || !b->src[i].n) continue;
                 const Slice& S = b->src[i];
                 const size_t need = (size_t)S.part_n(j) * 5 + (size_t)S.part_w(G, j) * 4 + 16;
-                if ((rc = host_pinned(b->bounce[i * G + j], b->cbounce[i * G + j], need))) return rc;
+                if ((rc = b->bounce[i * G + j].reserve(need))) return rc;
             }
         return TM_OK;
     }
@@ -452,7 +383,7 @@ struct tm_sharded {
             for (uint32_t i = 0; i < G; ++i) {
                 Slice& S = b->src[i];
                 SH_HIP(hipSetDevice(dev[i]));
-                SH_HIP(hipEventRecord(ev_p0[i], ss[i]));
+                SH_HIP(hipEventRecord(ev_p0[i].e, ss[i]));
                 if (S.n) {
                     PartArgs a = part_args(S);
                     a.tbase = S.lo;
@@ -467,11 +398,11 @@ struct tm_sharded {
                     }
                     if ((rc = enqueue_counts(S, a, ss[i]))) return rc;
                     SH_HIP(launch_part_scatter(a, ss[i]));
-                    SH_HIP(hipMemcpyAsync(S.h_segs, S.segs.p, 2 * ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, ss[i]));
+                    SH_HIP(hipMemcpyAsync(S.h_segs.p, S.segs.p, 2 * ((size_t)G + 1) * 4, hipMemcpyDeviceToHost, ss[i]));
                     for (uint32_t j = 0; j < G; ++j) {   // staged links: the part goes out to pinned memory
                         if (link[i * G + j] != TM_LINK_STAGED) continue;
                         const uint32_t pn = S.part_n(j), pw = S.part_w(G, j);
-                        uint8_t* bb = b->bounce[i * G + j];
+                        uint8_t* bb = b->bounce[i * G + j].p;
                         if (pn) SH_HIP(hipMemcpyAsync(bb, S.ptoff.p + S.seg[j] + j, (size_t)pn * 4, hipMemcpyDeviceToHost, ss[i]));
                         if (pw) SH_HIP(hipMemcpyAsync(bb + (size_t)pn * 4, S.pwords.p + S.seg[G + 1 + j], (size_t)pw * 4,
                                                       hipMemcpyDeviceToHost, ss[i]));
@@ -479,7 +410,7 @@ struct tm_sharded {
                                                       hipMemcpyDeviceToHost, ss[i]));
                     }
                 }
-                SH_HIP(hipEventRecord(ev_p1[i], ss[i]));
+                SH_HIP(hipEventRecord(ev_p1[i].e, ss[i]));
             }
         }
         // ---- shards: their parts land in their batches, which walk them
@@ -487,8 +418,8 @@ struct tm_sharded {
             const PartBuffers& P = b->pb[j];
             SH_HIP(hipSetDevice(dev[j]));
             if (G > 1) {
-                for (uint32_t i = 0; i < G; ++i) SH_HIP(hipStreamWaitEvent(P.stream, ev_p1[i], 0));
-                SH_HIP(hipEventRecord(ev_x0[j], P.stream));
+                for (uint32_t i = 0; i < G; ++i) SH_HIP(hipStreamWaitEvent(P.stream, ev_p1[i].e, 0));
+                SH_HIP(hipEventRecord(ev_x0[j].e, P.stream));
                 for (uint32_t i = 0; i < G; ++i) {
                     const Slice& S = b->src[i];
                     if (!S.n) continue;
@@ -497,7 +428,7 @@ struct tm_sharded {
                     uint32_t* dwords = P.words + b->W[i * G + j];
                     uint8_t* dflags = P.tflags + b->R[i * G + j];
                     if (link[i * G + j] == TM_LINK_STAGED) {
-                        const uint8_t* bb = b->bounce[i * G + j];
+                        const uint8_t* bb = b->bounce[i * G + j].p;
                         if (pn) SH_HIP(hipMemcpyAsync(dtoff, bb, (size_t)pn * 4, hipMemcpyHostToDevice, P.stream));
                         if (pw) SH_HIP(hipMemcpyAsync(dwords, bb + (size_t)pn * 4, (size_t)pw * 4, hipMemcpyHostToDevice,
                                                       P.stream));
@@ -506,22 +437,22 @@ struct tm_sharded {
                     }
                     // (same device or a peer: written there by the source's scatter)
                 }
-                SH_HIP(hipMemcpyAsync(P.toff + b->pn[j], b->h_close + j, 4, hipMemcpyHostToDevice, P.stream));
-                SH_HIP(hipEventRecord(ev_x1[j], P.stream));
+                SH_HIP(hipMemcpyAsync(P.toff + b->pn[j], b->h_close.p + j, 4, hipMemcpyHostToDevice, P.stream));
+                SH_HIP(hipEventRecord(ev_x1[j].e, P.stream));
             }
             if ((rc = tm_batch_launch(sh[j], b->part[j]))) return rc;
             SH_HIP(hipSetDevice(dev[j]));
-            SH_HIP(hipEventRecord(ev_done[j], P.stream));
+            SH_HIP(hipEventRecord(ev_done[j].e, P.stream));
         }
         // ---- one host wait: the home stream joins every part
         SH_HIP(hipSetDevice(home));
-        for (uint32_t j = 0; j < G; ++j) SH_HIP(hipStreamWaitEvent(s, ev_done[j], 0));
+        for (uint32_t j = 0; j < G; ++j) SH_HIP(hipStreamWaitEvent(s, ev_done[j].e, 0));
         SH_HIP(hipStreamSynchronize(s));
         ++waits;
         if (G > 1)
             for (uint32_t i = 0; i < G; ++i) {   // the device's partition must be the plan
                 const Slice& S = b->src[i];
-                if (S.n && !std::equal(S.seg.begin(), S.seg.end(), S.h_segs)) {
+                if (S.n && !std::equal(S.seg.begin(), S.seg.end(), S.h_segs.p)) {
                     snprintf(error_buf(), 512, "slice %u partitioned differently from its plan", i);
                     return TM_EIO;
                 }
@@ -549,8 +480,8 @@ struct tm_sharded {
         b->ms_partition = b->ms_exchange = 0;
         if (G > 1)
             for (uint32_t g = 0; g < G; ++g) {
-                b->ms_partition = std::max(b->ms_partition, elapsed(ev_p0[g], ev_p1[g]));
-                b->ms_exchange = std::max(b->ms_exchange, elapsed(ev_x0[g], ev_x1[g]));
+                b->ms_partition = std::max(b->ms_partition, elapsed(ev_p0[g].e, ev_p1[g].e));
+                b->ms_exchange = std::max(b->ms_exchange, elapsed(ev_x0[g].e, ev_x1[g].e));
             }
         b->ms_step = (float)(now_ms() - t0);
         b->host_waits = waits;
@@ -569,7 +500,7 @@ struct tm_sharded {
         const double t0 = now_ms();
         const uint32_t n = b->n;
         const uint64_t total = b->total;
-        for (DBuf<uint32_t>* x : {&b->counts_p, &b->ids_p, &b->gorder, &b->counts_o, &b->src_off, &b->src_bs,
+        for (ShardBuf<uint32_t>* x : {&b->counts_p, &b->ids_p, &b->gorder, &b->counts_o, &b->src_off, &b->src_bs,
                                   &b->dst_off, &b->dst_bs, &b->rowg, &b->out})
             x->dev = home;
         if ((rc = b->counts_p.reserve(std::max<size_t>(n, 1))) || (rc = b->ids_p.reserve(std::max<uint64_t>(total, 1))) ||
@@ -649,7 +580,7 @@ int tm_sharded_create(const int32_t* devices, uint32_t n, const tm_config* cfg, 
     s->G = n;
     s->home = devices[0];
     s->ss.assign(n, nullptr);
-    for (auto* v : {&s->ev_p0, &s->ev_p1, &s->ev_x0, &s->ev_x1, &s->ev_done}) v->assign(n, nullptr);
+    for (auto* v : {&s->ev_p0, &s->ev_p1, &s->ev_x0, &s->ev_x1, &s->ev_done}) v->resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         tm_config c = cfg ? *cfg : tm_config{0, 0, 0, 0};
         c.device = devices[i];
@@ -680,7 +611,7 @@ int tm_sharded_create(const int32_t* devices, uint32_t n, const tm_config* cfg, 
         ok = hipSetDevice(devices[g]) == hipSuccess &&
              hipStreamCreateWithFlags(&s->ss[g], hipStreamNonBlocking) == hipSuccess;
         for (auto* v : {&s->ev_p0, &s->ev_p1, &s->ev_x0, &s->ev_x1, &s->ev_done})
-            ok = ok && hipEventCreate(&(*v)[g]) == hipSuccess;
+            ok = ok && (*v)[g].create() == TM_OK;
     }
     if (!ok) {
         (void)hipGetLastError();
@@ -705,8 +636,7 @@ void tm_sharded_destroy(tm_sharded* s) {
             (void)hipStreamSynchronize(s->ss[g]);
             (void)hipStreamDestroy(s->ss[g]);
         }
-        for (auto* v : {&s->ev_p0, &s->ev_p1, &s->ev_x0, &s->ev_x1, &s->ev_done})
-            if ((*v)[g]) (void)hipEventDestroy((*v)[g]);
+        for (auto* v : {&s->ev_p0, &s->ev_p1, &s->ev_x0, &s->ev_x1, &s->ev_done}) (*v)[g].reset();
     }
     for (tm_engine* e : s->sh) tm_destroy(e);
     delete s;
@@ -843,8 +773,8 @@ int tm_sharded_prepare(tm_sharded* s, const uint8_t* topics, const uint64_t* off
         b->done = b->ordered = false;
         const uint64_t base = offsets[0], nbytes = offsets[n] - base;
         const double t0 = now_ms();
-        if ((rc = host_pinned(b->offs, b->c_offs, (size_t)n + 1)) ||
-            (rc = host_pinned(b->bytes, b->c_bytes, nbytes + 16)))   // (+16: the tokenisers' 16-B windows)
+        if ((rc = b->offs.reserve((size_t)n + 1)) ||
+            (rc = b->bytes.reserve(nbytes + 16)))   // (+16: the tokenisers' 16-B windows)
             throw std::bad_alloc();
         // copied by several threads (one would take ~30 ms for a 10M-publish
         // batch), which check every topic on the way: offsets that do not
@@ -863,12 +793,12 @@ int tm_sharded_prepare(tm_sharded* s, const uint8_t* topics, const uint64_t* off
             for (uint64_t it; (it = next.fetch_add(1, std::memory_order_relaxed)) < nbi + noi;) {
                 if (it < nbi) {
                     const uint64_t c0 = it * CB, c1 = std::min(nbytes, c0 + CB);
-                    memcpy(b->bytes + c0, topics + base + c0, c1 - c0);
+                    memcpy(b->bytes.p + c0, topics + base + c0, c1 - c0);
                 } else {
                     const uint64_t o0 = (it - nbi) * CO, o1 = std::min<uint64_t>((uint64_t)n + 1, o0 + CO);
                     bool ok = true;
                     for (uint64_t i = o0; i < o1; ++i) {
-                        b->offs[i] = offsets[i] - base;
+                        b->offs.p[i] = offsets[i] - base;
                         if (i < n) ok &= offsets[i + 1] >= offsets[i] && offsets[i + 1] - offsets[i] <= TM_MAX_TOPIC_LEN;
                     }
                     if (!ok) __atomic_store_n(&bad, true, __ATOMIC_RELEASE);
@@ -931,8 +861,8 @@ int tm_sharded_result(tm_sharded* s, tm_sharded_batch* b, tm_result* out) {
     if (!b->done) return TM_EINVAL;
     std::lock_guard<std::mutex> lk(s->mu);
     int rc;
-    if ((rc = host_pinned(b->h_row, b->ch_row, (size_t)b->n + 1))) return rc;
-    if ((rc = host_pinned(b->h_ids, b->ch_ids, std::max<uint64_t>(b->total, 1)))) return rc;
+    if ((rc = b->h_row.reserve((size_t)b->n + 1))) return rc;
+    if ((rc = b->h_ids.reserve(std::max<uint64_t>(b->total, 1)))) return rc;
     const uint32_t *d_row = nullptr, *d_ids = nullptr;
     try {
         if ((rc = s->device_csr(b, &d_row, &d_ids))) return rc;
@@ -940,17 +870,18 @@ int tm_sharded_result(tm_sharded* s, tm_sharded_batch* b, tm_result* out) {
         return TM_ENOMEM;
     }
     SH_HIP(hipSetDevice(s->home));
-    SH_HIP(hipMemcpyAsync(b->h_row, d_row, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, s->s));
-    if (b->total) SH_HIP(hipMemcpyAsync(b->h_ids, d_ids, b->total * 4, hipMemcpyDeviceToHost, s->s));
+    SH_HIP(hipMemcpyAsync(b->h_row.p, d_row, ((size_t)b->n + 1) * 4, hipMemcpyDeviceToHost, s->s));
+    if (b->total) SH_HIP(hipMemcpyAsync(b->h_ids.p, d_ids, b->total * 4, hipMemcpyDeviceToHost, s->s));
     SH_HIP(hipStreamSynchronize(s->s));
-    if (b->h_row[b->n] != b->total) {
-        snprintf(error_buf(), 512, "inconsistent sharded CSR: %u vs %llu", b->h_row[b->n], (unsigned long long)b->total);
+    if (b->h_row.p[b->n] != b->total) {
+        snprintf(error_buf(), 512, "inconsistent sharded CSR: %u vs %llu", b->h_row.p[b->n],
+                 (unsigned long long)b->total);
         return TM_EIO;
     }
     out->n_topics = b->n;
     out->n_matches = b->total;
-    out->row_offsets = b->h_row;
-    out->filter_ids = b->h_ids;
+    out->row_offsets = b->h_row.p;
+    out->filter_ids = b->h_ids.p;
     return TM_OK;
 }
 
@@ -994,7 +925,6 @@ void tm_sharded_batch_free(tm_sharded* s, tm_sharded_batch* b) {
             if (b->part[g]) tm_batch_free(s->sh[g], b->part[g]);
         if (s->last == b) s->last = nullptr;
     }
-    b->release();
     delete b;
 }
 

@@ -144,26 +144,26 @@ int tm_engine::sync_shared(Replica& R) {
     if (R.shared_gen == shared_gen) return TM_OK;
     const size_t sn = shared_nn, ns = h_gupd.size();
     int rc;
-    if ((rc = dev_reserve(R.d_goff, R.c_goff, sn + 1))) return rc;
-    if ((rc = dev_reserve(R.d_gcnt, R.c_gcnt, std::max<size_t>(sn, 1)))) return rc;
-    if ((rc = dev_reserve(R.d_gruns, R.c_gruns, std::max<size_t>(h_gruns.size(), 1)))) return rc;
-    if ((rc = dev_reserve(R.d_gmem, R.c_gmem, std::max<size_t>(h_gmem.size(), 1)))) return rc;
-    if ((rc = dev_reserve(R.d_gupd, R.c_gupd, std::max<size_t>(ns, 1)))) return rc;
-    if (ns > R.c_gslots || !R.d_gslots) {   // grown with the cursors kept; new slots start zeroed (epoch 0: never owned)
-        const size_t old = R.d_gslots ? R.c_gslots : 0;
-        if ((rc = dev_reserve(R.d_gslots, R.c_gslots, std::max<size_t>(ns, 1), true, old))) return rc;
-        HIP_OK(hipMemsetAsync(R.d_gslots + old, 0, (R.c_gslots - old) * sizeof(SharedSlot), R.stream));
+    if ((rc = R.tab.d_goff.reserve(sn + 1))) return rc;
+    if ((rc = R.tab.d_gcnt.reserve(std::max<size_t>(sn, 1)))) return rc;
+    if ((rc = R.tab.d_gruns.reserve(std::max<size_t>(h_gruns.size(), 1)))) return rc;
+    if ((rc = R.tab.d_gmem.reserve(std::max<size_t>(h_gmem.size(), 1)))) return rc;
+    if ((rc = R.tab.d_gupd.reserve(std::max<size_t>(ns, 1)))) return rc;
+    if (ns > R.tab.d_gslots.cap || !R.tab.d_gslots.p) {   // grown with the cursors kept; new slots start zeroed (epoch 0: never owned)
+        const size_t old = R.tab.d_gslots.p ? R.tab.d_gslots.cap : 0;
+        if ((rc = R.tab.d_gslots.reserve(std::max<size_t>(ns, 1), true, old))) return rc;
+        HIP_OK(hipMemsetAsync(R.tab.d_gslots.p + old, 0, (R.tab.d_gslots.cap - old) * sizeof(SharedSlot), R.stream));
     }
-    HIP_OK(hipMemcpyAsync(R.d_goff, h_goff.data(), (sn + 1) * 4, hipMemcpyHostToDevice, R.stream));
-    if (sn) HIP_OK(hipMemcpyAsync(R.d_gcnt, h_gcnt.data(), sn, hipMemcpyHostToDevice, R.stream));
+    HIP_OK(hipMemcpyAsync(R.tab.d_goff.p, h_goff.data(), (sn + 1) * 4, hipMemcpyHostToDevice, R.stream));
+    if (sn) HIP_OK(hipMemcpyAsync(R.tab.d_gcnt.p, h_gcnt.data(), sn, hipMemcpyHostToDevice, R.stream));
     if (!h_gruns.empty())
-        HIP_OK(hipMemcpyAsync(R.d_gruns, h_gruns.data(), h_gruns.size() * sizeof(uint4), hipMemcpyHostToDevice,
+        HIP_OK(hipMemcpyAsync(R.tab.d_gruns.p, h_gruns.data(), h_gruns.size() * sizeof(uint4), hipMemcpyHostToDevice,
                               R.stream));
     if (!h_gmem.empty())
-        HIP_OK(hipMemcpyAsync(R.d_gmem, h_gmem.data(), h_gmem.size() * 4, hipMemcpyHostToDevice, R.stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_gmem.p, h_gmem.data(), h_gmem.size() * 4, hipMemcpyHostToDevice, R.stream));
     if (ns) {
-        HIP_OK(hipMemcpyAsync(R.d_gupd, h_gupd.data(), ns * sizeof(uint2), hipMemcpyHostToDevice, R.stream));
-        HIP_OK(launch_shared_fold(R.d_gslots, R.d_gupd, (uint32_t)ns, R.stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_gupd.p, h_gupd.data(), ns * sizeof(uint2), hipMemcpyHostToDevice, R.stream));
+        HIP_OK(launch_shared_fold(R.tab.d_gslots.p, R.tab.d_gupd.p, (uint32_t)ns, R.stream));
     }
     HIP_OK(hipStreamSynchronize(R.stream));
     R.shared_gen = shared_gen;
@@ -184,88 +184,83 @@ int tm_engine::batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_sh
     const uint64_t m64 = b->total;   // match entries (< 2^32: u32 result CSR)
     if (m64 > 0xFFFFFFF0ull) return TM_EOVERFLOW;
     const uint32_t m = (uint32_t)m64;
-    if ((rc = dev_reserve(b->d_gcount, b->c_gcount, (size_t)m + 1))) return rc;
-    if ((rc = dev_reserve(b->d_geoff, b->c_geoff, (size_t)m + 1))) return rc;
-    if ((rc = dev_reserve(b->d_grow, b->c_grow, nn + 1))) return rc;
-    if ((rc = dev_reserve(b->d_gbsums, b->c_gbsums, (size_t)scan_block_count(m) + 1))) return rc;
-    if ((rc = dev_reserve(b->d_gtotal, b->c_gtotal, 1))) return rc;
-    if ((rc = dev_reserve(b->d_gtot64, b->c_gtot64, 1))) return rc;
-    if ((rc = host_reserve(b->h_gtot64, b->ch_gtot64, 1))) return rc;
-    for (hipEvent_t& ev : b->gev)
-        if (!ev) HIP_OK(hipEventCreate(&ev));
-    SharedArgs a{};
-    a.row_off = b->d_rowoff; a.ids = b->d_ids; a.n = n; a.m = m;
-    a.gcnt = R.d_gcnt; a.goff = R.d_goff; a.runs = R.d_gruns; a.mem = R.d_gmem;
-    a.nnodes = shared_nn; a.nruns = (uint32_t)h_gruns.size(); a.nmem = (uint32_t)h_gmem.size();
-    a.nslots = (uint32_t)h_gupd.size(); a.slots = R.d_gslots;
-    a.ecount = b->d_gcount; a.eoff = b->d_geoff; a.bsums = b->d_gbsums; a.total = b->d_gtotal;
-    a.total64 = b->d_gtot64; a.g_rowoff = b->d_grow;
-    a.strategy = o->strategy; a.seed = o->seed;
-    HIP_OK(hipEventRecord(b->gev[0], stream));
-    HIP_OK(hipMemsetAsync(b->d_gtot64, 0, 8, stream));
-    HIP_OK(launch_shared_count(a, stream));
     ScanArgs sa{};
-    sa.count = b->d_gcount; sa.row_off = b->d_geoff; sa.block_sums = b->d_gbsums; sa.n = m;
+    if ((rc = b->sh.es.reserve(m, nn, sa))) return rc;
+    if ((rc = b->sh.d_gtot64.reserve(1))) return rc;
+    if ((rc = b->sh.h_gtot64.reserve(1))) return rc;
+    for (Event& ev : b->sh.gev)
+        if ((rc = ev.create())) return rc;
+    SharedArgs a{};
+    a.row_off = b->dcsr.d_rowoff.p; a.ids = b->dcsr.d_ids.p; a.n = n; a.m = m;
+    a.gcnt = R.tab.d_gcnt.p; a.goff = R.tab.d_goff.p; a.runs = R.tab.d_gruns.p; a.mem = R.tab.d_gmem.p;
+    a.nnodes = shared_nn; a.nruns = (uint32_t)h_gruns.size(); a.nmem = (uint32_t)h_gmem.size();
+    a.nslots = (uint32_t)h_gupd.size(); a.slots = R.tab.d_gslots.p;
+    a.ecount = b->sh.es.count.p; a.eoff = b->sh.es.eoff.p; a.bsums = b->sh.es.bsums.p; a.total = b->sh.es.total.p;
+    a.total64 = b->sh.d_gtot64.p; a.g_rowoff = b->sh.es.row.p;
+    a.strategy = o->strategy; a.seed = o->seed;
+    HIP_OK(hipEventRecord(b->sh.gev[0].e, stream));
+    HIP_OK(hipMemsetAsync(b->sh.d_gtot64.p, 0, 8, stream));
+    HIP_OK(launch_shared_count(a, stream));
     if (m) {
-        HIP_OK(launch_scan(sa, stream, b->d_gtotal));
+        HIP_OK(launch_scan(sa, stream, b->sh.es.total.p));
     } else {
-        HIP_OK(hipMemsetAsync(b->d_gtotal, 0, 4, stream));
+        HIP_OK(hipMemsetAsync(b->sh.es.total.p, 0, 4, stream));
     }
     HIP_OK(launch_shared_rows(a, stream));
-    HIP_OK(hipEventRecord(b->gev[1], stream));
-    HIP_OK(hipMemcpyAsync(b->h_gtot64, b->d_gtot64, 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipEventRecord(b->sh.gev[1].e, stream));
+    HIP_OK(hipMemcpyAsync(b->sh.h_gtot64.p, b->sh.d_gtot64.p, 8, hipMemcpyDeviceToHost, stream));
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->h_gtot64[0];
+    const uint64_t total = b->sh.h_gtot64.p[0];
     if (total > 0xFFFFFFF0ull) return TM_EOVERFLOW;   // the u32 scan wrapped: nothing of it is used
     float ms = 0.f, ms2 = 0.f;
     if (!counts_only) {
-        if ((rc = dev_reserve(b->d_gfid, b->c_gfid, std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = dev_reserve(b->d_ggrp, b->c_ggrp, std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = dev_reserve(b->d_gsub, b->c_gsub, std::max<uint64_t>(total, 1)))) return rc;
+        if ((rc = b->sh.d_gfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
+        if ((rc = b->sh.d_ggrp.reserve(std::max<uint64_t>(total, 1)))) return rc;
+        if ((rc = b->sh.d_gsub.reserve(std::max<uint64_t>(total, 1)))) return rc;
         if (o->strategy == TM_SHARED_HASH && n) {
-            if ((rc = dev_reserve(b->d_gkeys, b->c_gkeys, nn))) return rc;
-            if ((rc = host_reserve(b->h_gkeys, b->ch_gkeys, nn))) return rc;
-            memcpy(b->h_gkeys, o->keys, (size_t)n * 4);
-            HIP_OK(hipMemcpyAsync(b->d_gkeys, b->h_gkeys, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-            a.keys = b->d_gkeys;
+            if ((rc = b->sh.d_gkeys.reserve(nn))) return rc;
+            if ((rc = b->sh.h_gkeys.reserve(nn))) return rc;
+            memcpy(b->sh.h_gkeys.p, o->keys, (size_t)n * 4);
+            HIP_OK(hipMemcpyAsync(b->sh.d_gkeys.p, b->sh.h_gkeys.p, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+            a.keys = b->sh.d_gkeys.p;
         }
-        a.out_fid = b->d_gfid; a.out_grp = b->d_ggrp; a.out_sub = b->d_gsub; a.cap = total;
-        HIP_OK(hipEventRecord(b->gev[2], stream));
+        a.out_fid = b->sh.d_gfid.p; a.out_grp = b->sh.d_ggrp.p; a.out_sub = b->sh.d_gsub.p; a.cap = total;
+        HIP_OK(hipEventRecord(b->sh.gev[2].e, stream));
         if (total) HIP_OK(launch_shared_pick(a, stream));
-        HIP_OK(hipEventRecord(b->gev[3], stream));
+        HIP_OK(hipEventRecord(b->sh.gev[3].e, stream));
     }
     out->n_topics = n;
     out->n_deliveries = total;
     if (o->flags & TM_SHARED_DEVICE) {
         HIP_OK(hipStreamSynchronize(stream));
     } else {
-        if ((rc = host_reserve(b->h_grow, b->ch_grow, nn + 1))) return rc;
-        HIP_OK(hipMemcpyAsync(b->h_grow, b->d_grow, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
+        if ((rc = b->sh.h_grow.reserve(nn + 1))) return rc;
+        HIP_OK(hipMemcpyAsync(b->sh.h_grow.p, b->sh.es.row.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
         if (!counts_only) {
-            if ((rc = host_reserve(b->h_gfid, b->ch_gfid, std::max<uint64_t>(total, 1)))) return rc;
-            if ((rc = host_reserve(b->h_ggrp, b->ch_ggrp, std::max<uint64_t>(total, 1)))) return rc;
-            if ((rc = host_reserve(b->h_gsub, b->ch_gsub, std::max<uint64_t>(total, 1)))) return rc;
+            if ((rc = b->sh.h_gfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
+            if ((rc = b->sh.h_ggrp.reserve(std::max<uint64_t>(total, 1)))) return rc;
+            if ((rc = b->sh.h_gsub.reserve(std::max<uint64_t>(total, 1)))) return rc;
             if (total) {
-                HIP_OK(hipMemcpyAsync(b->h_gfid, b->d_gfid, total * 4, hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipMemcpyAsync(b->h_ggrp, b->d_ggrp, total * 4, hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipMemcpyAsync(b->h_gsub, b->d_gsub, total * 4, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpyAsync(b->sh.h_gfid.p, b->sh.d_gfid.p, total * 4, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpyAsync(b->sh.h_ggrp.p, b->sh.d_ggrp.p, total * 4, hipMemcpyDeviceToHost, stream));
+                HIP_OK(hipMemcpyAsync(b->sh.h_gsub.p, b->sh.d_gsub.p, total * 4, hipMemcpyDeviceToHost, stream));
             }
         }
         HIP_OK(hipStreamSynchronize(stream));
-        if (b->h_grow[n] != total) {
-            snprintf(last_error(), 512, "inconsistent shared delivery CSR: %u vs %llu", b->h_grow[n],
+        if (b->sh.h_grow.p[n] != total) {
+            snprintf(last_error(), 512, "inconsistent shared delivery CSR: %u vs %llu", b->sh.h_grow.p[n],
                      (unsigned long long)total);
             return TM_EIO;
         }
     }
-    HIP_OK(hipEventElapsedTime(&ms, b->gev[0], b->gev[1]));
-    if (!counts_only) HIP_OK(hipEventElapsedTime(&ms2, b->gev[2], b->gev[3]));
+    HIP_OK(hipEventElapsedTime(&ms, b->sh.gev[0].e, b->sh.gev[1].e));
+    if (!counts_only) HIP_OK(hipEventElapsedTime(&ms2, b->sh.gev[2].e, b->sh.gev[3].e));
     out->kernel_ms = ms + ms2;
     const bool dev = o->flags & TM_SHARED_DEVICE;
-    out->row_offsets = dev ? b->d_grow : b->h_grow;
-    out->filter_ids = counts_only ? nullptr : dev ? b->d_gfid : b->h_gfid;
-    out->groups = counts_only ? nullptr : dev ? b->d_ggrp : b->h_ggrp;
-    out->subscribers = counts_only ? nullptr : dev ? b->d_gsub : b->h_gsub;
+    out->row_offsets = dev ? b->sh.es.row.p : b->sh.h_grow.p;
+    out->filter_ids = counts_only ? nullptr : dev ? b->sh.d_gfid.p : b->sh.h_gfid.p;
+    out->groups = counts_only ? nullptr : dev ? b->sh.d_ggrp.p : b->sh.h_ggrp.p;
+    out->subscribers = counts_only ? nullptr : dev ? b->sh.d_gsub.p : b->sh.h_gsub.p;
     return TM_OK;
 }
 

@@ -5,10 +5,11 @@
 bool tm_engine::upload_pending(const Replica& R) {
     if (full_dirty || !dirty.empty() || R.d_nslots != slots.size() || needs_repack()) return true;
     if (full_f_dirty || !dirty_f.empty() || fbytes.size() > R.fbytes_uploaded) return true;
-    if (R.c_foff < nd.size() || R.c_flen < nd.size() || R.c_fbytes < fbytes.size() + 1) return true;
+    if (R.tab.d_foff.cap < nd.size() || R.tab.d_flen.cap < nd.size() || R.tab.d_fbytes.cap < fbytes.size() + 1)
+        return true;
     if (dev_tok && (R.d_dict_n != dict.keys().size() || R.d_dict_gen != dict.gen() || !dict.dirty().empty() ||
                     dict.tails().size() > R.tails_uploaded || dict.arena().size() > R.arena_uploaded ||
-                    R.c_arena < dict.arena().size() + 1))
+                    R.tab.d_arena.cap < dict.arena().size() + 1))
         return true;
     return false;
 }
@@ -17,7 +18,7 @@ int tm_engine::ensure_delta_idle() {
     for (Replica* R : reps)
         if (R->delta_inflight) {
             HIP_OK(hipSetDevice(R->device));
-            HIP_OK(hipEventSynchronize(R->ev_delta));
+            HIP_OK(hipEventSynchronize(R->tab.ev_delta.e));
             R->delta_inflight = false;
         }
     return TM_OK;
@@ -53,12 +54,12 @@ int tm_engine::sync_device(const Replica* back) {
         blob_off[3] = blob_off[2] + al(k2 * sizeof(uint32_t));
         blob_off[4] = blob_off[3] + al(k2 * sizeof(uint64_t));
         blob_bytes = blob_off[4] + al(k2 * sizeof(uint32_t));
-        if (blob_bytes && (rc = host_reserve(h_dblob, ch_dblob, blob_bytes))) return rc;
-        h_didx = reinterpret_cast<uint32_t*>(h_dblob + blob_off[0]);
-        h_dval = reinterpret_cast<Slot*>(h_dblob + blob_off[1]);
-        h_fidx = reinterpret_cast<uint32_t*>(h_dblob + blob_off[2]);
-        h_foffv = reinterpret_cast<uint64_t*>(h_dblob + blob_off[3]);
-        h_flenv = reinterpret_cast<uint32_t*>(h_dblob + blob_off[4]);
+        if (blob_bytes && (rc = h_dblob.reserve(blob_bytes))) return rc;
+        h_didx = reinterpret_cast<uint32_t*>(h_dblob.p + blob_off[0]);
+        h_dval = reinterpret_cast<Slot*>(h_dblob.p + blob_off[1]);
+        h_fidx = reinterpret_cast<uint32_t*>(h_dblob.p + blob_off[2]);
+        h_foffv = reinterpret_cast<uint64_t*>(h_dblob.p + blob_off[3]);
+        h_flenv = reinterpret_cast<uint32_t*>(h_dblob.p + blob_off[4]);
     }
     if (!slots_full && !dirty.empty()) {
         const size_t k = dirty.size();
@@ -90,11 +91,11 @@ int tm_engine::sync_device(const Replica* back) {
         std::sort(dx.begin(), dx.end());
         dx.erase(std::unique(dx.begin(), dx.end()), dx.end());   // a slot may move twice: scatter it once
         const size_t k = dx.size();
-        if ((rc = host_reserve(h_dxidx, ch_dxidx, k))) return rc;
-        if ((rc = host_reserve(h_dxval, ch_dxval, k))) return rc;
+        if ((rc = h_dxidx.reserve(k))) return rc;
+        if ((rc = h_dxval.reserve(k))) return rc;
         for (size_t i = 0; i < k; ++i) {
-            h_dxidx[i] = dx[i];
-            h_dxval[i] = dict.keys()[dx[i]];
+            h_dxidx.p[i] = dx[i];
+            h_dxval.p[i] = dict.keys()[dx[i]];
         }
     }
     // apply to every replica (different devices run their copies concurrently)
@@ -127,10 +128,10 @@ int tm_engine::sync_device(const Replica* back) {
             // host vectors may be mutated / reallocated right after we return
             HIP_OK(hipStreamSynchronize(R.stream));
         } else if (async[r]) {
-            HIP_OK(hipEventRecord(R.ev_delta, R.stream));
+            HIP_OK(hipEventRecord(R.tab.ev_delta.e, R.stream));
             R.delta_inflight = true;
             if (!R.readers.empty()) {   // own-stream batches launched from now on wait for this upload
-                HIP_OK(hipEventRecord(R.ev_sync, R.stream));
+                HIP_OK(hipEventRecord(R.tab.ev_sync.e, R.stream));
                 ++R.upload_seq;
             }
         }
@@ -146,42 +147,43 @@ int tm_engine::upload_to(Replica& R, bool slots_full, bool keys_full, size_t nn,
     // tables change under the walks of this replica's own-stream batches in
     // flight: the uploads wait for them on the device, or on the host when
     // a table is reallocated (its old buffer is freed here)
-    const bool realloc = R.d_nslots != slots.size() || R.c_foff < nn || R.c_flen < nn ||
-                         R.c_fbytes < fbytes.size() + 1 ||
-                         (dev_tok && (R.d_dict_n != dict.keys().size() || R.c_tail < dict.tails().size() + 1 ||
-                                      R.c_arena < dict.arena().size() + 1));
+    const bool realloc = R.d_nslots != slots.size() || R.tab.d_foff.cap < nn || R.tab.d_flen.cap < nn ||
+                         R.tab.d_fbytes.cap < fbytes.size() + 1 ||
+                         (dev_tok && (R.d_dict_n != dict.keys().size() || R.tab.d_tail.cap < dict.tails().size() + 1 ||
+                                      R.tab.d_arena.cap < dict.arena().size() + 1));
     for (tm_batch* r : R.readers)
         if (r->launched && !r->done) {   // (a waited batch has finished reading them)
             if (realloc) {
                 HIP_OK(hipStreamSynchronize(r->own));
                 continue;
             }
-            if (!r->ev_read) HIP_OK(hipEventCreateWithFlags(&r->ev_read, hipEventDisableTiming));
-            HIP_OK(hipEventRecord(r->ev_read, r->own));
-            HIP_OK(hipStreamWaitEvent(stream, r->ev_read, 0));
+            if ((rc = r->walk.ev_read.create(hipEventDisableTiming))) return rc;
+            HIP_OK(hipEventRecord(r->walk.ev_read.e, r->own));
+            HIP_OK(hipStreamWaitEvent(stream, r->walk.ev_read.e, 0));
         }
     // the delta blob, in one copy (the scatters below read their parts)
     if (blob_bytes) {
-        if ((rc = dev_reserve(R.d_dblob, R.cd_dblob, blob_bytes))) return rc;
-        HIP_OK(hipMemcpyAsync(R.d_dblob, h_dblob, blob_bytes, hipMemcpyHostToDevice, stream));
+        if ((rc = R.tab.d_dblob.reserve(blob_bytes))) return rc;
+        HIP_OK(hipMemcpyAsync(R.tab.d_dblob.p, h_dblob.p, blob_bytes, hipMemcpyHostToDevice, stream));
         async_used = true;
     }
     // edge hash
     bool full = slots_full;
     if (R.d_nslots != slots.size()) {
-        dev_free(R.d_slots);
-        HIP_OK(hipMalloc((void**)&R.d_slots, slots.size() * sizeof(Slot)));
+        R.tab.d_slots.reset();
+        if ((rc = R.tab.d_slots.alloc(slots.size()))) return rc;
         R.d_nslots = slots.size();
         full = true;
     }
     if (full) {
         pageable_used = true;
-        HIP_OK(hipMemcpyAsync(R.d_slots, slots.data(), slots.size() * sizeof(Slot), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_slots.p, slots.data(), slots.size() * sizeof(Slot), hipMemcpyHostToDevice,
+                              stream));
         ++uploads_full;
     } else if (!dirty.empty()) {
         const size_t k = dirty.size();
-        HIP_OK(launch_scatter_slots(R.d_slots, reinterpret_cast<const uint32_t*>(R.d_dblob + blob_off[0]),
-                                    reinterpret_cast<const Slot*>(R.d_dblob + blob_off[1]), (uint32_t)k, stream));
+        HIP_OK(launch_scatter_slots(R.tab.d_slots.p, reinterpret_cast<const uint32_t*>(R.tab.d_dblob.p + blob_off[0]),
+                                    reinterpret_cast<const Slot*>(R.tab.d_dblob.p + blob_off[1]), (uint32_t)k, stream));
         ++uploads_delta;
         delta_slots += k;
         async_used = true;
@@ -192,21 +194,21 @@ int tm_engine::upload_to(Replica& R, bool slots_full, bool keys_full, size_t nn,
     // next upload reuses it)
     size_t app_need = 0, app_used = 0;
     {
-        const uint64_t fb_from = R.c_fbytes < fbytes.size() + 1 ? 0 : R.fbytes_uploaded;
+        const uint64_t fb_from = R.tab.d_fbytes.cap < fbytes.size() + 1 ? 0 : R.fbytes_uploaded;
         app_need += fbytes.size() > fb_from ? fbytes.size() - fb_from : 0;
         if (dev_tok) {
-            const size_t t_from = R.c_tail < dict.tails().size() + 1 ? 0 : R.tails_uploaded;
-            const size_t a_from = R.c_arena < dict.arena().size() + 1 ? 0 : R.arena_uploaded;
+            const size_t t_from = R.tab.d_tail.cap < dict.tails().size() + 1 ? 0 : R.tails_uploaded;
+            const size_t a_from = R.tab.d_arena.cap < dict.arena().size() + 1 ? 0 : R.arena_uploaded;
             if (dict.tails().size() > t_from) app_need += (dict.tails().size() - t_from) * sizeof(DictTail) + 16;
             if (dict.arena().size() > a_from) app_need += dict.arena().size() - a_from + 16;
         }
     }
     const bool app_pinned = app_need > 0 && app_need <= APP_MAX;
-    if (app_pinned && (rc = host_reserve(R.h_app, R.ch_app, app_need))) return rc;
+    if (app_pinned && (rc = R.tab.h_app.reserve(app_need))) return rc;
     // a host range -> device, through the pinned staging when it fits
     auto h2d_tail = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        if (app_pinned && app_used + bytes <= R.ch_app) {
-            uint8_t* stg = R.h_app + app_used;
+        if (app_pinned && app_used + bytes <= R.tab.h_app.cap) {
+            uint8_t* stg = R.tab.h_app.p + app_used;
             memcpy(stg, src, bytes);
             app_used = (app_used + bytes + 15) & ~(size_t)15;
             async_used = true;
@@ -221,29 +223,30 @@ int tm_engine::upload_to(Replica& R, bool slots_full, bool keys_full, size_t nn,
     // costs a full copy, a host wait for the batches reading the old one
     // and a new capture of every batch's launch graph -- its address is an
     // argument)
-    if (R.c_foff < nn || R.c_flen < nn) {
-        if ((rc = dev_reserve(R.d_foff, R.c_foff, 2 * nn))) return rc;
-        if ((rc = dev_reserve(R.d_flen, R.c_flen, 2 * nn))) return rc;
+    if (R.tab.d_foff.cap < nn || R.tab.d_flen.cap < nn) {
+        if ((rc = R.tab.d_foff.reserve(2 * nn))) return rc;
+        if ((rc = R.tab.d_flen.reserve(2 * nn))) return rc;
         f_full = true;
     }
-    if (R.c_fbytes < fbytes.size() + 1) {
-        if ((rc = dev_reserve(R.d_fbytes, R.c_fbytes, 2 * (fbytes.size() + 1)))) return rc;
+    if (R.tab.d_fbytes.cap < fbytes.size() + 1) {
+        if ((rc = R.tab.d_fbytes.reserve(2 * (fbytes.size() + 1)))) return rc;
         R.fbytes_uploaded = 0;
     }
     if (fbytes.size() > R.fbytes_uploaded) {
-        HIP_OK(h2d_tail(R.d_fbytes + R.fbytes_uploaded, fbytes.data() + R.fbytes_uploaded,
+        HIP_OK(h2d_tail(R.tab.d_fbytes.p + R.fbytes_uploaded, fbytes.data() + R.fbytes_uploaded,
                         fbytes.size() - R.fbytes_uploaded));
         R.fbytes_uploaded = fbytes.size();
     }
     if (f_full) {
         pageable_used = true;
-        HIP_OK(hipMemcpyAsync(R.d_foff, n_foff.data(), nn * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        HIP_OK(hipMemcpyAsync(R.d_flen, n_flen.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_foff.p, n_foff.data(), nn * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_flen.p, n_flen.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     } else if (!dirty_f.empty()) {
         const size_t k = dirty_f.size();
-        HIP_OK(launch_scatter_fmeta(R.d_foff, R.d_flen, reinterpret_cast<const uint32_t*>(R.d_dblob + blob_off[2]),
-                                    reinterpret_cast<const uint64_t*>(R.d_dblob + blob_off[3]),
-                                    reinterpret_cast<const uint32_t*>(R.d_dblob + blob_off[4]), (uint32_t)k, stream));
+        const uint8_t* blob = R.tab.d_dblob.p;
+        HIP_OK(launch_scatter_fmeta(R.tab.d_foff.p, R.tab.d_flen.p, reinterpret_cast<const uint32_t*>(blob + blob_off[2]),
+                                    reinterpret_cast<const uint64_t*>(blob + blob_off[3]),
+                                    reinterpret_cast<const uint32_t*>(blob + blob_off[4]), (uint32_t)k, stream));
         async_used = true;
     }
     if (dev_tok && (rc = sync_dict(R, keys_full, pageable_used, async_used, h2d_tail))) return rc;
