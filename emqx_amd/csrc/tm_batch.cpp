@@ -1034,7 +1034,7 @@ void tm_engine::fill_stats(tm_batch* b) {
 #if TM_PHASE_CYCLES
     // dev build: the tile walk's cycle sums over all waves, one line per batch
     fprintf(stderr, "tm_phase_cycles prologue=%llu loop=%llu readback=%llu sort=%llu ms_match=%.4f\n",
-            b->h_stats[ST_PHASE + 0], b->h_stats[ST_PHASE + 1], b->h_stats[ST_PHASE + 2], b->h_stats[ST_PHASE + 3],
+            b->walk.h_stats[ST_PHASE + 0], b->walk.h_stats[ST_PHASE + 1], b->walk.h_stats[ST_PHASE + 2], b->walk.h_stats[ST_PHASE + 3],
             ms_match);
 #endif
 }

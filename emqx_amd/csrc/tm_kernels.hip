@@ -256,6 +256,14 @@ __device__ __forceinline__ unsigned long long xor_lane64(unsigned long long v, u
     return ((unsigned long long)xor_lane32((uint32_t)(v >> 32), j) << 32) | xor_lane32((uint32_t)v, j);
 }
 
+// Sum of a value over the wave's 64 lanes, wave-uniform (the per-lane values
+// of one tile: far below 2^32 / 64 each).
+__device__ __forceinline__ uint32_t tile_sum(uint32_t v) {
+#pragma unroll
+    for (uint32_t j = 1; j < 64; j <<= 1) v += xor_lane32(v, j);
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
 // Per-wave cycle sums of a tile's four phases (-DTM_PHASE_CYCLES=1, dev builds
 // only: python -m emqx_amd.build --variant phase -DTM_PHASE_CYCLES=1).  The
 // sums leave with the wave's wstats partials and fill_stats prints them.  In
@@ -445,6 +453,58 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
     }
 }
 
+#ifndef TM_PREFETCH_NEXT
+#define TM_PREFETCH_NEXT 2   // 0: a tile's prologue loads its own offsets, flags and words; 1: offsets and flags ahead; 2: the words too
+#endif
+// Next-tile prefetch.  A tile's prologue used to pay two memory latencies in
+// a row (toff[] / tflags[], then the words they locate) for addresses known a
+// tile earlier.  The wave now loads them into registers while the previous
+// tile's epilogue runs: the per-lane offsets and flags right after the
+// frontier loop, the words once the read-back's first wait has brought the
+// offsets in.  The next prologue writes LDS from the registers.
+struct TileAhead {
+    uint32_t off, end, fl;    // toff[t], toff[t + 1], tflags[t] of this lane's topic (0, 0, TF_SLOW: no topic)
+#if TM_PREFETCH_NEXT >= 2
+    uint32_t w[WCAP / 64];    // words wbeg + lane + 64 j of a tile whose words fit the LDS cache
+#endif
+};
+
+template <bool CK>
+__device__ __forceinline__ void ahead_meta(const MatchArgs& a, uint32_t tile, uint32_t tt, TileAhead& p) {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t t = tile * tt + lane;
+    p.off = 0; p.end = 0; p.fl = TF_SLOW;
+    if (lane < tt && t < a.n) {
+        p.off = a.toff[CK_(t, a.n + 1, 4)];
+        p.end = a.toff[CK_(t + 1, a.n + 1, 5)];
+        p.fl = a.tflags[CK_(t, a.n, 6)];
+    }
+}
+
+// the tile's word range, from the lanes of its first and last topic (tile < ntiles: lane 0 has a topic)
+__device__ __forceinline__ void ahead_range(const MatchArgs& a, uint32_t tile, uint32_t tt, const TileAhead& p,
+                                            uint32_t& wbeg, uint32_t& wend) {
+    const uint32_t nv = min(tt, a.n - tile * tt);
+    wbeg = __builtin_amdgcn_readlane(p.off, 0);
+    wend = __builtin_amdgcn_readlane(p.end, nv - 1);
+}
+
+template <bool CK>
+__device__ __forceinline__ void ahead_words(const MatchArgs& a, uint32_t tile, uint32_t tt, TileAhead& p) {
+#if TM_PREFETCH_NEXT >= 2
+    const uint32_t lane = threadIdx.x;
+    uint32_t wbeg, wend;
+    ahead_range(a, tile, tt, p, wbeg, wend);
+    const uint32_t nw = wend - wbeg;
+    if (nw > (uint32_t)WCAP) return;   // read from HBM by the walk itself
+#pragma unroll
+    for (uint32_t j = 0; j < WCAP / 64; ++j) {
+        const uint32_t i = lane + 64 * j;
+        if (i < nw) p.w[j] = a.words[CK_(wbeg + i, a.nwords, 8)];
+    }
+#endif
+}
+
 #ifndef TM_LOG_U
 #define TM_LOG_U 12  // log entries per lane per read-back step, all in flight (4 / 8 / 12 / 16: 5.10 / 5.07 / 5.04 / 5.05 ms)
 #endif
@@ -452,13 +512,16 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
 // to a wave-private log in iteration order (coalesced: one store of <= 64
 // consecutive entries per emission role per iteration), each with its topic
 // lane in a parallel byte log.  The rows are rebuilt in LDS a chunk of whole
-// rows at a time -- the log is streamed (L2-resident: written moments ago)
-// and every entry of a chunk's rows goes to its row's next free place -- and
-// sorted as before.
-template <bool CK, class LT>
+// rows at a time -- the log is streamed (from memory, not from L2: a C2 wave's
+// log is long gone from its XCD's 4 MiB by the time the tile's frontier is
+// empty, the bucket reads of every wave having passed through it since) and
+// every entry of a chunk's rows goes to its row's next free place -- and
+// sorted as before.  ah_words: the next tile's word loads (TM_PREFETCH_NEXT),
+// issued after the first chunk's read-back.
+template <bool CK, class LT, class AW>
 __device__ __forceinline__ void sort_rows_log(const MatchArgs& a, LT& L, bool keep, uint32_t c, uint32_t dst,
                                               unsigned long long* wlog, uint8_t* wlane, uint32_t lcount,
-                                              PhaseClk& pc) {
+                                              PhaseClk& pc, const AW& ah_words) {
     constexpr uint32_t STAGE = LT::STAGE;
     const uint32_t lane = threadIdx.x;
     unsigned long long* stg = reinterpret_cast<unsigned long long*>(L.q);
@@ -514,6 +577,9 @@ __device__ __forceinline__ void sort_rows_log(const MatchArgs& a, LT& L, bool ke
         }
         __syncthreads();
         pc.lap(PH_READBACK);
+        // every load so far has come in, the next tile's offsets with them:
+        // its words go out here, under the sort
+        if (rs == 0) ah_words();
         sort_classes<CK, LT>(a, L, in_chunk, c, pos - p0, dst, free);
         __syncthreads();
         pc.lap(PH_SORT);
@@ -537,11 +603,13 @@ __device__ __forceinline__ void send_to_slow(const MatchArgs& a, bool mine, uint
 // One tile.  IN_LDS: the tile's words are staged in LDS (the common case);
 // otherwise they are read from HBM.  Templated so word reads are plain ds_read
 // or global_load, never flat.
-template <bool CK, bool BIG, bool IN_LDS, class LT>
+// ah_meta / ah_words issue the next tile's loads (TM_PREFETCH_NEXT): each is
+// called exactly once on every way out, ah_meta first.
+template <bool CK, bool BIG, bool IN_LDS, class LT, class AM, class AW>
 __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t0, uint32_t tend, uint32_t wbase,
                                            uint8_t fl, bool valid, unsigned long long& sV, unsigned long long& sH,
                                            unsigned long long& sW, unsigned long long& sM, unsigned long long& sP,
-                                           PhaseClk& pc) {
+                                           PhaseClk& pc, const AM& ah_meta, const AW& ah_words) {
     const uint32_t lane = threadIdx.x;
     const uint32_t t = t0 + lane;
     const uint32_t* wsrc = IN_LDS ? L.words : a.words;
@@ -557,7 +625,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     uint8_t* const wlane =
         reinterpret_cast<uint8_t*>(a.rows + (uint64_t)a.grid * lcap) + (uint64_t)blockIdx.x * lcap;
     uint32_t lcount = 0;
-    uint32_t tV = 0, tH = 0, tW = 0, tP = 0;   // committed only if the tile does not overflow
+    uint32_t tV = 0, tH = 0, tP = 0;   // committed only if the tile does not overflow
     const uint32_t d_me = L.depth[lane];
 
     // ---- level 0: root expansion, one topic per lane
@@ -568,7 +636,6 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
             const bool dollar = fl & TF_DOLLAR;
             tV += 1;
             if (!dollar && (a.root.flags & NF_HASH)) tH += 1;
-            tW += d_me;
             w0 = wsrc[CK_(L.toff[lane], wlim, 9)];
             expand_root(a.root, dollar, d_me, w0, x);
         }
@@ -787,14 +854,25 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     }
     __syncthreads();
     pc.lap(PH_LOOP);
+    ah_meta();
 
     if (qn > 0) {
         // probe stack overflow: every regular topic of the tile goes to the slow path
         send_to_slow<CK>(a, valid && active, t);
+        ah_words();
         return;
     }
-    sV += tV; sH += tH; sW += tW;
-    if (lane == 0) sP += (tP & 0xFFFFFu) | ((unsigned long long)(tP >> 20) << 40);   // probes | iterations << 40
+    // The wave's sums are wave-uniform (scalar registers): a tile's per-lane
+    // counts are added up here, once per tile, rather than carried as five
+    // u64 per lane through every tile and summed at the kernel's end.  (The
+    // topic's word count is read again, not carried through the loop:
+    // depth[] is intact until the read-back.)
+    sV += tile_sum(tV); sH += tile_sum(tH);
+    sW += tile_sum((active && L.depth[lane] > 0) ? L.depth[lane] : 0u);
+    {
+        const uint32_t p = __builtin_amdgcn_readfirstlane(tP);
+        sP += (p & 0xFFFFFu) | ((unsigned long long)(p >> 20) << 40);   // probes | iterations << 40
+    }
     const uint32_t c_me = L.cnt[lane];
     const bool row_ovf = valid && active && c_me > a.row_cap;   // row longer than K
     send_to_slow<CK>(a, row_ovf, t);
@@ -819,15 +897,16 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     const uint32_t dst = base + incl - c;
     pc.lap(PH_SORT);   // the staging reservation counts as staging
     if (fits) {
-        sort_rows_log<CK, LT>(a, L, keep, c, dst, wrows, wlane, lcount, pc);
-    } else if (lane == 0) {
-        atomicOr(&a.ctrl[CTRL_ERR], ERR_STAGING);   // host grows sfids[] and reruns
+        sort_rows_log<CK, LT>(a, L, keep, c, dst, wrows, wlane, lcount, pc, ah_words);
+    } else {
+        if (lane == 0) atomicOr(&a.ctrl[CTRL_ERR], ERR_STAGING);   // host grows sfids[] and reruns
+        ah_words();
     }
     if (keep) {
         a.count[CK_(t, a.n, 16)] = c_me;
         a.src[CK_(t, a.n, 17)] = dst;
-        sM += c_me;
     }
+    sM += __builtin_amdgcn_readfirstlane(tot);   // the kept rows' sizes
     pc.lap(PH_SORT);
     (void)tend;
 }
@@ -864,6 +943,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
     // static round-robin tiles, then tickets for the tail; a ticket is taken at
     // the start of a tile so its latency hides behind the tile's work
     uint32_t tile = blockIdx.x, round = 0;
+#if TM_PREFETCH_NEXT
+    TileAhead nx;
+    if (tile < ntiles) {   // the wave's first tile has nothing to hide behind
+        ahead_meta<CK>(a, tile, tt, nx);
+        ahead_words<CK>(a, tile, tt, nx);
+    }
+#endif
     while (tile < ntiles) {
         // the next tile: round-robin for the first static_rounds, then from a
         // ticket (a contended counter's latency would stall every in-order vmcnt
@@ -876,6 +962,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
         const uint32_t tend = min(t0 + tt, a.n);
         const uint32_t t = t0 + lane;
         const bool valid = lane < tt && t < a.n;
+#if TM_PREFETCH_NEXT
+        // this tile's inputs are in nx, loaded under the previous tile's epilogue
+        uint32_t wbeg, wend;
+        ahead_range(a, tile, tt, nx, wbeg, wend);
+        const bool in_lds = (wend - wbeg) <= (uint32_t)WCAP;
+        const uint32_t my_off = valid ? nx.off : wend;
+        const uint32_t my_end = valid ? nx.end : wend;
+        const uint8_t fl = (uint8_t)nx.fl;
+#if TM_PREFETCH_NEXT >= 2
+        if (in_lds) {
+#pragma unroll
+            for (uint32_t j = 0; j < WCAP / 64; ++j) {
+                const uint32_t i = lane + 64 * j;
+                if (i < wend - wbeg) L.words[CK_(i, WCAP, 7)] = nx.w[j];
+            }
+        }
+#else
+        if (in_lds)
+            for (uint32_t i = lane; i < wend - wbeg; i += 64) L.words[CK_(i, WCAP, 7)] = a.words[CK_(wbeg + i, a.nwords, 8)];
+#endif
+#else
         const uint32_t wbeg = a.toff[CK_(t0, a.n + 1, 2)], wend = a.toff[CK_(tend, a.n + 1, 3)];
         const bool in_lds = (wend - wbeg) <= (uint32_t)WCAP;
         const uint32_t my_off = valid ? a.toff[CK_(t, a.n + 1, 4)] : wend;
@@ -883,25 +990,40 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QC == 384 ? 
         const uint8_t fl = valid ? a.tflags[CK_(t, a.n, 6)] : (uint8_t)TF_SLOW;
         if (in_lds)
             for (uint32_t i = lane; i < wend - wbeg; i += 64) L.words[CK_(i, WCAP, 7)] = a.words[CK_(wbeg + i, a.nwords, 8)];
+#endif
         L.toff[lane] = in_lds ? my_off - wbeg : my_off;
         L.depth[lane] = my_end - my_off;
         L.cnt[lane] = 0;
         __syncthreads();
-        if (in_lds) match_tile<CK, BIG, true>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc);
-        else match_tile<CK, BIG, false>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc);
+        // the tile after this one: round-robin, or the ticket taken above.  Its
+        // loads are issued from inside match_tile, once the frontier is empty;
+        // none when this is the wave's last tile.
+        uint32_t next = ntiles;
+        const auto next_tile = [&]() -> uint32_t {
+            return round + 1 < a.static_rounds
+                       ? blockIdx.x + (round + 1) * gridDim.x
+                       : a.static_rounds * gridDim.x + __builtin_amdgcn_readfirstlane(ticket) * TICKET_GROUPS +
+                             blockIdx.x % TICKET_GROUPS;
+        };
+#if TM_PREFETCH_NEXT
+        const auto ah_meta = [&] {
+            next = next_tile();
+            if (next < ntiles) ahead_meta<CK>(a, next, tt, nx);
+        };
+        const auto ah_words = [&] {
+            if (next < ntiles) ahead_words<CK>(a, next, tt, nx);
+        };
+#else
+        const auto ah_meta = [&] { next = next_tile(); };
+        const auto ah_words = [] {};
+#endif
+        if (in_lds) match_tile<CK, BIG, true>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc, ah_meta, ah_words);
+        else match_tile<CK, BIG, false>(a, L, t0, tend, wbeg, fl, valid, sV, sH, sW, sM, sP, pc, ah_meta, ah_words);
         __syncthreads();
         ++round;
-        tile = round < a.static_rounds
-                   ? blockIdx.x + round * gridDim.x
-                   : a.static_rounds * gridDim.x + __builtin_amdgcn_readfirstlane(ticket) * TICKET_GROUPS +
-                         blockIdx.x % TICKET_GROUPS;
+        tile = next;
     }
 
-    for (int o = 32; o > 0; o >>= 1) {
-        sV += __shfl_xor(sV, o, 64); sH += __shfl_xor(sH, o, 64);
-        sW += __shfl_xor(sW, o, 64); sM += __shfl_xor(sM, o, 64);
-        sP += __shfl_xor(sP, o, 64);
-    }
     if (lane == 0 && a.wstats) {
         // the wave's sums, added up by tm_stats_reduce: ~4,000 waves ending
         // together would queue 6 same-line device atomics each (~30 ns apiece)
