@@ -97,6 +97,16 @@ class SharedDeliveries(C.Structure):
                 ("subscribers", C.POINTER(C.c_uint32)), ("kernel_ms", C.c_float)]
 
 
+class Inboxes(C.Structure):
+    _fields_ = [("n_topics", C.c_uint32), ("n_subscribers", C.c_uint32), ("n_deliveries", C.c_uint64),
+                ("subscribers", C.POINTER(C.c_uint32)), ("inbox_offsets", C.POINTER(C.c_uint32)),
+                ("publishes", C.POINTER(C.c_uint32)), ("filter_ids", C.POINTER(C.c_uint32)),
+                ("kernel_ms", C.c_float), ("passes", C.c_uint32)]
+
+
+TM_INBOX_DEVICE = 1
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -214,6 +224,8 @@ SIGNATURES = {
     "tm_unsubscribe": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32]),
     "tm_subscriber_down": (C.c_int, [P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_batch_dispatch": (C.c_int, [P, P, C.c_uint32, C.POINTER(Deliveries)]),
+    "tm_batch_inboxes": (C.c_int, [P, P, C.c_uint32, C.POINTER(Inboxes)]),
+    "tm_inbox_tile": (C.c_uint32, []),
     "tm_match_routes_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Routes)]),
     "tm_trie_insert_many": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_trie_delete_many": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -27,6 +27,7 @@
  */
 #include <erl_nif.h>
 #include <pthread.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "emqx_tm.h"
@@ -523,6 +524,73 @@ static ERL_NIF_TERM nif_dispatch_batch(ErlNifEnv* env, int argc, const ERL_NIF_T
             row = enif_make_list_cell(env, enif_make_uint(env, d.subscribers[k]), row);
         out = enif_make_list_cell(env, row, out);
     }
+    tm_batch_free(r->e, b);
+    return out;
+}
+
+static int cmp_u32(const void* a, const void* b) {
+    const uint32_t x = *(const uint32_t*)a, y = *(const uint32_t*)b;
+    return x < y ? -1 : x > y;
+}
+
+/* deliver_batch(Engine, [Topic]) -> [{SubId, [{PublishIndex0, Filter}]}]
+ * The deliveries of dispatch_batch grouped by subscriber on the device
+ * (tm_batch_inboxes): SubIds ascending, each with its deliveries in mailbox
+ * order (src/emqx_broker.erl:298-302) -- the list emqx_misc:drain_deliver/1
+ * (src/emqx_misc.erl:128-142) would collect.  The distinct filters are copied
+ * out once (tm_filters_copy) and every delivery shares its filter's binary. */
+static ERL_NIF_TERM nif_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    unsigned n;
+    uint8_t* buf;
+    uint64_t* offs;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !pack_binaries(env, argv[1], &n, &buf, &offs)) return enif_make_badarg(env);
+    tm_batch* b;
+    tm_inboxes ib;
+    packed p;
+    int rc = run_batch(r->e, buf, offs, n, &b);
+    enif_free(buf); enif_free(offs);
+    if (!rc) rc = tm_batch_inboxes(r->e, b, 0, &ib);
+    if (rc) {
+        if (b) tm_batch_free(r->e, b);
+        return err(env, rc);
+    }
+    const uint64_t nd = ib.n_deliveries;
+    uint32_t* uniq = enif_alloc(sizeof(uint32_t) * (nd ? nd : 1));
+    uint32_t nu = 0;
+    if (uniq) {
+        if (nd) memcpy(uniq, ib.filter_ids, sizeof(uint32_t) * nd);
+        qsort(uniq, nd, sizeof(uint32_t), cmp_u32);
+        for (uint64_t q = 0; q < nd; ++q)
+            if (!nu || uniq[nu - 1] != uniq[q]) uniq[nu++] = uniq[q];
+    }
+    ERL_NIF_TERM* term = enif_alloc(sizeof(ERL_NIF_TERM) * (nu ? nu : 1));
+    uint8_t* live = enif_alloc(nu ? nu : 1);
+    rc = (uniq && term && live) ? pack_filters(r->e, uniq, nu, &p) : TM_ENOMEM;
+    if (rc) {
+        enif_free(uniq); enif_free(term); enif_free(live);
+        tm_batch_free(r->e, b);
+        return err(env, rc);
+    }
+    memset(live, 0, nu ? nu : 1);
+    for (uint32_t k = 0; k < p.n; ++k) {
+        term[p.keep[k]] = make_bin(env, p.buf + p.offs[k], p.offs[k + 1] - p.offs[k]);
+        live[p.keep[k]] = 1;
+    }
+    ERL_NIF_TERM out = enif_make_list(env, 0);
+    for (uint32_t s = ib.n_subscribers; s-- > 0;) {
+        ERL_NIF_TERM box = enif_make_list(env, 0);
+        for (uint32_t q = ib.inbox_offsets[s + 1]; q-- > ib.inbox_offsets[s];) {
+            const uint32_t* u = bsearch(&ib.filter_ids[q], uniq, nu, sizeof(uint32_t), cmp_u32);
+            if (!u || !live[u - uniq]) continue;   /* deleted meanwhile and its id reused */
+            box = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, ib.publishes[q]), term[u - uniq]),
+                                      box);
+        }
+        out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, ib.subscribers[s]), box), out);
+    }
+    packed_free(&p);
+    enif_free(uniq); enif_free(term); enif_free(live);
     tm_batch_free(r->e, b);
     return out;
 }
@@ -1076,6 +1144,7 @@ static ErlNifFunc funcs[] = {
     {"unsubscribe", 4, nif_unsubscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"subscriber_down", 3, nif_subscriber_down, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"dispatch_batch", 2, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"deliver_batch", 2, nif_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_routes_batch", 2, nif_match_routes_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"rules_match", 4, nif_rules_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"topic_match", 2, nif_topic_match, 0},

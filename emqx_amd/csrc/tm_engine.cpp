@@ -716,6 +716,32 @@ int tm_batch_dispatch(tm_engine* e, tm_batch* b, uint32_t flags, tm_deliveries* 
     }
 }
 
+int tm_batch_inboxes(tm_engine* e, tm_batch* b, uint32_t flags, tm_inboxes* out) {
+    // the arguments are checked first, so a host-only engine reports them too
+    if (!e) return TM_EINVAL;
+    if (!out) {
+        snprintf(last_error(), 512, "tm_batch_inboxes: out is NULL");
+        return TM_EINVAL;
+    }
+    if (flags & ~TM_INBOX_DEVICE) {
+        snprintf(last_error(), 512, "tm_batch_inboxes: unknown flag");
+        return TM_EINVAL;
+    }
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    int rc = e->use(b->rep);
+    if (rc) return rc;
+    try {
+        return e->batch_inboxes(b, flags, out);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+uint32_t tm_inbox_tile(void) { return INBOX_TILE; }
+
 int tm_batch_routes(tm_engine* e, tm_batch* b, tm_routes* out) {
     if (!e || !b || !out) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;   // host-only engine

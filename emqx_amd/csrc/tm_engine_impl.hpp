@@ -522,6 +522,16 @@ struct tm_batch {
         Event gev[4];   // around count + scan + rows, around the pick
     } sh;
 
+    // per-subscriber inboxes (tm_batch_inboxes): the sort's second key array and
+    // both payload arrays (the first key array is fan.d_fout), the pass table,
+    // the finish's head counts, and the result with its pinned mirror
+    struct Inbox {
+        DevBuf<uint32_t> d_val0, d_key1, d_val1, d_pubof, d_hist, d_hbs, d_hcount, d_hcbs, d_R;
+        DevBuf<uint32_t> d_pub, d_fid, d_sub, d_off;
+        PinBuf<uint32_t> h_R, h_pub, h_fid, h_sub, h_off;
+        Event iev0, iev1;   // around the inbox kernels
+    } inbox;
+
     static constexpr size_t HDR_FIXED = ((size_t)XG_WORD + TICKET_GROUPS * TICKET_STRIDE) * 4;
     static size_t hdr_bytes(size_t n) { return HDR_FIXED + n * 12; }
     // the replica (device copy of the trie) the batch runs on; fixed for the
@@ -609,6 +619,7 @@ struct tm_batch {
         rt = {};
         fan = {};
         sh = {};
+        inbox = {};
         dtab_dirty = true;
         end_recorded = false;
         graph.reset();
@@ -1825,6 +1836,7 @@ struct tm_engine {
     std::unordered_map<uint32_t, std::vector<std::string>> topics_of;
     bool subs_dirty = true;
     uint64_t sub_entries = 0, subs_version = 0;
+    uint32_t max_sub = 0;          // largest subscriber id ever subscribed (monotone): the inbox sort's key width
     uint64_t subs_gen = 0;         // bumped when the host arrays below are rebuilt
     // host image of the device arrays: soff (u64), subs, scnt = per node
     // min(soff[f + 1] - soff[f], 255) (the scan's 1-B gather), sone = the
@@ -1853,7 +1865,11 @@ struct tm_engine {
     int sync_subs(Replica& R);
 
     // tm_batch_dispatch: deliveries of a waited batch, resolved on the device
-    int batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out);
+    // entries (tm_batch_inboxes): the fill also writes every delivery's match
+    // entry into b->inbox.d_val0, and more than MAX_RESULT deliveries is TM_EOVERFLOW
+    int batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out, bool entries = false);
+    // tm_batch_inboxes: the batch's deliveries grouped by subscriber (fan-out, then a stable radix sort)
+    int batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out);
 
     // ---- shared subscriptions: the ?SHARED_SUBS bag of the local node
     // (src/emqx_shared_sub.erl:287-315, 358-367).  topic -> its (group, topic)

@@ -142,6 +142,7 @@ int tm_engine::subscribe(const uint8_t* t, size_t len, uint32_t sub, uint32_t no
     }
     sit->second.push_back(sub);
     topics_of[sub].push_back(std::move(k));
+    max_sub = std::max(max_sub, sub);
     ++sub_entries;
     subs_dirty = true;
     return TM_OK;
@@ -229,7 +230,7 @@ int tm_engine::sync_subs(Replica& R) {
     return TM_OK;
 }
 
-int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out) {
+int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out, bool entries) {
     if (!b->done) return TM_EINVAL;
     const bool rows = flags & TM_DISPATCH_ROWS;
     if (rows && ((flags & TM_DISPATCH_MATCH_OFFSETS) || !b->csr)) return TM_EINVAL;
@@ -302,6 +303,11 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out) {
         if ((rc = b->fan.d_fout.reserve(std::max<uint64_t>(total, 1)))) return rc;
         if ((rc = b->fan.d_ftile.reserve((size_t)(total / fan_fill_tile()) + 2))) return rc;
         fa.out = b->fan.d_fout.p; fa.total = total; fa.tile_j = b->fan.d_ftile.p;
+        if (entries) {
+            if (total > MAX_RESULT) return TM_EOVERFLOW;   // the sort's payload and the inbox offsets are u32
+            if ((rc = b->inbox.d_val0.reserve(std::max<uint64_t>(total, 1)))) return rc;
+            fa.out_j = b->inbox.d_val0.p;
+        }
         HIP_OK(hipEventRecord(b->fan.fev0.e, stream));
         HIP_OK(launch_fan_fill(fa, stream));
         HIP_OK(hipEventRecord(b->fan.fev1.e, stream));
@@ -343,6 +349,100 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out) {
     out->match_offsets = want_moff ? b->fan.h_moff.p : nullptr;
     out->subscribers = counts_only ? nullptr : b->fan.h_fout.p;
     out->fill_ms = fill_ms;
+    return TM_OK;
+}
+
+int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
+    auto einval = [](const char* msg) {
+        snprintf(last_error(), 512, "%s", msg);
+        return TM_EINVAL;
+    };
+    if (!b->done) return einval("tm_batch_inboxes: the batch has not been waited for");
+    if (b->dedup) return einval("tm_batch_inboxes: a TM_BATCH_DEDUP batch (an inbox entry names a publish)");
+    if (b->total > MAX_RESULT) return TM_EOVERFLOW;
+    tm_deliveries dl{};
+    int rc;
+    if ((rc = batch_dispatch(b, TM_DISPATCH_DEVICE, &dl, true))) return rc;   // returns with the stream idle
+    Replica& R = *b->rep;
+    const hipStream_t stream = R.stream;
+    tm_batch::Inbox& ib = b->inbox;
+    const uint32_t n = b->n, m = (uint32_t)b->total;
+    const uint32_t D = (uint32_t)dl.n_deliveries;   // <= MAX_RESULT (batch_dispatch checked)
+    const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
+    const uint32_t bits = max_sub ? 32u - (uint32_t)__builtin_clz(max_sub) : 0u;
+    const uint32_t passes = std::max(1u, (bits + 7) / 8);
+    // a subscriber with a delivery has a subscription: R <= both
+    const uint32_t rcap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(D, topics_of.size()));
+    const size_t dd = std::max<size_t>(D, 1), nh = (size_t)256 * ntiles;
+    if ((rc = ib.d_key1.reserve(dd))) return rc;
+    if ((rc = ib.d_val1.reserve(dd))) return rc;
+    if ((rc = ib.d_pubof.reserve(std::max<size_t>(m, 1)))) return rc;
+    if ((rc = ib.d_hist.reserve(nh + 1))) return rc;
+    if ((rc = ib.d_hbs.reserve((size_t)scan_block_count((uint32_t)nh) + 1))) return rc;
+    if ((rc = ib.d_hcount.reserve((size_t)ntiles + 1))) return rc;
+    if ((rc = ib.d_hcbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
+    if ((rc = ib.d_R.reserve(1))) return rc;
+    if ((rc = ib.h_R.reserve(1))) return rc;
+    if ((rc = ib.d_pub.reserve(dd))) return rc;
+    if ((rc = ib.d_fid.reserve(dd))) return rc;
+    if ((rc = ib.d_sub.reserve(rcap))) return rc;
+    if ((rc = ib.d_off.reserve((size_t)rcap + 1))) return rc;
+    if ((rc = ib.iev0.create())) return rc;
+    if ((rc = ib.iev1.create())) return rc;
+    InboxArgs a{};
+    a.row_off = b->dcsr.d_rowoff.p; a.ids = b->dcsr.d_ids.p; a.n = n; a.m = m; a.D = D; a.ntiles = ntiles;
+    a.passes = passes; a.pub_of = ib.d_pubof.p;
+    a.key0 = b->fan.d_fout.p; a.val0 = ib.d_val0.p; a.key1 = ib.d_key1.p; a.val1 = ib.d_val1.p;
+    a.hist = ib.d_hist.p; a.hbs = ib.d_hbs.p; a.rcap = rcap; a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
+    a.d_R = ib.d_R.p; a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
+    a.inbox_offsets = ib.d_off.p;
+    uint32_t nsub = 0;
+    float ms = 0.f;
+    if (D) {
+        HIP_OK(hipEventRecord(ib.iev0.e, stream));
+        HIP_OK(launch_inbox_pubof(a, stream));
+        HIP_OK(launch_inbox_sort(a, stream));
+        HIP_OK(launch_inbox_finish(a, stream));
+        HIP_OK(hipEventRecord(ib.iev1.e, stream));
+        HIP_OK(hipMemcpyAsync(ib.h_R.p, ib.d_R.p, 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        HIP_OK(hipEventElapsedTime(&ms, ib.iev0.e, ib.iev1.e));
+        nsub = ib.h_R.p[0];
+        if (nsub == 0 || nsub > rcap) {
+            snprintf(last_error(), 512, "inconsistent inboxes: %u subscribers for %u deliveries (capacity %u)", nsub, D, rcap);
+            return TM_EIO;
+        }
+    } else {
+        HIP_OK(hipMemsetAsync(ib.d_off.p, 0, 4, stream));   // inbox_offsets = {0}
+        HIP_OK(hipStreamSynchronize(stream));
+    }
+    out->n_topics = n;
+    out->n_subscribers = nsub;
+    out->n_deliveries = D;
+    out->kernel_ms = ms;
+    out->passes = D ? passes : 0;
+    if (flags & TM_INBOX_DEVICE) {
+        out->subscribers = ib.d_sub.p; out->inbox_offsets = ib.d_off.p;
+        out->publishes = ib.d_pub.p; out->filter_ids = ib.d_fid.p;
+        return TM_OK;
+    }
+    if ((rc = ib.h_sub.reserve(std::max<size_t>(nsub, 1)))) return rc;
+    if ((rc = ib.h_off.reserve((size_t)nsub + 1))) return rc;
+    if ((rc = ib.h_pub.reserve(dd))) return rc;
+    if ((rc = ib.h_fid.reserve(dd))) return rc;
+    HIP_OK(hipMemcpyAsync(ib.h_off.p, ib.d_off.p, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, stream));
+    if (nsub) HIP_OK(hipMemcpyAsync(ib.h_sub.p, ib.d_sub.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, stream));
+    if (D) {
+        HIP_OK(hipMemcpyAsync(ib.h_pub.p, ib.d_pub.p, (size_t)D * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(ib.h_fid.p, ib.d_fid.p, (size_t)D * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    if (ib.h_off.p[nsub] != D) {
+        snprintf(last_error(), 512, "inconsistent inbox offsets: %u vs %u", ib.h_off.p[nsub], D);
+        return TM_EIO;
+    }
+    out->subscribers = ib.h_sub.p; out->inbox_offsets = ib.h_off.p;
+    out->publishes = ib.h_pub.p; out->filter_ids = ib.h_fid.p;
     return TM_OK;
 }
 

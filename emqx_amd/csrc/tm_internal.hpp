@@ -308,6 +308,7 @@ struct FanArgs {
     const uint32_t* rcount;   // n: the walk's row lengths (tm_batch_rows)
     const unsigned long long* rsrc;   // n: the rows' first staging entries
     uint32_t* dcount;         // n: deliveries of each row (drow = its first)
+    uint32_t* out_j;          // tm_batch_inboxes: match entry of delivery p (the fill's entries variant), else null
 };
 
 // staging region capacity of a launch: a multiple of 16 entries per region so
@@ -359,6 +360,45 @@ struct SharedArgs {
     uint32_t* out_grp;
     uint32_t* out_sub;
     uint64_t cap;             // capacity of the three
+};
+
+// Per-subscriber inboxes (tm_batch_inboxes): the batch's deliveries, which the
+// fan-out wrote in publish order, grouped by subscriber.  A stable LSD radix
+// sort of D (subscriber, match entry) pairs, 8 bits per pass, over tiles of
+// INBOX_TILE pairs; each pass is histogram -> scan -> scatter on that pass's
+// input, and no kernel waits for another workgroup.  The
+// finish turns the sorted pairs into (publish, filter) and the inbox heads
+// into subscribers[] / inbox_offsets[].
+constexpr uint32_t INBOX_TILE = 4096;   // pairs per 256-thread workgroup: wave w owns pairs [1024 w, 1024 w + 1024)
+constexpr uint32_t INBOX_MAX_PASSES = 4;
+struct InboxArgs {
+    const uint32_t* row_off;  // match CSR (n + 1) and filter ids (m entries)
+    const uint32_t* ids;
+    uint32_t n;
+    uint32_t m;
+    uint32_t D;               // deliveries (<= 2^32 - 16)
+    uint32_t ntiles;          // ceil(D / INBOX_TILE)
+    uint32_t passes;          // 1 .. INBOX_MAX_PASSES
+    uint32_t* pub_of;         // m: publish of match entry j
+    // the ping-pong: pass 0 reads (key0, val0) -- the fan-out's subscribers and
+    // entries -- and writes (key1, val1); pass 1 the other way, and so on
+    uint32_t* key0;
+    uint32_t* val0;
+    uint32_t* key1;
+    uint32_t* val1;
+    // the current pass's table (256 * ntiles + 1): pairs of tile t with digit d
+    // at [d * ntiles + t] (digit-major, so its exclusive scan is the scatter's
+    // offset), scanned in place (block-local; + hbs[i / SCAN_TILE])
+    uint32_t* hist;
+    uint32_t* hbs;
+    uint32_t rcap;            // capacity of subscribers (inbox_offsets holds rcap + 1)
+    uint32_t* hcount;         // ntiles + 1: inbox heads per tile, scanned in place (+ hcbs)
+    uint32_t* hcbs;
+    uint32_t* d_R;            // subscribers with a delivery
+    uint32_t* publishes;      // D
+    uint32_t* filter_ids;     // D
+    uint32_t* subscribers;    // rcap
+    uint32_t* inbox_offsets;  // rcap + 1
 };
 
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
@@ -443,7 +483,12 @@ hipError_t launch_route_fill(const RouteArgs& a, hipStream_t s);
 // fan-out: per-match delivery counts + u64 scan (moff, d_total), publish row
 // offsets (drow), then the load-balanced subscriber copy (out[total])
 hipError_t launch_fan_scan(const FanArgs& a, hipStream_t s);
-hipError_t launch_fan_fill(const FanArgs& a, hipStream_t s);
+hipError_t launch_fan_fill(const FanArgs& a, hipStream_t s);   // a.out_j set: also the entry of every delivery
+// inboxes: publish of every match entry; the sort (the sorted pairs end in
+// key0 / val0 after an even number of passes, else key1 / val1); the finish
+hipError_t launch_inbox_pubof(const InboxArgs& a, hipStream_t s);
+hipError_t launch_inbox_sort(const InboxArgs& a, hipStream_t s);
+hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s);
 hipError_t launch_fan_globalize(const FanArgs& a, hipStream_t s);   // block-relative moff -> global
 uint32_t fan_scan_tile();   // match entries per scan block
 uint32_t fan_fill_tile();   // deliveries per fill block

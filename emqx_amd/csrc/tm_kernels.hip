@@ -1927,7 +1927,9 @@ __global__ __launch_bounds__(FAN_BLOCK) void tm_fan_tiles(FanArgs a, uint64_t nt
 // of filters without local subscribers) searches moff per delivery instead.
 // WIDE: the batch delivers more than big_limit (some scan block may hold u64
 // offsets); otherwise only the 32-bit staging path is compiled in
-template <bool WIDE>
+// WJ (tm_batch_inboxes): the entry of every delivery goes to out_j as well --
+// the max-scan has it already, so it is one more coalesced store
+template <bool WIDE, bool WJ = false>
 __global__ __launch_bounds__(FAN_BLOCK) void tm_fan_fill(FanArgs a) {
     __shared__ int64_t base[FAN_LDS_ENTRIES];
     __shared__ __attribute__((aligned(16))) uint16_t own[FAN_FILL_TILE];
@@ -1946,6 +1948,7 @@ __global__ __launch_bounds__(FAN_BLOCK) void tm_fan_fill(FanArgs a) {
         for (uint64_t p = start + t; p < end; p += FAN_BLOCK) {
             j = fan_upper(a, j, jhi + 1, p) - 1;
             a.out[p] = a.subs[a.soff[fan_fid(a, j)] + (p - fan_moff(a, j))];
+            if constexpr (WJ) a.out_j[p] = (uint32_t)j;
         }
         return;
     }
@@ -2099,6 +2102,243 @@ __global__ __launch_bounds__(FAN_BLOCK) void tm_fan_fill(FanArgs a) {
     for (uint32_t u = 0; u < FAN_FILL_PER; ++u) {
         const uint32_t i = t + u * FAN_BLOCK;
         if (i < len) a.out[start + i] = r[u];
+    }
+    if constexpr (WJ) {
+#pragma unroll
+        for (uint32_t u = 0; u < FAN_FILL_PER; ++u) {
+            const uint32_t i = t + u * FAN_BLOCK;
+            if (i < len) a.out_j[start + i] = (uint32_t)(jlo + ((uint32_t)own[i] - 1u));
+        }
+    }
+}
+
+// ------------------------------------- per-subscriber inboxes (tm_batch_inboxes)
+//
+// SubPid ! {deliver, Topic, Msg} (src/emqx_broker.erl:298-302) for a whole
+// batch: the fan-out's deliveries, in publish order, regrouped by subscriber
+// with each subscriber's deliveries kept in that order -- a stable sort of
+// (subscriber, match entry) pairs.  LSD radix, 8 bits per pass:
+//   hist     the pass's digit counts per tile, digit-major
+//   scan     (the project's two-level scan) -> the first output slot of (digit, tile)
+//   scatter  rank of a pair among the equal digits before it in its tile, from
+//            wave ballots (no LDS atomics: a '#' subscriber makes a whole
+//            tile one key), staged in LDS by digit, written as runs
+// A tile's histogram for pass p counts the pairs the tile holds when pass p
+// starts, i.e. as pass p - 1 left them, so tm_inbox_hist runs once per pass on
+// that pass's input: one read of the unsorted keys can give every pass's
+// GLOBAL histogram but not the per-tile ones a scatter without look-back needs.
+// Every kernel terminates on its own inputs.
+
+constexpr uint32_t INBOX_BLOCK = 256;
+constexpr uint32_t INBOX_WAVE_PAIRS = INBOX_TILE / (INBOX_BLOCK / 64);   // 1024 consecutive pairs per wave
+constexpr uint32_t INBOX_ROUNDS = INBOX_WAVE_PAIRS / 64;                 // of 64 consecutive pairs each
+static_assert(MAX_RESULT + 16 <= 0x100000000ull, "a delivery index plus a tile's slack fits u32");
+
+// lanes of the wave whose digit equals mine, among the active ones: 8 ballots,
+// the same cost whatever the skew
+__device__ __forceinline__ uint64_t inbox_peers(uint32_t d, uint64_t act) {
+    uint64_t peers = act;
+#pragma unroll
+    for (uint32_t b = 0; b < 8; ++b) {
+        const bool s = (d >> b) & 1u;
+        const uint64_t m = __ballot(s);
+        peers &= s ? m : ~m;
+    }
+    return peers;
+}
+__device__ __forceinline__ uint32_t inbox_mbcnt(uint64_t m) {   // set bits of m below my lane
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+__global__ __launch_bounds__(256) void tm_inbox_pubof(InboxArgs a) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= a.m) return;
+    // the last row p with row_off[p] <= j (rows before it may be empty)
+    uint32_t lo = 0, hi = a.n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.row_off[mid] <= j) lo = mid; else hi = mid;
+    }
+    a.pub_of[j] = lo;
+}
+
+// hist[d * ntiles + tile] = pairs of the tile whose digit (key >> shift) & 255 is d
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_hist(InboxArgs a, const uint32_t* keys, uint32_t* hist,
+                                                             uint32_t shift) {
+    __shared__ uint32_t cnt[INBOX_BLOCK / 64][256];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    for (uint32_t i = t; i < (INBOX_BLOCK / 64) * 256; i += INBOX_BLOCK) (&cnt[0][0])[i] = 0;
+    __syncthreads();
+    const uint64_t wbase = (uint64_t)blockIdx.x * INBOX_TILE + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t key[INBOX_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        key[r] = q < a.D ? keys[q] : 0u;
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint32_t d = (key[r] >> shift) & 255u;
+        const uint64_t peers = inbox_peers(d, __ballot(on));
+        // the first lane of every digit adds its lanes to the wave's own counter
+        if (on && inbox_mbcnt(peers) == 0) cnt[w][d] += (uint32_t)__popcll(peers);
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < INBOX_BLOCK / 64; ++k) s += cnt[k][t];
+    hist[(uint64_t)t * a.ntiles + blockIdx.x] = s;   // t = digit (256 threads, 256 digits)
+}
+static_assert(INBOX_BLOCK == 256, "one thread per digit");
+
+// One pass over one tile: (kin, vin) -> (kout, vout) by digit (key >> shift) & 255.
+// off / bs: the pass's scanned table.
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_scatter(InboxArgs a, const uint32_t* kin, const uint32_t* vin,
+                                                                uint32_t* kout, uint32_t* vout, const uint32_t* off,
+                                                                const uint32_t* bs, uint32_t shift) {
+    __shared__ uint32_t sk[INBOX_TILE], sv[INBOX_TILE];
+    __shared__ uint32_t cnt[INBOX_BLOCK / 64][256];   // per wave and digit: pairs so far, then the wave's first slot
+    __shared__ uint32_t gb[256];                      // per digit: first output slot - first staged slot
+    __shared__ uint32_t sh[33];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    for (uint32_t i = t; i < (INBOX_BLOCK / 64) * 256; i += INBOX_BLOCK) (&cnt[0][0])[i] = 0;
+    __syncthreads();
+    const uint64_t tbase = (uint64_t)blockIdx.x * INBOX_TILE;
+    const uint64_t wbase = tbase + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t key[INBOX_ROUNDS], val[INBOX_ROUNDS], rk[INBOX_ROUNDS];
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        key[r] = q < a.D ? kin[q] : 0u;
+        val[r] = q < a.D ? vin[q] : 0u;
+    }
+    // rank among the wave's equal digits: earlier rounds (the counter), then lower lanes (mbcnt)
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint32_t d = (key[r] >> shift) & 255u;
+        const uint64_t peers = inbox_peers(d, __ballot(on));
+        const uint32_t below = inbox_mbcnt(peers);
+        const uint32_t c0 = on ? cnt[w][d] : 0u;
+        __builtin_amdgcn_wave_barrier();
+        if (on && below == 0) cnt[w][d] = c0 + (uint32_t)__popcll(peers);
+        __builtin_amdgcn_wave_barrier();
+        rk[r] = c0 + below;
+    }
+    __syncthreads();
+    // thread = digit: the digit's first staged slot (scan over the digits), its
+    // waves' first slots (earlier waves first), and where its run goes
+    {
+        uint32_t c[INBOX_BLOCK / 64], tot = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < INBOX_BLOCK / 64; ++k) { c[k] = cnt[k][t]; tot += c[k]; }
+        uint32_t all;
+        const uint32_t first = block_excl_scan(tot, sh, all);
+        uint32_t run = first;
+#pragma unroll
+        for (uint32_t k = 0; k < INBOX_BLOCK / 64; ++k) { cnt[k][t] = run; run += c[k]; }
+        const uint64_t i = (uint64_t)t * a.ntiles + blockIdx.x;
+        gb[t] = off[i] + bs[i / SCAN_TILE] - first;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        if (q < a.D) {
+            const uint32_t pos = cnt[w][(key[r] >> shift) & 255u] + rk[r];
+            if (pos < INBOX_TILE) { sk[pos] = key[r]; sv[pos] = val[r]; }
+        }
+    }
+    __syncthreads();
+    const uint32_t len = (uint32_t)min<uint64_t>(INBOX_TILE, a.D - tbase);
+#pragma unroll
+    for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+        const uint32_t s = k * INBOX_BLOCK + t;
+        if (s < len) {
+            const uint32_t ky = sk[s];
+            const uint32_t dst = gb[(ky >> shift) & 255u] + s;
+            if (dst < a.D) { kout[dst] = ky; vout[dst] = sv[s]; }
+        }
+    }
+}
+
+// The sorted pairs -> (publish, filter) of every delivery, and the inbox heads
+// (the first delivery of every subscriber) of the tile counted.
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_finish(InboxArgs a, const uint32_t* keys, const uint32_t* vals) {
+    __shared__ uint32_t hw[INBOX_BLOCK / 64];
+    const uint32_t t = threadIdx.x;
+    const uint64_t tbase = (uint64_t)blockIdx.x * INBOX_TILE;
+    uint32_t heads = 0;
+    uint32_t j[INBOX_TILE / INBOX_BLOCK], ky[INBOX_TILE / INBOX_BLOCK], kp[INBOX_TILE / INBOX_BLOCK];
+#pragma unroll
+    for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+        const uint64_t q = tbase + k * INBOX_BLOCK + t;
+        j[k] = q < a.D ? vals[q] : a.m;
+        ky[k] = q < a.D ? keys[q] : 0u;
+        kp[k] = (q < a.D && q) ? keys[q - 1] : ~ky[k];
+    }
+    uint32_t p[INBOX_TILE / INBOX_BLOCK], f[INBOX_TILE / INBOX_BLOCK];
+#pragma unroll
+    for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+        const bool ok = j[k] < a.m;
+        p[k] = ok ? a.pub_of[j[k]] : NONE;
+        f[k] = ok ? a.ids[j[k]] : NONE;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+        const uint64_t q = tbase + k * INBOX_BLOCK + t;
+        if (q < a.D) {
+            a.publishes[q] = p[k];
+            a.filter_ids[q] = f[k];
+        }
+        heads += (uint32_t)__popcll(__ballot(q < a.D && ky[k] != kp[k]));
+    }
+    if ((t & 63) == 0) hw[t >> 6] = heads;
+    __syncthreads();
+    if (t == 0) a.hcount[blockIdx.x] = hw[0] + hw[1] + hw[2] + hw[3];
+}
+
+// Compaction of the heads: subscribers[r] and inbox_offsets[r] of the r-th
+// inbox, r = heads before it (earlier tiles: the scan; earlier waves; earlier
+// rounds; lower lanes).
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_heads(InboxArgs a, const uint32_t* keys) {
+    __shared__ uint32_t hw[INBOX_BLOCK / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const uint64_t wbase = (uint64_t)blockIdx.x * INBOX_TILE + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t ky[INBOX_ROUNDS];
+    uint64_t hm[INBOX_ROUNDS];
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        ky[r] = q < a.D ? keys[q] : 0u;
+        const uint32_t kp = (q < a.D && q) ? keys[q - 1] : ~ky[r];
+        hm[r] = __ballot(q < a.D && ky[r] != kp);
+        mine += (uint32_t)__popcll(hm[r]);
+    }
+    if (lane == 0) hw[w] = mine;
+    __syncthreads();
+    uint32_t base = a.hcount[blockIdx.x] + a.hcbs[blockIdx.x / SCAN_TILE];
+    for (uint32_t k = 0; k < w; ++k) base += hw[k];
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        if ((hm[r] >> lane) & 1ull) {
+            const uint32_t i = base + inbox_mbcnt(hm[r]);
+            if (i < a.rcap) {
+                a.subscribers[i] = ky[r];
+                a.inbox_offsets[i] = (uint32_t)q;
+            }
+        }
+        base += (uint32_t)__popcll(hm[r]);
+    }
+    if (blockIdx.x == 0 && t == 0) {
+        const uint32_t R = *a.d_R;
+        if (R <= a.rcap) a.inbox_offsets[R] = a.D;
     }
 }
 
@@ -3735,9 +3975,48 @@ hipError_t launch_fan_fill(const FanArgs& a, hipStream_t s) {
         const uint64_t nt = (a.total + FAN_FILL_TILE - 1) / FAN_FILL_TILE;
         hipLaunchKernelGGL(tm_fan_tiles, dim3((uint32_t)((nt + 1 + FAN_BLOCK - 1) / FAN_BLOCK)), dim3(FAN_BLOCK), 0, s,
                            a, nt);
-        if (a.total > a.big_limit) hipLaunchKernelGGL(tm_fan_fill<true>, dim3((uint32_t)nt), dim3(FAN_BLOCK), 0, s, a);
+        if (a.out_j) {
+            if (a.total > a.big_limit) hipLaunchKernelGGL((tm_fan_fill<true, true>), dim3((uint32_t)nt), dim3(FAN_BLOCK), 0, s, a);
+            else hipLaunchKernelGGL((tm_fan_fill<false, true>), dim3((uint32_t)nt), dim3(FAN_BLOCK), 0, s, a);
+        } else if (a.total > a.big_limit) hipLaunchKernelGGL(tm_fan_fill<true>, dim3((uint32_t)nt), dim3(FAN_BLOCK), 0, s, a);
         else hipLaunchKernelGGL(tm_fan_fill<false>, dim3((uint32_t)nt), dim3(FAN_BLOCK), 0, s, a);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_inbox_pubof(const InboxArgs& a, hipStream_t s) {
+    if (a.m && a.n) hipLaunchKernelGGL(tm_inbox_pubof, dim3((a.m + 255) / 256), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_inbox_sort(const InboxArgs& a, hipStream_t s) {
+    if (!a.D || !a.ntiles || a.passes > INBOX_MAX_PASSES) return hipGetLastError();
+    ScanArgs sa{};
+    sa.count = a.hist; sa.row_off = a.hist; sa.block_sums = a.hbs; sa.n = 256u * a.ntiles;   // in place
+    for (uint32_t p = 0; p < a.passes; ++p) {
+        const uint32_t* kin = p & 1 ? a.key1 : a.key0;
+        const uint32_t* vin = p & 1 ? a.val1 : a.val0;
+        uint32_t* kout = p & 1 ? a.key0 : a.key1;
+        uint32_t* vout = p & 1 ? a.val0 : a.val1;
+        hipLaunchKernelGGL(tm_inbox_hist, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, kin, a.hist, 8 * p);
+        const hipError_t e = launch_scan(sa, s, nullptr);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(tm_inbox_scatter, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, kin, vin, kout, vout,
+                           (const uint32_t*)a.hist, (const uint32_t*)a.hbs, 8 * p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s) {
+    if (!a.D || !a.ntiles) return hipGetLastError();
+    const uint32_t* keys = a.passes & 1 ? a.key1 : a.key0;
+    const uint32_t* vals = a.passes & 1 ? a.val1 : a.val0;
+    hipLaunchKernelGGL(tm_inbox_finish, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys, vals);
+    ScanArgs sa{};
+    sa.count = a.hcount; sa.row_off = a.hcount; sa.block_sums = a.hcbs; sa.n = a.ntiles;   // in place
+    const hipError_t e = launch_scan(sa, s, a.d_R);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(tm_inbox_heads, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys);
     return hipGetLastError();
 }
 

@@ -134,3 +134,40 @@ def publish_batch(topic_list):
         assert len(row) == offs[i + 1] - offs[i]
         out.append(row)
     return out
+
+
+def mailboxes(rows):
+    """The `SubPid ! {deliver, To, Msg}` loop of dispatch/2 (:298-302) over the
+    publishes of a batch in order, as mailboxes: rows[i] = publish i's
+    deliveries [(To, pid)] -> {pid: [(i, To)]}, each list in arrival order --
+    what emqx_misc:drain_deliver/1 (src/emqx_misc.erl:128-142) hands the
+    session.  Pure host code."""
+    boxes = {}
+    for i, row in enumerate(rows):
+        for to, pid in row:
+            boxes.setdefault(pid, []).append((i, to))
+    return boxes
+
+
+def deliver_batch(topic_list):
+    """publish_batch regrouped by subscriber on the device (tm_batch_inboxes):
+    {pid: [(publish index, To)]}, every pid's list in mailbox order; equals
+    mailboxes(publish_batch(topic_list))."""
+    eng = R.engine()
+    b = eng.prepare(topic_list)
+    b.launch()
+    b.wait()
+    subs, offs, pubs, fids = b.inboxes()
+    b.free()
+    cache = {}
+    out = {}
+    for r, s in enumerate(subs):
+        box = []
+        for q in range(int(offs[r]), int(offs[r + 1])):
+            fid = int(fids[q])
+            f = cache.get(fid)
+            if f is None:
+                f = cache[fid] = eng.filter_bytes(fid)
+            box.append((int(pubs[q]), f))
+        out[_terms[int(s)]] = box
+    return out

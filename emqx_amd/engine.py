@@ -187,6 +187,30 @@ class Batch:
         return (int(d.n_deliveries), float(d.kernel_ms), ptr(d.row_offsets), ptr(d.filter_ids), ptr(d.groups),
                 ptr(d.subscribers))
 
+    def inboxes(self):
+        """Per-subscriber inboxes (tm_batch_inboxes): the deliveries of
+        dispatch() grouped by subscriber, each inbox in mailbox order ->
+        (subscribers u32[R] ascending, offsets u32[R+1], publishes u32[D],
+        filter_ids u32[D]); inbox r is entries offsets[r] .. offsets[r+1]."""
+        d = self._inboxes(0)
+        r, t = int(d.n_subscribers), int(d.n_deliveries)
+        cp = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, np.uint32)  # noqa: E731
+        self.inbox_info = {"kernel_ms": float(d.kernel_ms), "passes": int(d.passes)}
+        return cp(d.subscribers, r), cp(d.inbox_offsets, r + 1), cp(d.publishes, t), cp(d.filter_ids, t)
+
+    def inboxes_device(self):
+        """TM_INBOX_DEVICE: -> (n_subscribers, n_deliveries, kernel ms, passes,
+        device ptrs subscribers / offsets / publishes / filter_ids)."""
+        d = self._inboxes(N.TM_INBOX_DEVICE)
+        ptr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        return (int(d.n_subscribers), int(d.n_deliveries), float(d.kernel_ms), int(d.passes), ptr(d.subscribers),
+                ptr(d.inbox_offsets), ptr(d.publishes), ptr(d.filter_ids))
+
+    def _inboxes(self, flags: int) -> "N.Inboxes":
+        d = N.Inboxes()
+        N.check(self.eng.L.tm_batch_inboxes(self.eng.h, self.h, flags, C.byref(d)), "tm_batch_inboxes")
+        return d
+
     def _dispatch_shared(self, strategy, keys, seed: int, flags: int) -> "N.SharedDeliveries":
         o = N.SharedOpts()
         o.strategy = N.SHARED_STRATEGIES.get(strategy, strategy) if isinstance(strategy, str) else int(strategy)

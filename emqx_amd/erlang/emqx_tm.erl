@@ -22,6 +22,7 @@
         , unsubscribe/4
         , subscriber_down/3
         , dispatch_batch/2
+        , deliver_batch/2
         , match_routes_batch/2
         , rules_match/4
         , acl_new/2
@@ -123,6 +124,14 @@ subscriber_down(_Engine, _SubId, _NodeDestId) -> erlang:nif_error(nif_not_loaded
 %% SubIds to deliver to ([] = {error, no_subscribers}).
 -spec(dispatch_batch(reference(), [binary()]) -> [[non_neg_integer()]]).
 dispatch_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
+
+%% The same deliveries grouped by subscriber on the device: SubIds ascending,
+%% each with its {PublishIndex0, To} in mailbox order (src/emqx_broker.erl:
+%% 298-302), so the caller sends one inbox per SubPid, in order, and
+%% emqx_misc:drain_deliver/1 collects it whole (INTEGRATION.md).
+-spec(deliver_batch(reference(), [binary()])
+      -> [{non_neg_integer(), [{non_neg_integer(), binary()}]}] | {error, term()}).
+deliver_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
 
 %% Shared-subscription members (emqx_shared_sub's handle_call({subscribe |
 %% unsubscribe, Group, Topic, SubPid}) and cleanup_down/1,

@@ -430,6 +430,51 @@ typedef struct {
 #define TM_DISPATCH_ROWS          8u
 TM_API int  tm_batch_dispatch(tm_engine* e, tm_batch* b, uint32_t flags, tm_deliveries* out);
 
+/* Deliveries of a waited batch grouped by subscriber: what each SubPid's
+ * mailbox holds after the batch's messages were published in order
+ * (src/emqx_broker.erl:298-302) and what emqx_misc:drain_deliver/1 hands the
+ * session as one list (src/emqx_misc.erl:128-142, src/emqx_connection.erl:376-378).
+ * Let L be the batch's deliveries in tm_batch_dispatch order: publish order,
+ * a publish's filters in match (Erlang binary) order, a filter's subscribers
+ * in subscription order.  The inbox of subscriber S = subscribers[r] is
+ * entries [inbox_offsets[r], inbox_offsets[r + 1]) of publishes / filter_ids:
+ * the subsequence of L whose subscriber is S, in L's order.  A publish that
+ * reaches S through two filters (a/+ and a/#) appears twice, in match order,
+ * as the reference sends two messages.  This is SubPid's mailbox order when
+ * one process publishes the batch's messages in order (Erlang keeps the
+ * signal order between two processes); within one publish the reference
+ * dispatches the filters in the order emqx_trie:match/1 found them (a DFS
+ * over ETS lookups), which DESIGN.md §1 treats as a set -- here it is the
+ * match order of tm_batch_result.
+ * The call runs the fan-out itself (dense CSR, device-resident) and then a
+ * stable radix sort by subscriber, so it counts as a dispatch of the batch:
+ * pointers from an earlier tm_batch_dispatch or tm_batch_inboxes on the batch
+ * are valid until the next of either, a re-prepare or a free.
+ * TM_INBOX_DEVICE: no copy back, the four arrays are device memory of the
+ * batch; otherwise batch-owned pinned memory, valid likewise.  passes = 8-bit
+ * radix passes run: max(1, ceil(bits of the largest subscriber id ever given
+ * to tm_subscribe / 8)); 0 when there was nothing to sort.
+ * n_topics = 0 or no delivery: n_subscribers = 0, inbox_offsets = {0}, rc 0.
+ * TM_EINVAL + tm_last_error(): out NULL, an unknown flag, a batch not waited,
+ * a TM_BATCH_DEDUP batch (an inbox entry names a publish, and a deduplicated
+ * row is not one).  TM_ENODEV on a host-only engine.  TM_EOVERFLOW for more
+ * than 2^32 - 16 deliveries (offsets and the sort's payload are u32). */
+typedef struct {
+    uint32_t        n_topics;       /* publishes of the batch */
+    uint32_t        n_subscribers;  /* R: subscribers with at least one delivery */
+    uint64_t        n_deliveries;   /* D: equals tm_batch_dispatch's n_deliveries */
+    const uint32_t* subscribers;    /* R ids, strictly ascending */
+    const uint32_t* inbox_offsets;  /* R + 1 */
+    const uint32_t* publishes;      /* D: publish index of each delivery */
+    const uint32_t* filter_ids;     /* D: the matched filter (To of {deliver, To, Msg}) */
+    float           kernel_ms;      /* device time of the inbox kernels (not the fan-out before them) */
+    uint32_t        passes;         /* radix passes run */
+} tm_inboxes;
+#define TM_INBOX_DEVICE 1u          /* no copy back: device pointers of the batch */
+TM_API int tm_batch_inboxes(tm_engine* e, tm_batch* b, uint32_t flags, tm_inboxes* out);
+/* diagnostic: deliveries per sort tile (tests place D around its multiples) */
+TM_API uint32_t tm_inbox_tile(void);
+
 /* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
 /* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
  * 287-305) of the local node.  group_dest = the aggregated dest id the caller
