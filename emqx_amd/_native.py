@@ -107,6 +107,33 @@ class Inboxes(C.Structure):
 TM_INBOX_DEVICE = 1
 
 
+class SubOpts(C.Structure):
+    _fields_ = [("qos", C.c_uint8), ("nl", C.c_uint8), ("rap", C.c_uint8), ("rh", C.c_uint8), ("subid", C.c_uint32)]
+
+    def asdict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+TM_SUBOPT_QOS, TM_SUBOPT_NL, TM_SUBOPT_RAP, TM_SUBOPT_RH, TM_SUBOPT_SUBID = 1, 2, 4, 8, 16
+SUBOPT_MASKS = {"qos": TM_SUBOPT_QOS, "nl": TM_SUBOPT_NL, "rap": TM_SUBOPT_RAP, "rh": TM_SUBOPT_RH,
+                "subid": TM_SUBOPT_SUBID}
+TM_SUBID_MAX = 268435455
+TM_MSG_RETAIN, TM_MSG_RETAINED, TM_MSG_NL = 4, 8, 8
+TM_DELIVER_DEVICE, TM_DELIVER_UPGRADE_QOS, TM_DELIVER_NL_ALL, TM_DELIVER_SUBIDS = 1, 2, 4, 8
+
+
+class DeliverOpts(C.Structure):
+    _fields_ = [("from_", C.c_void_p), ("msg", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class SessionInboxes(C.Structure):
+    _fields_ = [("n_topics", C.c_uint32), ("n_subscribers", C.c_uint32), ("n_deliveries", C.c_uint64),
+                ("n_dropped_no_local", C.c_uint64),
+                ("subscribers", C.POINTER(C.c_uint32)), ("inbox_offsets", C.POINTER(C.c_uint32)),
+                ("publishes", C.POINTER(C.c_uint32)), ("filter_ids", C.POINTER(C.c_uint32)),
+                ("msg", C.POINTER(C.c_uint8)), ("subids", C.POINTER(C.c_uint32)), ("kernel_ms", C.c_float)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -226,6 +253,10 @@ SIGNATURES = {
     "tm_batch_dispatch": (C.c_int, [P, P, C.c_uint32, C.POINTER(Deliveries)]),
     "tm_batch_inboxes": (C.c_int, [P, P, C.c_uint32, C.POINTER(Inboxes)]),
     "tm_inbox_tile": (C.c_uint32, []),
+    "tm_subscribe_opts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32, C.POINTER(SubOpts)]),
+    "tm_set_subopts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32, C.POINTER(SubOpts)]),
+    "tm_get_subopts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.POINTER(SubOpts)]),
+    "tm_batch_deliver": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(SessionInboxes)]),
     "tm_match_routes_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Routes)]),
     "tm_trie_insert_many": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_trie_delete_many": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(C.c_uint64)]),

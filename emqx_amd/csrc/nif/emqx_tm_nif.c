@@ -43,7 +43,8 @@ static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_TRUE, ATOM_FALSE, ATOM_UNDEFINED, 
     ATOM_TRIE_NODE, ATOM_NODE_NOT_FOUND, ATOM_ENOMEM, ATOM_EIO, ATOM_EINVAL, ATOM_ENODEV,
     ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH,
     ATOM_ALLOW, ATOM_DENY, ATOM_NOMATCH, ATOM_NONE, ATOM_ALL, ATOM_CLIENT, ATOM_USER, ATOM_IPADDR, ATOM_AND, ATOM_OR,
-    ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB, ATOM_RANDOM, ATOM_ROUND_ROBIN, ATOM_HASH;
+    ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB, ATOM_RANDOM, ATOM_ROUND_ROBIN, ATOM_HASH, ATOM_UPGRADE_QOS,
+    ATOM_NL_ALL;
 
 /* set while a match callback runs on the engine's completion thread */
 static __thread int in_engine_callback;
@@ -471,6 +472,47 @@ static ERL_NIF_TERM nif_subscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM a
     return rc ? err(env, rc) : ATOM_OK;
 }
 
+/* subscribe(Engine, Topic, SubId, NodeDestId, {QoS, NL, RAP, RH, SubIdent}) -> ok
+ * emqx_broker:subscribe/3 (src/emqx_broker.erl:127-136) with the ?SUBOPTION
+ * entry: a new subscription stores the options, an existing one merges them
+ * (the four flags replaced, SubIdent only when non-zero; 0 = none). */
+static ERL_NIF_TERM nif_subscribe_opts(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    ErlNifBinary b;
+    unsigned sub, dest, v[5];
+    const ERL_NIF_TERM* t;
+    int arity;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &b) || !enif_get_uint(env, argv[2], &sub) ||
+        !enif_get_uint(env, argv[3], &dest) || !enif_get_tuple(env, argv[4], &arity, &t) || arity != 5)
+        return enif_make_badarg(env);
+    for (int i = 0; i < 5; ++i)
+        if (!enif_get_uint(env, t[i], &v[i])) return enif_make_badarg(env);
+    if (v[0] > 2 || v[1] > 1 || v[2] > 1 || v[3] > 2 || v[4] > TM_SUBID_MAX) return enif_make_badarg(env);
+    const tm_subopts o = {(uint8_t)v[0], (uint8_t)v[1], (uint8_t)v[2], (uint8_t)v[3], v[4]};
+    int rc = tm_subscribe_opts(r->e, b.data, b.size, sub, dest, &o);
+    return rc ? err(env, rc) : ATOM_OK;
+}
+
+/* get_subopts(Engine, Topic, SubId) -> {ok, {QoS, NL, RAP, RH, SubIdent}} | undefined
+ * (emqx_broker:get_subopts/2, :373-386) */
+static ERL_NIF_TERM nif_get_subopts(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    ErlNifBinary b;
+    unsigned sub;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &b) || !enif_get_uint(env, argv[2], &sub))
+        return enif_make_badarg(env);
+    tm_subopts o;
+    int rc = tm_get_subopts(r->e, b.data, b.size, sub, &o);
+    if (rc == TM_ENOENT) return ATOM_UNDEFINED;
+    if (rc) return err(env, rc);
+    return enif_make_tuple2(env, ATOM_OK,
+                            enif_make_tuple5(env, enif_make_uint(env, o.qos), enif_make_uint(env, o.nl),
+                                             enif_make_uint(env, o.rap), enif_make_uint(env, o.rh),
+                                             enif_make_uint(env, o.subid)));
+}
+
 /* unsubscribe(Engine, Topic, SubId, NodeDestId) -> ok  (do_unsubscribe/4, :179-191;
  * not subscribed -> ok, as unsubscribe/1's `[] -> ok`) */
 static ERL_NIF_TERM nif_unsubscribe(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
@@ -588,6 +630,126 @@ static ERL_NIF_TERM nif_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TE
                                       box);
         }
         out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, ib.subscribers[s]), box), out);
+    }
+    packed_free(&p);
+    enif_free(uniq); enif_free(term); enif_free(live);
+    tm_batch_free(r->e, b);
+    return out;
+}
+
+static int get_bool(ERL_NIF_TERM t, unsigned* out) {
+    if (enif_is_identical(t, ATOM_TRUE)) { *out = 1; return 1; }
+    if (enif_is_identical(t, ATOM_FALSE)) { *out = 0; return 1; }
+    return 0;
+}
+
+/* session_deliver_batch(Engine, [{FromSubId | none, QoS, Retain, Retained, Topic}], [upgrade_qos | nl_all])
+ *   -> [{SubId, [{{PublishIndex0, Filter}, QoS, Retain, NL, SubIdent}]}]
+ * deliver_batch after emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693)
+ * and emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529), on the
+ * device (tm_batch_deliver): SubIds ascending, the subscribers that lost every
+ * delivery left out, each list in mailbox order.  Retain, Retained and NL are
+ * true | false, SubIdent 0 = none.  A delivery is a 5-tuple around the
+ * {PublishIndex0, Filter} pair of deliver_batch rather than a flat 6-tuple. */
+static ERL_NIF_TERM nif_session_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    unsigned n, nf;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_get_list_length(env, argv[1], &n) ||
+        !enif_get_list_length(env, argv[2], &nf))
+        return enif_make_badarg(env);
+    tm_deliver_opts o = {NULL, NULL, TM_DELIVER_SUBIDS};
+    ERL_NIF_TERM head, tail = argv[2];
+    for (unsigned i = 0; i < nf; i++) {
+        if (!enif_get_list_cell(env, tail, &head, &tail)) return enif_make_badarg(env);
+        if (enif_is_identical(head, ATOM_UPGRADE_QOS)) o.flags |= TM_DELIVER_UPGRADE_QOS;
+        else if (enif_is_identical(head, ATOM_NL_ALL)) o.flags |= TM_DELIVER_NL_ALL;
+        else return enif_make_badarg(env);
+    }
+    uint32_t* from = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
+    uint8_t* msg = enif_alloc(n ? n : 1);
+    uint64_t* offs = enif_alloc(sizeof(uint64_t) * (n + 1));
+    ErlNifBinary* bins = enif_alloc(sizeof(ErlNifBinary) * (n ? n : 1));
+    uint8_t* buf = NULL;
+    ERL_NIF_TERM out;
+    int ok = from && msg && offs && bins;
+    uint64_t total = 0;
+    tail = argv[1];
+    for (unsigned i = 0; ok && i < n; i++) {
+        const ERL_NIF_TERM* el;
+        int arity;
+        unsigned f = TM_NONE, qos, retain, retained;
+        ok = enif_get_list_cell(env, tail, &head, &tail) && enif_get_tuple(env, head, &arity, &el) && arity == 5 &&
+             (enif_is_identical(el[0], ATOM_NONE) || (enif_get_uint(env, el[0], &f) && f != TM_NONE)) &&
+             enif_get_uint(env, el[1], &qos) && qos <= 2 && get_bool(el[2], &retain) && get_bool(el[3], &retained) &&
+             enif_inspect_binary(env, el[4], &bins[i]);
+        if (!ok) break;
+        from[i] = f;
+        msg[i] = (uint8_t)(qos | (retain ? TM_MSG_RETAIN : 0u) | (retained ? TM_MSG_RETAINED : 0u));
+        offs[i] = total;
+        total += bins[i].size;
+    }
+    const int have = from && msg && offs && bins;
+    if (ok) buf = enif_alloc(total ? total : 1);
+    if (!ok || !buf) {
+        out = (have && !ok) ? enif_make_badarg(env) : err(env, TM_ENOMEM);
+        enif_free(from); enif_free(msg); enif_free(offs); enif_free(bins);
+        return out;
+    }
+    offs[n] = total;
+    for (unsigned i = 0; i < n; i++) memcpy(buf + offs[i], bins[i].data, bins[i].size);
+    enif_free(bins);
+    o.from = from;
+    o.msg = msg;
+    tm_batch* b;
+    tm_session_inboxes si;
+    packed p;
+    int rc = run_batch(r->e, buf, offs, n, &b);
+    enif_free(buf); enif_free(offs);
+    if (!rc) rc = tm_batch_deliver(r->e, b, &o, &si);
+    enif_free(from); enif_free(msg);
+    if (rc) {
+        if (b) tm_batch_free(r->e, b);
+        return err(env, rc);
+    }
+    /* the distinct filters copied out once; every delivery shares its filter's binary */
+    const uint64_t nd = si.n_deliveries;
+    uint32_t* uniq = enif_alloc(sizeof(uint32_t) * (nd ? nd : 1));
+    uint32_t nu = 0;
+    if (uniq) {
+        if (nd) memcpy(uniq, si.filter_ids, sizeof(uint32_t) * nd);
+        qsort(uniq, nd, sizeof(uint32_t), cmp_u32);
+        for (uint64_t q = 0; q < nd; ++q)
+            if (!nu || uniq[nu - 1] != uniq[q]) uniq[nu++] = uniq[q];
+    }
+    ERL_NIF_TERM* term = enif_alloc(sizeof(ERL_NIF_TERM) * (nu ? nu : 1));
+    uint8_t* live = enif_alloc(nu ? nu : 1);
+    rc = (uniq && term && live) ? pack_filters(r->e, uniq, nu, &p) : TM_ENOMEM;
+    if (rc) {
+        enif_free(uniq); enif_free(term); enif_free(live);
+        tm_batch_free(r->e, b);
+        return err(env, rc);
+    }
+    memset(live, 0, nu ? nu : 1);
+    for (uint32_t k = 0; k < p.n; ++k) {
+        term[p.keep[k]] = make_bin(env, p.buf + p.offs[k], p.offs[k + 1] - p.offs[k]);
+        live[p.keep[k]] = 1;
+    }
+    out = enif_make_list(env, 0);
+    for (uint32_t s = si.n_subscribers; s-- > 0;) {
+        ERL_NIF_TERM box = enif_make_list(env, 0);
+        for (uint32_t q = si.inbox_offsets[s + 1]; q-- > si.inbox_offsets[s];) {
+            const uint32_t* u = bsearch(&si.filter_ids[q], uniq, nu, sizeof(uint32_t), cmp_u32);
+            if (!u || !live[u - uniq]) continue;   /* deleted meanwhile and its id reused */
+            const uint8_t m = si.msg[q];
+            box = enif_make_list_cell(
+                env,
+                enif_make_tuple5(env, enif_make_tuple2(env, enif_make_uint(env, si.publishes[q]), term[u - uniq]),
+                                 enif_make_uint(env, m & 3u), (m & TM_MSG_RETAIN) ? ATOM_TRUE : ATOM_FALSE,
+                                 (m & TM_MSG_NL) ? ATOM_TRUE : ATOM_FALSE, enif_make_uint(env, si.subids[q])),
+                box);
+        }
+        out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, si.subscribers[s]), box), out);
     }
     packed_free(&p);
     enif_free(uniq); enif_free(term); enif_free(live);
@@ -1126,6 +1288,8 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     ATOM_RANDOM = enif_make_atom(env, "random");
     ATOM_ROUND_ROBIN = enif_make_atom(env, "round_robin");
     ATOM_HASH = enif_make_atom(env, "hash");
+    ATOM_UPGRADE_QOS = enif_make_atom(env, "upgrade_qos");
+    ATOM_NL_ALL = enif_make_atom(env, "nl_all");
     return 0;
 }
 
@@ -1141,10 +1305,13 @@ static ErlNifFunc funcs[] = {
     {"route_delete", 3, nif_route_delete, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"route_apply", 2, nif_route_apply, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"subscribe", 4, nif_subscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"subscribe", 5, nif_subscribe_opts, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"get_subopts", 3, nif_get_subopts, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"unsubscribe", 4, nif_unsubscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"subscriber_down", 3, nif_subscriber_down, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"dispatch_batch", 2, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"deliver_batch", 2, nif_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"session_deliver_batch", 3, nif_session_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_routes_batch", 2, nif_match_routes_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"rules_match", 4, nif_rules_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"topic_match", 2, nif_topic_match, 0},

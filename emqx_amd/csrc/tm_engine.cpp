@@ -742,6 +742,94 @@ int tm_batch_inboxes(tm_engine* e, tm_batch* b, uint32_t flags, tm_inboxes* out)
 
 uint32_t tm_inbox_tile(void) { return INBOX_TILE; }
 
+// the range checks of tm_subopts fields named by mask; 0 or TM_EINVAL + tm_last_error()
+static int subopts_check(const char* fn, const tm_subopts* o, uint32_t mask) {
+    const char* bad = nullptr;
+    if ((mask & TM_SUBOPT_QOS) && o->qos > 2) bad = "qos > 2";
+    else if ((mask & TM_SUBOPT_NL) && o->nl > 1) bad = "nl > 1";
+    else if ((mask & TM_SUBOPT_RAP) && o->rap > 1) bad = "rap > 1";
+    else if ((mask & TM_SUBOPT_RH) && o->rh > 2) bad = "rh > 2";
+    else if ((mask & TM_SUBOPT_SUBID) && o->subid > TM_SUBID_MAX) bad = "subid above 268435455";
+    if (!bad) return TM_OK;
+    snprintf(last_error(), 512, "%s: %s", fn, bad);
+    return TM_EINVAL;
+}
+static constexpr uint32_t SUBOPT_ALL = TM_SUBOPT_QOS | TM_SUBOPT_NL | TM_SUBOPT_RAP | TM_SUBOPT_RH | TM_SUBOPT_SUBID;
+
+int tm_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, uint32_t node_dest,
+                      const tm_subopts* opts) {
+    if (!e || (!topic && len)) return TM_EINVAL;
+    const tm_subopts o = opts ? *opts : tm_subopts{};
+    if (int rc = subopts_check("tm_subscribe_opts", &o, SUBOPT_ALL)) return rc;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    try {
+        return e->subscribe_opts(topic, len, subscriber, node_dest, o);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+int tm_set_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, uint32_t mask,
+                   const tm_subopts* opts) {
+    if (!e || (!topic && len)) return TM_EINVAL;
+    if (mask & ~SUBOPT_ALL) {
+        snprintf(last_error(), 512, "tm_set_subopts: unknown mask bit");
+        return TM_EINVAL;
+    }
+    if (!opts) {
+        snprintf(last_error(), 512, "tm_set_subopts: opts is NULL");
+        return TM_EINVAL;
+    }
+    if (int rc = subopts_check("tm_set_subopts", opts, mask)) return rc;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    try {
+        return e->set_subopts(topic, len, subscriber, mask, *opts);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+int tm_get_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, tm_subopts* out) {
+    if (!e || (!topic && len)) return TM_EINVAL;
+    if (!out) {
+        snprintf(last_error(), 512, "tm_get_subopts: out is NULL");
+        return TM_EINVAL;
+    }
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    try {
+        tm_subopts* o;
+        if (int rc = e->find_subopts(topic, len, subscriber, &o)) return rc;   // TM_ENOENT: get_subopts/2's `undefined`
+        *out = *o;
+        return TM_OK;
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_session_inboxes* out) {
+    // the arguments are checked first, so a host-only engine reports them too
+    if (!e) return TM_EINVAL;
+    if (!out || !opts) {
+        snprintf(last_error(), 512, "tm_batch_deliver: %s is NULL", out ? "opts" : "out");
+        return TM_EINVAL;
+    }
+    if (opts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS)) {
+        snprintf(last_error(), 512, "tm_batch_deliver: unknown flag");
+        return TM_EINVAL;
+    }
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    int rc = e->use(b->rep);
+    if (rc) return rc;
+    try {
+        return e->batch_deliver(b, opts, out);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
 int tm_batch_routes(tm_engine* e, tm_batch* b, tm_routes* out) {
     if (!e || !b || !out) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;   // host-only engine

@@ -532,6 +532,20 @@ struct tm_batch {
         Event iev0, iev1;   // around the inbox kernels
     } inbox;
 
+    // what the session sends (tm_batch_deliver): the per-call inputs (from,
+    // msg) and their pinned staging, the per-inbox and per-delivery scratch,
+    // the per-tile counts of what is left, and the result with its pinned mirror
+    struct Deliver {
+        DevBuf<uint32_t> d_from, d_first, d_esubid, d_kcount, d_kbs, d_ncount, d_nbs, d_tot;
+        DevBuf<uint8_t> d_min, d_own, d_emsg;
+        DevBuf<uint2> d_rng;
+        DevBuf<uint32_t> d_sub, d_off, d_pub, d_fid, d_subid;
+        DevBuf<uint8_t> d_msg;
+        PinBuf<uint32_t> h_from, h_tot, h_sub, h_off, h_pub, h_fid, h_subid;
+        PinBuf<uint8_t> h_min, h_msg;
+        Event dev0, dev1;   // around the delivery kernels
+    } dlv;
+
     static constexpr size_t HDR_FIXED = ((size_t)XG_WORD + TICKET_GROUPS * TICKET_STRIDE) * 4;
     static size_t hdr_bytes(size_t n) { return HDR_FIXED + n * 12; }
     // the replica (device copy of the trie) the batch runs on; fixed for the
@@ -620,6 +634,7 @@ struct tm_batch {
         fan = {};
         sh = {};
         inbox = {};
+        dlv = {};
         dtab_dirty = true;
         end_recorded = false;
         graph.reset();
@@ -757,6 +772,8 @@ struct Replica {
         DevBuf<uint64_t> d_soff;
         DevBuf<uint32_t> d_subs, d_sone;
         DevBuf<uint8_t> d_scnt;
+        // subscription options: CSR by subscriber (etm::DeliverArgs)
+        DevBuf<uint32_t> d_tsub, d_tstart, d_tnode, d_tval;
         // shared subscriptions: gcnt / goff by node id, runs, members; the run
         // slots' cursors stay here across uploads
         DevBuf<uint8_t> d_gcnt;
@@ -774,6 +791,7 @@ struct Replica {
     size_t tails_uploaded = 0, arena_uploaded = 0;
     uint64_t routes_gen = ~0ull;    // engine routes_gen / subs_gen / shared_gen when uploaded
     uint64_t subs_gen = ~0ull;
+    uint64_t subopts_gen = ~0ull;
     uint64_t shared_gen = ~0ull;
 
     // async pipeline (tm_match_async / tm_match_coalesced): calls queue on amu;
@@ -1851,6 +1869,28 @@ struct tm_engine {
     // topic's first subscriber adds the node's route (handle_call({subscribe,
     // Topic}) -> emqx_router:do_add_route/1, :438-440).
     int subscribe(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest);
+
+    // ---- the ?SUBOPTION table ({SubPid, Topic} -> SubOpts, :80, 101-102):
+    // opts_of[sub][i] are the options of topics_of[sub][i]; nl_entries counts
+    // the subscriptions with nl = 1 (none: no delivery can be dropped)
+    std::unordered_map<uint32_t, std::vector<tm_subopts>> opts_of;
+    uint64_t nl_entries = 0;
+    bool subopts_dirty = true;
+    uint64_t subopts_version = 0, subopts_gen = 0;
+    uint32_t subopts_nn = 0;
+    // host image of the device table (etm::DeliverArgs): CSR by subscriber
+    std::vector<uint32_t> h_tsub, h_tstart, h_tnode, h_tval;
+    // *out = the options of (topic, sub); TM_ENOENT when not subscribed, TM_EIO
+    // + tm_last_error() if the table is out of step with the bag
+    int find_subopts(const uint8_t* t, size_t len, uint32_t sub, tm_subopts** out);
+    // subscribe/3 (:127-136): new -> subscribe + store; subscribed already -> merge
+    int subscribe_opts(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest, const tm_subopts& o);
+    // set_subopts/2 (:388-393) for the fields of mask
+    int set_subopts(const uint8_t* t, size_t len, uint32_t sub, uint32_t mask, const tm_subopts& o);
+    // rebuilt by the rule of sync_subs, uploaded to a replica holding an older build
+    int sync_subopts(Replica& R);
+    // tm_batch_deliver: the batch's inboxes after ignore_local/3 and enrich_subopts/3
+    int batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_inboxes* out);
 
     // do_unsubscribe/4 (:179-191) + handle_cast({unsubscribed, Topic}) (:463-469):
     // the last subscriber of a topic deletes the node's route.

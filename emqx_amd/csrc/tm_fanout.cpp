@@ -130,21 +130,78 @@ int tm_engine::batch_routes(tm_batch* b, tm_routes* out) {
 }
 
 int tm_engine::subscribe(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest) {
+    return subscribe_opts(t, len, sub, node_dest, tm_subopts{});   // ?DEFAULT_SUBOPTS (include/emqx_mqtt.hrl:207-211)
+}
+
+int tm_engine::find_subopts(const uint8_t* t, size_t len, uint32_t sub, tm_subopts** out) {
+    *out = nullptr;
+    auto it = topics_of.find(sub);
+    if (it == topics_of.end()) return TM_ENOENT;
+    const std::string k((const char*)t, len);
+    auto ti = std::find(it->second.begin(), it->second.end(), k);
+    if (ti == it->second.end()) return TM_ENOENT;
+    auto oit = opts_of.find(sub);
+    if (oit == opts_of.end() || oit->second.size() != it->second.size()) {
+        snprintf(last_error(), 512, "subscriber %u: %zu topics, %zu option entries", sub, it->second.size(),
+                 oit == opts_of.end() ? (size_t)0 : oit->second.size());
+        return TM_EIO;
+    }
+    *out = &oit->second[(size_t)(ti - it->second.begin())];
+    return TM_OK;
+}
+
+int tm_engine::set_subopts(const uint8_t* t, size_t len, uint32_t sub, uint32_t mask, const tm_subopts& o) {
+    tm_subopts* cur;
+    if (int rc = find_subopts(t, len, sub, &cur)) return rc;   // TM_ENOENT: set_subopts/2's `false` (:392)
+    if (mask & TM_SUBOPT_QOS) cur->qos = o.qos;
+    if (mask & TM_SUBOPT_NL) {
+        nl_entries += o.nl;
+        nl_entries -= cur->nl;
+        cur->nl = o.nl;
+    }
+    if (mask & TM_SUBOPT_RAP) cur->rap = o.rap;
+    if (mask & TM_SUBOPT_RH) cur->rh = o.rh;
+    if (mask & TM_SUBOPT_SUBID) cur->subid = o.subid;
+    subopts_dirty = true;
+    return TM_OK;
+}
+
+int tm_engine::subscribe_opts(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest, const tm_subopts& o) {
     std::string k((const char*)t, len);
     auto it = topics_of.find(sub);
-    if (it != topics_of.end() && std::find(it->second.begin(), it->second.end(), k) != it->second.end())
-        return TM_OK;   // subscribed already: only subopts would change (:127-139)
+    if (it != topics_of.end() && std::find(it->second.begin(), it->second.end(), k) != it->second.end()) {
+        // subscribed already: only the subopts change (:127-139) -- maps:merge(Old, New),
+        // where New holds the four flags and a subid only when one was given (:139-142)
+        const uint32_t mask = TM_SUBOPT_QOS | TM_SUBOPT_NL | TM_SUBOPT_RAP | TM_SUBOPT_RH | (o.subid ? TM_SUBOPT_SUBID : 0u);
+        return set_subopts(t, len, sub, mask, o);
+    }
     auto sit = subs_of.find(k);
     if (sit == subs_of.end()) {
         int rc = route_add(t, len, node_dest);
         if (rc) return rc;
         sit = subs_of.emplace(k, std::vector<uint32_t>()).first;
     }
-    sit->second.push_back(sub);
-    topics_of[sub].push_back(std::move(k));
+    // the options first, and taken back if the bag's insert throws: opts_of[sub]
+    // and topics_of[sub] stay index for index
+    auto& os = opts_of[sub];
+    os.push_back(o);
+    try {
+        auto& ts = topics_of[sub];
+        ts.reserve(ts.size() + 1);
+        sit->second.push_back(sub);
+        ts.push_back(std::move(k));   // within the reserved capacity: does not throw
+    } catch (...) {
+        os.pop_back();
+        if (os.empty()) opts_of.erase(sub);
+        auto ti = topics_of.find(sub);
+        if (ti != topics_of.end() && ti->second.empty()) topics_of.erase(ti);
+        throw;
+    }
+    nl_entries += o.nl;
     max_sub = std::max(max_sub, sub);
     ++sub_entries;
     subs_dirty = true;
+    subopts_dirty = true;
     return TM_OK;
 }
 
@@ -155,6 +212,15 @@ int tm_engine::unsubscribe(const uint8_t* t, size_t len, uint32_t sub, uint32_t 
     auto& ts = it->second;
     auto ti = std::find(ts.begin(), ts.end(), k);
     if (ti == ts.end()) return TM_ENOENT;   // unsubscribe/1's `[] -> ok` (:170-177)
+    {   // ets:delete(?SUBOPTION, {SubPid, Topic}) (:179-181)
+        auto oit = opts_of.find(sub);
+        if (oit == opts_of.end() || oit->second.size() != ts.size()) return TM_EIO;
+        auto oi = oit->second.begin() + (ti - ts.begin());
+        nl_entries -= oi->nl;
+        oit->second.erase(oi);
+        if (oit->second.empty()) opts_of.erase(oit);
+        subopts_dirty = true;
+    }
     ts.erase(ti);
     if (ts.empty()) topics_of.erase(it);
     auto sit = subs_of.find(k);
@@ -443,6 +509,233 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     }
     out->subscribers = ib.h_sub.p; out->inbox_offsets = ib.h_off.p;
     out->publishes = ib.h_pub.p; out->filter_ids = ib.h_fid.p;
+    return TM_OK;
+}
+
+static_assert(DLV_UPGRADE_QOS == TM_DELIVER_UPGRADE_QOS && DLV_NL_ALL == TM_DELIVER_NL_ALL, "TM_DELIVER_* flags");
+static_assert(MSG_RETAIN == TM_MSG_RETAIN && MSG_RETAINED == TM_MSG_RETAINED && MSG_NL == TM_MSG_NL, "TM_MSG_* bits");
+static_assert(TM_SUBID_MAX >> (32 - SO_SUBID_SHIFT) == 0, "a subid fits the table's payload word");
+
+int tm_engine::sync_subopts(Replica& R) {
+    const size_t nn = nd.size();
+    if (subopts_dirty || subopts_version != version || subopts_nn != nn || h_tstart.empty()) {
+        h_tsub.clear();
+        h_tsub.reserve(topics_of.size());
+        for (const auto& kv : topics_of) h_tsub.push_back(kv.first);
+        std::sort(h_tsub.begin(), h_tsub.end());
+        h_tstart.assign(h_tsub.size() + 1, 0);
+        h_tnode.clear();
+        h_tval.clear();
+        h_tnode.reserve(sub_entries);
+        h_tval.reserve(sub_entries);
+        std::vector<std::pair<uint32_t, uint32_t>> row;
+        for (size_t s = 0; s < h_tsub.size(); ++s) {
+            const auto& ts = topics_of[h_tsub[s]];
+            const auto& os = opts_of[h_tsub[s]];
+            if (os.size() != ts.size()) {
+                snprintf(last_error(), 512, "subscriber %u: %zu topics, %zu option entries", h_tsub[s], ts.size(), os.size());
+                return TM_EIO;
+            }
+            row.clear();
+            for (size_t i = 0; i < ts.size(); ++i) {
+                const uint32_t n = node_of((const uint8_t*)ts[i].data(), ts[i].size());
+                if (n == NONE || n >= nn) continue;   // not in the trie: no route, no dispatch (sync_subs)
+                const tm_subopts& o = os[i];
+                row.emplace_back(n, o.subid << SO_SUBID_SHIFT | (o.rap ? SO_RAP : 0u) | (o.nl ? SO_NL : 0u) | (o.qos & SO_QOS));
+            }
+            std::sort(row.begin(), row.end());
+            h_tstart[s] = (uint32_t)h_tnode.size();
+            for (const auto& e : row) {
+                h_tnode.push_back(e.first);
+                h_tval.push_back(e.second);
+            }
+        }
+        h_tstart[h_tsub.size()] = (uint32_t)h_tnode.size();
+        subopts_dirty = false;
+        subopts_version = version;
+        subopts_nn = (uint32_t)nn;
+        ++subopts_gen;
+    }
+    if (R.subopts_gen == subopts_gen) return TM_OK;
+    const size_t ns = h_tsub.size(), nt = h_tnode.size();
+    int rc;
+    if ((rc = R.tab.d_tsub.reserve(std::max<size_t>(ns, 1)))) return rc;
+    if ((rc = R.tab.d_tstart.reserve(ns + 1))) return rc;
+    if ((rc = R.tab.d_tnode.reserve(std::max<size_t>(nt, 1)))) return rc;
+    if ((rc = R.tab.d_tval.reserve(std::max<size_t>(nt, 1)))) return rc;
+    if (ns) HIP_OK(hipMemcpyAsync(R.tab.d_tsub.p, h_tsub.data(), ns * 4, hipMemcpyHostToDevice, R.stream));
+    HIP_OK(hipMemcpyAsync(R.tab.d_tstart.p, h_tstart.data(), (ns + 1) * 4, hipMemcpyHostToDevice, R.stream));
+    if (nt) {
+        HIP_OK(hipMemcpyAsync(R.tab.d_tnode.p, h_tnode.data(), nt * 4, hipMemcpyHostToDevice, R.stream));
+        HIP_OK(hipMemcpyAsync(R.tab.d_tval.p, h_tval.data(), nt * 4, hipMemcpyHostToDevice, R.stream));
+    }
+    HIP_OK(hipStreamSynchronize(R.stream));
+    R.subopts_gen = subopts_gen;
+    return TM_OK;
+}
+
+int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_inboxes* out) {
+    auto einval = [](const char* msg) {
+        snprintf(last_error(), 512, "%s", msg);
+        return TM_EINVAL;
+    };
+    if (!b->done) return einval("tm_batch_deliver: the batch has not been waited for");
+    if (b->dedup) return einval("tm_batch_deliver: a TM_BATCH_DEDUP batch (a delivery names a publish)");
+    const uint32_t n = b->n;
+    if (o->msg)
+        for (uint32_t i = 0; i < n; ++i)
+            if ((o->msg[i] & ~0xFu) || (o->msg[i] & 3u) == 3u) {
+                snprintf(last_error(), 512, "tm_batch_deliver: msg[%u] = 0x%02x (QoS 3 or bits above 3)", i, o->msg[i]);
+                return TM_EINVAL;
+            }
+    const bool device = o->flags & TM_DELIVER_DEVICE, want_subids = o->flags & TM_DELIVER_SUBIDS;
+    // nothing can drop without a publisher or without a No-Local subscription
+    const bool can_drop = o->from && nl_entries > 0;
+    tm_inboxes ibx{};
+    int rc;
+    if ((rc = batch_inboxes(b, (device || can_drop) ? TM_INBOX_DEVICE : 0u, &ibx))) return rc;   // returns with the stream idle
+    Replica& R = *b->rep;
+    const hipStream_t stream = R.stream;
+    tm_batch::Inbox& ib = b->inbox;
+    tm_batch::Deliver& dv = b->dlv;
+    const uint32_t D = (uint32_t)ibx.n_deliveries, nsub = ibx.n_subscribers;
+    const size_t dd = std::max<size_t>(D, 1);
+    *out = tm_session_inboxes{};
+    out->n_topics = n;
+    if ((rc = dv.d_msg.reserve(dd))) return rc;
+    if ((rc = dv.h_msg.reserve(dd))) return rc;
+    if (want_subids) {
+        if ((rc = dv.d_subid.reserve(dd))) return rc;
+        if ((rc = dv.h_subid.reserve(dd))) return rc;
+    }
+    if (!D) {   // no delivery: n_subscribers = 0, inbox_offsets = {0}
+        if (device) {
+            out->inbox_offsets = ib.d_off.p;
+            out->subscribers = ib.d_sub.p; out->publishes = ib.d_pub.p; out->filter_ids = ib.d_fid.p;
+            out->msg = dv.d_msg.p; out->subids = want_subids ? dv.d_subid.p : nullptr;
+            return TM_OK;
+        }
+        if ((rc = dv.h_off.reserve(1))) return rc;
+        if ((rc = dv.h_sub.reserve(1))) return rc;
+        dv.h_off.p[0] = 0;
+        out->inbox_offsets = dv.h_off.p;
+        out->subscribers = out->publishes = out->filter_ids = dv.h_sub.p;
+        out->msg = dv.h_msg.p; out->subids = want_subids ? dv.h_subid.p : nullptr;
+        return TM_OK;
+    }
+    if ((rc = sync_subopts(R))) return rc;
+    const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
+    if ((rc = dv.d_rng.reserve(nsub))) return rc;
+    if ((rc = dv.d_first.reserve(nsub))) return rc;
+    if ((rc = dv.d_tot.reserve(4))) return rc;
+    if ((rc = dv.h_tot.reserve(4))) return rc;
+    if ((rc = dv.dev0.create())) return rc;
+    if ((rc = dv.dev1.create())) return rc;
+    DeliverArgs a{};
+    a.keys = ibx.passes & 1 ? ib.d_key1.p : b->fan.d_fout.p;   // where the sort left the pairs
+    a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
+    a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
+    a.D = D; a.R = nsub; a.n = n; a.ntiles = ntiles;
+    a.tsub = R.tab.d_tsub.p; a.tstart = R.tab.d_tstart.p; a.tnode = R.tab.d_tnode.p; a.tval = R.tab.d_tval.p;
+    a.T = (uint32_t)h_tnode.size(); a.NS = (uint32_t)h_tsub.size();
+    a.flags = o->flags;
+    a.rng = dv.d_rng.p; a.first = dv.d_first.p;
+    a.err = dv.d_tot.p + 2; a.d_tot = dv.d_tot.p;
+    if (o->msg) {
+        if ((rc = dv.d_min.reserve(n))) return rc;
+        if ((rc = dv.h_min.reserve(n))) return rc;
+        memcpy(dv.h_min.p, o->msg, n);
+        HIP_OK(hipMemcpyAsync(dv.d_min.p, dv.h_min.p, n, hipMemcpyHostToDevice, stream));
+        a.msg = dv.d_min.p;
+    }
+    if (can_drop) {
+        if ((rc = dv.d_from.reserve(n))) return rc;
+        if ((rc = dv.h_from.reserve(n))) return rc;
+        memcpy(dv.h_from.p, o->from, (size_t)n * 4);
+        HIP_OK(hipMemcpyAsync(dv.d_from.p, dv.h_from.p, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+        a.from = dv.d_from.p;
+        if ((rc = dv.d_own.reserve(dd))) return rc;
+        if ((rc = dv.d_emsg.reserve(dd))) return rc;
+        if (want_subids && (rc = dv.d_esubid.reserve(dd))) return rc;
+        if ((rc = dv.d_kcount.reserve((size_t)ntiles + 1))) return rc;
+        if ((rc = dv.d_kbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
+        if ((rc = dv.d_ncount.reserve((size_t)ntiles + 1))) return rc;
+        if ((rc = dv.d_nbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
+        if ((rc = dv.d_sub.reserve(nsub))) return rc;
+        if ((rc = dv.d_off.reserve((size_t)nsub + 1))) return rc;
+        if ((rc = dv.d_pub.reserve(dd))) return rc;
+        if ((rc = dv.d_fid.reserve(dd))) return rc;
+        a.own = dv.d_own.p; a.emsg = dv.d_emsg.p; a.esubid = want_subids ? dv.d_esubid.p : nullptr;
+        a.kcount = dv.d_kcount.p; a.kbs = dv.d_kbs.p; a.ncount = dv.d_ncount.p; a.nbs = dv.d_nbs.p;
+        a.o_sub = dv.d_sub.p; a.o_off = dv.d_off.p; a.o_pub = dv.d_pub.p; a.o_fid = dv.d_fid.p;
+        a.o_msg = dv.d_msg.p; a.o_subid = want_subids ? dv.d_subid.p : nullptr;
+    } else {   // the enriched bytes are the result; the other four arrays are the inboxes'
+        a.emsg = dv.d_msg.p; a.esubid = want_subids ? dv.d_subid.p : nullptr;
+    }
+    HIP_OK(hipMemsetAsync(dv.d_tot.p, 0, 16, stream));
+    HIP_OK(hipEventRecord(dv.dev0.e, stream));
+    HIP_OK(launch_deliver_flags(a, can_drop, stream));
+    if (can_drop) HIP_OK(launch_deliver_compact(a, stream));
+    HIP_OK(hipEventRecord(dv.dev1.e, stream));
+    HIP_OK(hipMemcpyAsync(dv.h_tot.p, dv.d_tot.p, 16, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipEventElapsedTime(&out->kernel_ms, dv.dev0.e, dv.dev1.e));
+    if (dv.h_tot.p[2]) {
+        snprintf(last_error(), 512, "tm_batch_deliver: %u of %u deliveries without subscription options", dv.h_tot.p[2], D);
+        return TM_EIO;
+    }
+    uint32_t left = D, rleft = nsub;
+    if (can_drop) {
+        left = dv.h_tot.p[0];
+        rleft = dv.h_tot.p[1];
+        if (left > D || rleft > nsub || (left == 0) != (rleft == 0)) {
+            snprintf(last_error(), 512, "inconsistent session inboxes: %u of %u deliveries, %u of %u subscribers", left, D,
+                     rleft, nsub);
+            return TM_EIO;
+        }
+    }
+    out->n_subscribers = rleft;
+    out->n_deliveries = left;
+    out->n_dropped_no_local = D - left;
+    if (device) {
+        out->subscribers = can_drop ? dv.d_sub.p : ib.d_sub.p;
+        out->inbox_offsets = can_drop ? dv.d_off.p : ib.d_off.p;
+        out->publishes = can_drop ? dv.d_pub.p : ib.d_pub.p;
+        out->filter_ids = can_drop ? dv.d_fid.p : ib.d_fid.p;
+        out->msg = dv.d_msg.p;
+        out->subids = want_subids ? dv.d_subid.p : nullptr;
+        return TM_OK;
+    }
+    if (left) {
+        HIP_OK(hipMemcpyAsync(dv.h_msg.p, dv.d_msg.p, left, hipMemcpyDeviceToHost, stream));
+        if (want_subids) HIP_OK(hipMemcpyAsync(dv.h_subid.p, dv.d_subid.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
+    }
+    if (can_drop) {
+        if ((rc = dv.h_sub.reserve(std::max<size_t>(rleft, 1)))) return rc;
+        if ((rc = dv.h_off.reserve((size_t)rleft + 1))) return rc;
+        if ((rc = dv.h_pub.reserve(dd))) return rc;
+        if ((rc = dv.h_fid.reserve(dd))) return rc;
+        if (rleft) {
+            HIP_OK(hipMemcpyAsync(dv.h_off.p, dv.d_off.p, ((size_t)rleft + 1) * 4, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpyAsync(dv.h_sub.p, dv.d_sub.p, (size_t)rleft * 4, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpyAsync(dv.h_pub.p, dv.d_pub.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
+            HIP_OK(hipMemcpyAsync(dv.h_fid.p, dv.d_fid.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
+        }
+        HIP_OK(hipStreamSynchronize(stream));
+        if (!rleft) dv.h_off.p[0] = 0;
+        if (dv.h_off.p[rleft] != left) {
+            snprintf(last_error(), 512, "inconsistent session inbox offsets: %u vs %u", dv.h_off.p[rleft], left);
+            return TM_EIO;
+        }
+        out->subscribers = dv.h_sub.p; out->inbox_offsets = dv.h_off.p;
+        out->publishes = dv.h_pub.p; out->filter_ids = dv.h_fid.p;
+    } else {
+        HIP_OK(hipStreamSynchronize(stream));
+        out->subscribers = ibx.subscribers; out->inbox_offsets = ibx.inbox_offsets;
+        out->publishes = ibx.publishes; out->filter_ids = ibx.filter_ids;
+    }
+    out->msg = dv.h_msg.p;
+    out->subids = want_subids ? dv.h_subid.p : nullptr;
     return TM_OK;
 }
 

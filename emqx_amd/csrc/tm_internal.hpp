@@ -401,6 +401,58 @@ struct InboxArgs {
     uint32_t* inbox_offsets;  // rcap + 1
 };
 
+// What the session sends (tm_batch_deliver): the inboxes above after
+// emqx_channel:ignore_local/3 and emqx_session:enrich_subopts/3.  The device
+// image of the ?SUBOPTION table is a CSR by subscriber:
+//   tsub[s]    the subscribers that hold a subscription, ascending (NS)
+//   tstart[s]  subscriptions tstart[s] .. tstart[s + 1] of tnode / tval (NS + 1)
+//   tnode[k]   trie node id (the filter id of a delivery), ascending inside a subscriber's range
+//   tval[k]    subid << 4 | rap << 3 | nl << 2 | qos (a subid has 28 bits)
+// One search of tsub per inbox (tm_deliver_range), then every delivery
+// searches only its subscriber's range.
+constexpr uint32_t SO_QOS = 3u, SO_NL = 4u, SO_RAP = 8u, SO_SUBID_SHIFT = 4;
+constexpr uint8_t DLV_KEEP = 1, DLV_HEAD = 2;   // DeliverArgs::own after tm_deliver_count
+// TM_DELIVER_UPGRADE_QOS / TM_DELIVER_NL_ALL and TM_MSG_* (tm_fanout.cpp asserts them)
+constexpr uint32_t DLV_UPGRADE_QOS = 2u, DLV_NL_ALL = 4u;
+constexpr uint32_t MSG_QOS = 3u, MSG_RETAIN = 4u, MSG_RETAINED = 8u, MSG_NL = 8u;
+struct DeliverArgs {
+    // the batch's inboxes: the sorted keys (subscriber of delivery q), the
+    // result arrays and the finish's scanned head counts per tile
+    const uint32_t* keys;          // D
+    const uint32_t* publishes;     // D
+    const uint32_t* filter_ids;    // D
+    const uint32_t* subscribers;   // R
+    const uint32_t* hcount;        // ntiles + 1 (+ hcbs[tile / SCAN_TILE])
+    const uint32_t* hcbs;
+    uint32_t D, R, n, ntiles;
+    const uint32_t* tsub;
+    const uint32_t* tstart;
+    const uint32_t* tnode;
+    const uint32_t* tval;
+    uint32_t T, NS;
+    const uint32_t* from;          // n, or null: nobody's own
+    const uint8_t* msg;            // n, or null: all 0
+    uint32_t flags;                // TM_DELIVER_*
+    uint32_t pad0;
+    uint2* rng;                    // R: the table range of inbox r
+    uint32_t* first;               // R: the first delivery of inbox r that is not own (NONE: every one is)
+    uint8_t* own;                  // D: 1 = own; after tm_deliver_count DLV_KEEP | DLV_HEAD
+    uint8_t* emsg;                 // D: the enriched byte of every delivery
+    uint32_t* esubid;              // D, or null
+    uint32_t* err;                 // [0]: lookups that found nothing or indices out of range
+    uint32_t* kcount;              // ntiles + 1: deliveries left per tile, scanned in place (+ kbs)
+    uint32_t* kbs;
+    uint32_t* ncount;              // ntiles + 1: inbox heads left per tile, scanned in place (+ nbs)
+    uint32_t* nbs;
+    uint32_t* d_tot;               // [0] = D', [1] = R'
+    uint32_t* o_sub;               // R
+    uint32_t* o_off;               // R + 1
+    uint32_t* o_pub;               // D
+    uint32_t* o_fid;               // D
+    uint8_t* o_msg;                // D
+    uint32_t* o_subid;             // D, or null
+};
+
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
 struct RulesArgs {
     const uint32_t* nwords;   // name word ids (rule dictionary; unknown = W_UNKNOWN)
@@ -489,6 +541,11 @@ hipError_t launch_fan_fill(const FanArgs& a, hipStream_t s);   // a.out_j set: a
 hipError_t launch_inbox_pubof(const InboxArgs& a, hipStream_t s);
 hipError_t launch_inbox_sort(const InboxArgs& a, hipStream_t s);
 hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s);
+// deliver: the options of every delivery and its enriched byte (drop: also
+// own / first); then, when something can drop, count + scans + the stable
+// compaction into o_*
+hipError_t launch_deliver_flags(const DeliverArgs& a, bool drop, hipStream_t s);
+hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s);
 hipError_t launch_fan_globalize(const FanArgs& a, hipStream_t s);   // block-relative moff -> global
 uint32_t fan_scan_tile();   // match entries per scan block
 uint32_t fan_fill_tile();   // deliveries per fill block

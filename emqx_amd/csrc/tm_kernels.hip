@@ -2342,6 +2342,213 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_heads(InboxArgs a, const
     }
 }
 
+// ------------------------------------- what the session sends (tm_batch_deliver)
+//
+// emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693) and
+// emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529) over the
+// batch's inboxes.  The kernels walk the deliveries in the sort's tiles (wave
+// w of tile t owns pairs [4096 t + 1024 w, + 1024), 64 consecutive pairs per
+// round), so a delivery's inbox index is a count of the inbox heads before it:
+// the finish's scanned per-tile head counts, the earlier waves of the tile
+// (LDS), the earlier rounds and the lower lanes (ballots).
+//   range    one search of the table's subscribers per inbox
+//   flags    per delivery: its options (a search inside the inbox's range),
+//            the enriched byte, own / not own; per inbox the first delivery
+//            that is not own (atomicMin, at most one per inbox and wave round,
+//            skipped when the minimum read beforehand is lower already: a '#'
+//            subscriber's inbox spans thousands of waves)
+//   count    keep = not own, or (default mode) behind the inbox's first not-own
+//            delivery; that delivery is the head of what is left of the inbox
+//   scans    deliveries and heads left per tile (the project's two-level scan)
+//   scatter  the stable compaction
+// No kernel waits for another workgroup.
+
+// Heads among the wave's pairs -> hw[wave]; returns the heads before the wave's
+// first pair.  Every thread of the block calls it.
+__device__ __forceinline__ uint32_t dlv_heads_before(const DeliverArgs& a, uint32_t* hw, uint64_t wbase) {
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t mine = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint32_t ky = on ? a.keys[q] : 0u;
+        const uint32_t kp = (on && q) ? a.keys[q - 1] : ~ky;
+        mine += (uint32_t)__popcll(__ballot(on && ky != kp));
+    }
+    if (lane == 0) hw[w] = mine;
+    __syncthreads();
+    uint32_t base = a.hcount[blockIdx.x] + a.hcbs[blockIdx.x / SCAN_TILE];
+    for (uint32_t k = 0; k < w; ++k) base += hw[k];
+    return base;
+}
+
+__global__ __launch_bounds__(256) void tm_deliver_range(DeliverArgs a) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint32_t S = a.subscribers[r];
+    uint32_t lo = 0, hi = a.NS;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.tsub[mid] < S) lo = mid + 1; else hi = mid;
+    }
+    uint2 g = make_uint2(0u, 0u);
+    if (lo < a.NS && a.tsub[lo] == S) {
+        g.y = min(a.tstart[lo + 1], a.T);
+        g.x = min(a.tstart[lo], g.y);
+    } else {
+        atomicAdd(a.err, 1u);   // a subscriber of the fan-out without options: TM_EIO
+    }
+    a.rng[r] = g;
+    a.first[r] = NONE;
+}
+
+template <bool DROP>
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_flags(DeliverArgs a) {
+    __shared__ uint32_t hw[INBOX_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t wbase = (uint64_t)blockIdx.x * INBOX_TILE + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t hb = dlv_heads_before(a, hw, wbase);
+    const bool upgrade = a.flags & DLV_UPGRADE_QOS;
+    uint32_t bad = 0;
+#pragma unroll 2
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint32_t S = on ? a.keys[q] : 0u;
+        const uint32_t kp = (on && q) ? a.keys[q - 1] : ~S;
+        const uint64_t hm = __ballot(on && S != kp);
+        // heads at or before me, less one
+        const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
+        hb += (uint32_t)__popcll(hm);
+        bool ok = on && ri < a.R;
+        uint32_t v = 0, p = NONE;
+        if (ok) {
+            p = a.publishes[q];
+            const uint32_t f = a.filter_ids[q];
+            const uint2 g = a.rng[ri];
+            uint32_t lo = g.x, hi = min(g.y, a.T);
+            const uint32_t end = hi;
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (a.tnode[mid] < f) lo = mid + 1; else hi = mid;
+            }
+            if (lo < end && a.tnode[lo] == f) v = a.tval[lo]; else ok = false;
+            if (p >= a.n) ok = false;
+        }
+        if (on && !ok) ++bad;
+        const uint32_t pm = (ok && a.msg) ? a.msg[p] : 0u;
+        const uint32_t sq = v & SO_QOS, pq = pm & MSG_QOS;
+        const uint32_t qos = upgrade ? max(sq, pq) : min(sq, pq);
+        const bool retain = (pm & MSG_RETAIN) && ((v & SO_RAP) || (pm & MSG_RETAINED));
+        if (on) {
+            a.emsg[q] = (uint8_t)(qos | (retain ? MSG_RETAIN : 0u) | ((v & SO_NL) ? MSG_NL : 0u));
+            if (a.esubid) a.esubid[q] = v >> SO_SUBID_SHIFT;
+        }
+        if (DROP) {
+            const uint32_t fr = (ok && a.from) ? a.from[p] : NONE;
+            const bool own = ok && (v & SO_NL) && fr != NONE && fr == S;
+            if (on) a.own[q] = own ? 1 : 0;
+            // the first not-own delivery of my inbox inside this round: no
+            // not-own lane between my inbox's first lane of the round and me
+            const bool cand = ok && !own;
+            const uint64_t nz = __ballot(cand);
+            const uint64_t upto = ~0ull >> (63u - lane);   // lanes 0 .. lane
+            const uint32_t s = 63u - (uint32_t)__clzll((hm | 1ull) & upto);
+            const uint64_t before = nz & (upto >> 1) & ~((1ull << s) - 1ull);
+            if (cand && !before) {
+                uint32_t* slot = a.first + ri;
+                if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > (uint32_t)q)
+                    atomicMin(slot, (uint32_t)q);
+            }
+        }
+    }
+    if (bad) atomicAdd(a.err, bad);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_count(DeliverArgs a) {
+    __shared__ uint32_t hw[INBOX_BLOCK / 64], kw[INBOX_BLOCK / 64], nw[INBOX_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t wbase = (uint64_t)blockIdx.x * INBOX_TILE + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t hb = dlv_heads_before(a, hw, wbase);
+    const bool all = a.flags & DLV_NL_ALL;
+    uint32_t kept = 0, heads = 0;
+#pragma unroll 2
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint32_t S = on ? a.keys[q] : 0u;
+        const uint32_t kp = (on && q) ? a.keys[q - 1] : ~S;
+        const uint64_t hm = __ballot(on && S != kp);
+        const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
+        hb += (uint32_t)__popcll(hm);
+        const bool ok = on && ri < a.R;
+        const uint32_t fst = ok ? a.first[ri] : NONE;
+        const bool own = ok && a.own[q];
+        const bool keep = ok && (!own || (!all && (uint32_t)q > fst));
+        const bool head = keep && (uint32_t)q == fst;
+        if (on) a.own[q] = (uint8_t)((keep ? DLV_KEEP : 0) | (head ? DLV_HEAD : 0));
+        kept += (uint32_t)__popcll(__ballot(keep));
+        heads += (uint32_t)__popcll(__ballot(head));
+    }
+    if (lane == 0) { kw[w] = kept; nw[w] = heads; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.kcount[blockIdx.x] = kw[0] + kw[1] + kw[2] + kw[3];
+        a.ncount[blockIdx.x] = nw[0] + nw[1] + nw[2] + nw[3];
+    }
+}
+static_assert(INBOX_BLOCK / 64 == 4, "four waves per tile");
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_scatter(DeliverArgs a) {
+    __shared__ uint32_t kw[INBOX_BLOCK / 64], nw[INBOX_BLOCK / 64];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t wbase = (uint64_t)blockIdx.x * INBOX_TILE + (uint64_t)w * INBOX_WAVE_PAIRS;
+    uint32_t kept = 0, heads = 0;
+    // (both loops stay short of fully unrolled: seventeen pointers are live, and
+    // unrolled further the kernel spills SGPRs)
+#pragma unroll 4
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const uint32_t fl = q < a.D ? a.own[q] : 0u;
+        kept += (uint32_t)__popcll(__ballot(fl & DLV_KEEP));
+        heads += (uint32_t)__popcll(__ballot(fl & DLV_HEAD));
+    }
+    if (lane == 0) { kw[w] = kept; nw[w] = heads; }
+    __syncthreads();
+    uint32_t kb = a.kcount[blockIdx.x] + a.kbs[blockIdx.x / SCAN_TILE];
+    uint32_t nb = a.ncount[blockIdx.x] + a.nbs[blockIdx.x / SCAN_TILE];
+    for (uint32_t k = 0; k < w; ++k) { kb += kw[k]; nb += nw[k]; }
+#pragma unroll 1
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const uint32_t fl = q < a.D ? a.own[q] : 0u;
+        const uint64_t km = __ballot(fl & DLV_KEEP), hm = __ballot(fl & DLV_HEAD);
+        if (fl & DLV_KEEP) {
+            const uint32_t pos = kb + inbox_mbcnt(km);
+            if (pos < a.D) {
+                a.o_pub[pos] = a.publishes[q];
+                a.o_fid[pos] = a.filter_ids[q];
+                a.o_msg[pos] = a.emsg[q];
+                if (a.o_subid) a.o_subid[pos] = a.esubid[q];
+                if (fl & DLV_HEAD) {
+                    const uint32_t i = nb + inbox_mbcnt(hm);
+                    if (i < a.R) {
+                        a.o_sub[i] = a.keys[q];
+                        a.o_off[i] = pos;
+                    }
+                }
+            }
+        }
+        kb += (uint32_t)__popcll(km);
+        nb += (uint32_t)__popcll(hm);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint32_t left = a.d_tot[1];
+        if (left <= a.R) a.o_off[left] = a.d_tot[0];
+    }
+}
+
 // ------------------------------------------ batched predicate (emqx_topic:match/2)
 
 // One thread per name, all rules: the word-by-word clauses of
@@ -4017,6 +4224,29 @@ hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s) {
     const hipError_t e = launch_scan(sa, s, a.d_R);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tm_inbox_heads, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_deliver_flags(const DeliverArgs& a, bool drop, hipStream_t s) {
+    if (!a.D || !a.R || !a.ntiles) return hipGetLastError();
+    hipLaunchKernelGGL(tm_deliver_range, dim3((a.R + 255) / 256), dim3(256), 0, s, a);
+    if (drop)
+        hipLaunchKernelGGL(tm_deliver_flags<true>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    else
+        hipLaunchKernelGGL(tm_deliver_flags<false>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s) {
+    if (!a.D || !a.R || !a.ntiles) return hipGetLastError();
+    hipLaunchKernelGGL(tm_deliver_count, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    ScanArgs sk{}, sn{};
+    sk.count = a.kcount; sk.row_off = a.kcount; sk.block_sums = a.kbs; sk.n = a.ntiles;   // in place
+    sn.count = a.ncount; sn.row_off = a.ncount; sn.block_sums = a.nbs; sn.n = a.ntiles;
+    hipError_t e = launch_scan(sk, s, a.d_tot);
+    if (e != hipSuccess) return e;
+    if ((e = launch_scan(sn, s, a.d_tot + 1)) != hipSuccess) return e;
+    hipLaunchKernelGGL(tm_deliver_scatter, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

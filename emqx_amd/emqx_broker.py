@@ -49,12 +49,17 @@ _nsubs = {}       # topic -> local subscriber count
 _order = {}       # topic -> [subscriber term], subscription order
 
 
-def subscribe(topic: bytes, pid="self"):
-    """subscribe/1,2 -> do_subscribe/4, non-shared clause (:117-158)."""
+def subscribe(topic: bytes, pid="self", subopts=None):
+    """subscribe/1,2,3 -> do_subscribe/4, non-shared clause (:117-158).
+    subopts: {qos, nl, rap, rh, subid}, merged over ?DEFAULT_SUBOPTS (:127-136);
+    on an existing subscription only the options change (set_subopts/2)."""
     if not isinstance(topic, (bytes, bytearray)):
         raise TypeError("function_clause")
     topic, sid = bytes(topic), _sid(pid)
-    R.engine().subscribe(topic, sid, _node_dest())
+    if subopts is None:
+        R.engine().subscribe(topic, sid, _node_dest())
+    else:
+        R.engine().subscribe_opts(topic, sid, dict(subopts), _node_dest())
     ts = _topics_of.setdefault(sid, [])
     if topic not in ts:
         ts.append(topic)
@@ -95,6 +100,22 @@ def subscriber_down(pid) -> int:
     for t in list(_topics_of.get(sid, [])):
         _dropped(t, sid)
     return n
+
+
+def get_subopts(pid, topic: bytes):
+    """get_subopts/2 (:373-386): the options map, or None for `undefined`."""
+    return R.engine().get_subopts(bytes(topic), _sid(pid))
+
+
+def set_subopts(topic: bytes, newopts: dict, pid="self") -> bool:
+    """set_subopts/2 (:388-393): maps:merge(Old, New); False when not subscribed."""
+    return R.engine().set_subopts(bytes(topic), _sid(pid), dict(newopts))
+
+
+def subscriptions(pid):
+    """subscriptions/1 (:349-356): [(Topic, SubOpts)] of pid, in subscription order."""
+    sid = _sid(pid)
+    return [(t, R.engine().get_subopts(t, sid)) for t in _topics_of.get(sid, [])]
 
 
 def subscribers(topic: bytes):

@@ -206,6 +206,55 @@ class Batch:
         return (int(d.n_subscribers), int(d.n_deliveries), float(d.kernel_ms), int(d.passes), ptr(d.subscribers),
                 ptr(d.inbox_offsets), ptr(d.publishes), ptr(d.filter_ids))
 
+    def deliver(self, from_=None, msg=None, upgrade_qos: bool = False, nl_all: bool = False, subids: bool = False):
+        """What the session sends (tm_batch_deliver): inboxes() after
+        ignore_local/3 and enrich_subopts/3.  from_: u32[n] publisher of every
+        publish (TM_NONE = none; None = nobody), msg: u8[n] QoS | TM_MSG_RETAIN
+        | TM_MSG_RETAINED -> (subscribers u32[R'], offsets u32[R'+1], publishes
+        u32[D'], filter_ids u32[D'], msg u8[D'], subids u32[D'] or None);
+        deliver_info holds n_dropped_no_local and kernel_ms."""
+        d, _keep = self._deliver(from_, msg, self._deliver_flags(upgrade_qos, nl_all, subids))
+        r, t = int(d.n_subscribers), int(d.n_deliveries)
+        cp = lambda p, k, ty=np.uint32: (np.ctypeslib.as_array(p, shape=(k,)).copy() if k  # noqa: E731
+                                         else np.zeros(0, ty))
+        self.deliver_info = {"kernel_ms": float(d.kernel_ms), "n_dropped_no_local": int(d.n_dropped_no_local)}
+        return (cp(d.subscribers, r), cp(d.inbox_offsets, r + 1), cp(d.publishes, t), cp(d.filter_ids, t),
+                cp(d.msg, t, np.uint8), cp(d.subids, t) if subids else None)
+
+    def deliver_device(self, from_=None, msg=None, upgrade_qos: bool = False, nl_all: bool = False,
+                       subids: bool = False):
+        """TM_DELIVER_DEVICE: -> (n_subscribers, n_deliveries, n_dropped_no_local,
+        kernel ms, device ptrs subscribers / offsets / publishes / filter_ids /
+        msg / subids (None without subids))."""
+        d, _keep = self._deliver(from_, msg, self._deliver_flags(upgrade_qos, nl_all, subids) | N.TM_DELIVER_DEVICE)
+        ptr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        return (int(d.n_subscribers), int(d.n_deliveries), int(d.n_dropped_no_local), float(d.kernel_ms),
+                ptr(d.subscribers), ptr(d.inbox_offsets), ptr(d.publishes), ptr(d.filter_ids), ptr(d.msg),
+                ptr(d.subids) if subids else None)
+
+    @staticmethod
+    def _deliver_flags(upgrade_qos: bool, nl_all: bool, subids: bool) -> int:
+        return ((N.TM_DELIVER_UPGRADE_QOS if upgrade_qos else 0) | (N.TM_DELIVER_NL_ALL if nl_all else 0)
+                | (N.TM_DELIVER_SUBIDS if subids else 0))
+
+    def _deliver(self, from_, msg, flags: int):
+        o = N.DeliverOpts()
+        o.flags = flags
+        keep = []
+        for name, val, ty in (("from_", from_, np.uint32), ("msg", msg, np.uint8)):
+            if val is None:
+                continue
+            a = np.ascontiguousarray(np.asarray(val, dtype=ty))
+            if len(a) != self.n:
+                raise ValueError(f"{len(a)} {name.rstrip('_')} entries for {self.n} publishes")
+            if not len(a):
+                a = np.zeros(1, ty)
+            keep.append(a)
+            setattr(o, name, a.ctypes.data)
+        d = N.SessionInboxes()
+        N.check(self.eng.L.tm_batch_deliver(self.eng.h, self.h, C.byref(o), C.byref(d)), "tm_batch_deliver")
+        return d, keep
+
     def _inboxes(self, flags: int) -> "N.Inboxes":
         d = N.Inboxes()
         N.check(self.eng.L.tm_batch_inboxes(self.eng.h, self.h, flags, C.byref(d)), "tm_batch_inboxes")
@@ -729,6 +778,49 @@ class Engine:
     # ---- subscribers (emqx_broker subscribe/unsubscribe/subscriber_down) ------
     def subscribe(self, topic: bytes, sub: int, node_dest: int = 0):
         N.check(self.L.tm_subscribe(self.h, topic, len(topic), sub, node_dest), "tm_subscribe")
+
+    # ---- the ?SUBOPTION table (emqx_broker subscribe/3, set_subopts/2, get_subopts/2) --
+    @staticmethod
+    def _subopts(opts) -> "N.SubOpts":
+        opts = opts or {}
+        unknown = set(opts) - set(N.SUBOPT_MASKS)
+        if unknown:
+            raise ValueError(f"unknown subscription options {sorted(unknown)}")
+        vals = {k: int(v) for k, v in opts.items()}
+        for k, v in vals.items():   # ctypes would wrap a value past the field's width before the C range check
+            if not 0 <= v <= (N.TM_SUBID_MAX if k == "subid" else 255):
+                raise ValueError(f"subscription option {k} = {v} out of range")
+        return N.SubOpts(**vals)
+
+    def subscribe_opts(self, topic: bytes, sub: int, opts=None, node_dest: int = 0):
+        """subscribe/3: opts = {qos, nl, rap, rh, subid} (missing = default;
+        None = all defaults).  An existing subscription merges: the four flags
+        are replaced, the subid only when non-zero."""
+        o = self._subopts(opts)
+        N.check(self.L.tm_subscribe_opts(self.h, topic, len(topic), sub, node_dest, C.byref(o) if opts is not None
+                                         else None), "tm_subscribe_opts")
+
+    def set_subopts(self, topic: bytes, sub: int, opts: dict) -> bool:
+        """set_subopts/2 for a partial map: only the keys of opts change.
+        False when not subscribed."""
+        o = self._subopts(opts)
+        mask = 0
+        for k in opts:
+            mask |= N.SUBOPT_MASKS[k]
+        rc = self.L.tm_set_subopts(self.h, topic, len(topic), sub, mask, C.byref(o))
+        if rc == N.TM_ENOENT:
+            return False
+        N.check(rc, "tm_set_subopts")
+        return True
+
+    def get_subopts(self, topic: bytes, sub: int):
+        """get_subopts/2: {qos, nl, rap, rh, subid}, or None when not subscribed."""
+        o = N.SubOpts()
+        rc = self.L.tm_get_subopts(self.h, topic, len(topic), sub, C.byref(o))
+        if rc == N.TM_ENOENT:
+            return None
+        N.check(rc, "tm_get_subopts")
+        return o.asdict()
 
     def unsubscribe(self, topic: bytes, sub: int, node_dest: int = 0) -> bool:
         rc = self.L.tm_unsubscribe(self.h, topic, len(topic), sub, node_dest)

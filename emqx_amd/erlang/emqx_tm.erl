@@ -19,10 +19,13 @@
         , route_delete/3
         , route_apply/2
         , subscribe/4
+        , subscribe/5
+        , get_subopts/3
         , unsubscribe/4
         , subscriber_down/3
         , dispatch_batch/2
         , deliver_batch/2
+        , session_deliver_batch/3
         , match_routes_batch/2
         , rules_match/4
         , acl_new/2
@@ -114,6 +117,18 @@ route_apply(_Engine, _Events) -> erlang:nif_error(nif_not_loaded).
 -spec(subscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
 subscribe(_Engine, _Topic, _SubId, _NodeDestId) -> erlang:nif_error(nif_not_loaded).
 
+%% subscribe/3 with the ?SUBOPTION entry (src/emqx_broker.erl:127-136):
+%% SubOpts = {QoS, NL, RAP, RH, SubIdent} (SubIdent 0 = none).  A new
+%% subscription stores them; an existing one merges them (the four flags are
+%% replaced, SubIdent only when non-zero).  subscribe/4 is the defaults.
+-type(subopts() :: {0..2, 0..1, 0..1, 0..2, non_neg_integer()}).
+-spec(subscribe(reference(), binary(), non_neg_integer(), non_neg_integer(), subopts()) -> ok | {error, term()}).
+subscribe(_Engine, _Topic, _SubId, _NodeDestId, _SubOpts) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_broker:get_subopts/2 (:373-386).
+-spec(get_subopts(reference(), binary(), non_neg_integer()) -> {ok, subopts()} | undefined | {error, term()}).
+get_subopts(_Engine, _Topic, _SubId) -> erlang:nif_error(nif_not_loaded).
+
 -spec(unsubscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
 unsubscribe(_Engine, _Topic, _SubId, _NodeDestId) -> erlang:nif_error(nif_not_loaded).
 
@@ -132,6 +147,19 @@ dispatch_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
 -spec(deliver_batch(reference(), [binary()])
       -> [{non_neg_integer(), [{non_neg_integer(), binary()}]}] | {error, term()}).
 deliver_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
+
+%% deliver_batch/2 after emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693)
+%% and emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529), on the
+%% device: what each session sends.  A publish is {FromSubId | none, QoS,
+%% Retain, Retained, Topic}; a delivery is {{PublishIndex0, Filter}, QoS,
+%% Retain, NL, SubIdent} (SubIdent 0 = none), the inboxes that lost every
+%% delivery left out.  Flags: upgrade_qos (#session.upgrade_qos = true for the
+%% whole call), nl_all (drop every own delivery, not only the leading run).
+-type(publish() :: {non_neg_integer() | none, 0..2, boolean(), boolean(), binary()}).
+-type(delivery() :: {{non_neg_integer(), binary()}, 0..2, boolean(), boolean(), non_neg_integer()}).
+-spec(session_deliver_batch(reference(), [publish()], [upgrade_qos | nl_all])
+      -> [{non_neg_integer(), [delivery()]}] | {error, term()}).
+session_deliver_batch(_Engine, _Publishes, _Flags) -> erlang:nif_error(nif_not_loaded).
 
 %% Shared-subscription members (emqx_shared_sub's handle_call({subscribe |
 %% unsubscribe, Group, Topic, SubPid}) and cleanup_down/1,

@@ -395,6 +395,42 @@ TM_API int  tm_unsubscribe(tm_engine* e, const uint8_t* topic, size_t len, uint3
  * *n_removed (may be NULL) = how many. */
 TM_API int  tm_subscriber_down(tm_engine* e, uint32_t subscriber, uint32_t node_dest, uint64_t* n_removed);
 
+/* The ?SUBOPTION table: {SubPid, Topic} -> SubOpts (src/emqx_broker.erl:80,
+ * 101-102, 127-136, 150-158), non-shared subscriptions.  The defaults are
+ * {qos 0, nl 0, rap 0, rh 0}, no subid (include/emqx_mqtt.hrl:207-211).
+ * tm_subscribe_opts: emqx_broker:subscribe/3 (:127-136).  A new (topic,
+ * subscriber) subscribes exactly as tm_subscribe does and stores opts; an
+ * existing one merges as set_subopts/2 does (maps:merge(Old, New), :388-393):
+ * qos, nl, rap and rh are replaced, subid only when non-zero
+ * (with_subid(undefined, _), :139-142).  opts = NULL: the defaults.
+ * tm_subscribe is tm_subscribe_opts with the defaults: on an existing
+ * subscription it resets the four flags and keeps the subid.
+ * tm_set_subopts: set_subopts/2 for a partial map -- only the fields named by
+ * mask (TM_SUBOPT_*) change; TM_ENOENT when not subscribed (`false`).
+ * tm_get_subopts: get_subopts/2 (:373-386); TM_ENOENT for `undefined`.
+ * TM_EINVAL + tm_last_error(): qos > 2, nl > 1, rap > 1, rh > 2, a subid
+ * above 268,435,455, an unknown mask bit, NULL opts where one is required
+ * (tm_set_subopts), NULL out.  tm_unsubscribe and tm_subscriber_down delete the
+ * options with the subscription.  All three work on a host-only engine. */
+typedef struct {
+    uint8_t  qos;    /* 0..2 */
+    uint8_t  nl;     /* 0 | 1  No Local */
+    uint8_t  rap;    /* 0 | 1  Retain As Published */
+    uint8_t  rh;     /* 0..2   Retain Handling: stored and returned, not used on delivery */
+    uint32_t subid;  /* 0 = none, else 1 .. 268,435,455 (the MQTT Subscription Identifier range) */
+} tm_subopts;
+#define TM_SUBOPT_QOS 1u
+#define TM_SUBOPT_NL 2u
+#define TM_SUBOPT_RAP 4u
+#define TM_SUBOPT_RH 8u
+#define TM_SUBOPT_SUBID 16u
+#define TM_SUBID_MAX 268435455u
+TM_API int tm_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber,
+                             uint32_t node_dest, const tm_subopts* opts);
+TM_API int tm_set_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber,
+                          uint32_t mask, const tm_subopts* opts);
+TM_API int tm_get_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, tm_subopts* out);
+
 /* Deliveries of a waited batch: dispatch(To, Delivery) (:284-309) for every
  * filter To matched by publish i (its local route, do_route/2 :243-244):
  * deliveries of row i = subscribers[row_offsets[i] .. row_offsets[i+1]), the
@@ -474,6 +510,69 @@ typedef struct {
 TM_API int tm_batch_inboxes(tm_engine* e, tm_batch* b, uint32_t flags, tm_inboxes* out);
 /* diagnostic: deliveries per sort tile (tests place D around its multiples) */
 TM_API uint32_t tm_inbox_tile(void);
+
+/* What the session sends, per subscriber: the inboxes of tm_batch_inboxes on
+ * the same batch (R subscribers, D deliveries, each inbox one drained
+ * `Delivers` list in mailbox order) after the reference's two per-delivery
+ * lookups of maps:find(To, Subscriptions), in the reference's order.
+ * 1. emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693).  A delivery
+ *    (publish i, filter To) of inbox S is *own* when the options of (S, To)
+ *    have nl = 1 and from[i] == S; from[i] = TM_NONE is never own.  The
+ *    reference uses lists:dropwhile: the LEADING RUN of own deliveries of the
+ *    list is dropped and nothing after the first delivery that is not own --
+ *    the default here.  TM_DELIVER_NL_ALL drops every own delivery
+ *    (MQTT-3.8.3-3).  n_dropped_no_local counts the drops
+ *    ('delivery.dropped.no_local').
+ * 2. emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529) on every
+ *    delivery left, with the options of (S, To): QoS = min(sub qos, publish
+ *    qos), or max with TM_DELIVER_UPGRADE_QOS (#session.upgrade_qos, per call
+ *    here); nl = 1 sets TM_MSG_NL whoever published (:510-511); the retain
+ *    flag is the publish's when rap = 1, and also when rap = 0 and the publish
+ *    has TM_MSG_RETAINED (:522-523), otherwise 0 (:524-525); subids[q] = the
+ *    stored Subscription Identifier (TM_DELIVER_SUBIDS).
+ * An inbox that loses every delivery disappears from subscribers /
+ * inbox_offsets; the order inside an inbox is unchanged.  When nothing can
+ * drop (no subscription has nl = 1, or from = NULL) subscribers,
+ * inbox_offsets, publishes and filter_ids ARE the arrays of tm_batch_inboxes;
+ * the options are still looked up for msg / subids (msg is uploaded, one
+ * search per inbox and one per delivery run), so kernel_ms is not 0 on that
+ * path, from = msg = NULL included.
+ * The call runs tm_batch_inboxes itself, so it counts as a dispatch of the
+ * batch: pointers of earlier dispatch / inboxes / deliver calls are valid
+ * until the next of any of them, a re-prepare or a free.  Without
+ * TM_DELIVER_DEVICE the results are batch-owned pinned memory.  Options
+ * changed between two calls on the same waited batch are seen by the second.
+ * TM_EINVAL + tm_last_error(): NULL out or opts, an unknown flag, a msg[i]
+ * with QoS 3 or bits above 3, a batch not waited, a TM_BATCH_DEDUP batch.
+ * TM_ENODEV on a host-only engine.  TM_EOVERFLOW as tm_batch_inboxes.  TM_EIO
+ * + tm_last_error() if a (subscriber, filter) of the fan-out has no options
+ * (both come from one host state under the engine lock). */
+#define TM_MSG_RETAIN    4u  /* publish: #message.flags.retain; delivery: the flag after rap */
+#define TM_MSG_RETAINED  8u  /* publish only: headers.retained =:= true */
+#define TM_MSG_NL        8u  /* delivery only: emqx_message:set_flag(nl, Msg) */
+#define TM_DELIVER_DEVICE      1u  /* no copy back: device pointers of the batch */
+#define TM_DELIVER_UPGRADE_QOS 2u  /* #session.upgrade_qos = true */
+#define TM_DELIVER_NL_ALL      4u  /* drop every own delivery, not only the leading run */
+#define TM_DELIVER_SUBIDS      8u  /* fill subids[] */
+typedef struct {
+    const uint32_t* from;   /* n_topics host u32: the subscriber id of publish i's publisher; TM_NONE = none.
+                               NULL = all TM_NONE */
+    const uint8_t*  msg;    /* n_topics host bytes: bits 0-1 QoS, TM_MSG_RETAIN, TM_MSG_RETAINED; NULL = all 0 */
+    uint32_t        flags;
+} tm_deliver_opts;
+typedef struct {
+    uint32_t n_topics, n_subscribers;      /* R': subscribers with at least one delivery LEFT */
+    uint64_t n_deliveries;                 /* D': deliveries left */
+    uint64_t n_dropped_no_local;           /* D' + this = tm_batch_inboxes' D */
+    const uint32_t* subscribers;           /* R', strictly ascending */
+    const uint32_t* inbox_offsets;         /* R' + 1 */
+    const uint32_t* publishes;             /* D' */
+    const uint32_t* filter_ids;            /* D' */
+    const uint8_t*  msg;                   /* D': bits 0-1 QoS, TM_MSG_RETAIN, TM_MSG_NL */
+    const uint32_t* subids;                /* D' with TM_DELIVER_SUBIDS (0 = none), else NULL */
+    float    kernel_ms;                    /* device time of the delivery kernels only (not the inboxes before them) */
+} tm_session_inboxes;
+TM_API int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_session_inboxes* out);
 
 /* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
 /* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
