@@ -193,23 +193,30 @@ struct tm_sharded {
         return tm_stats(sh[0], &st) == TM_OK ? st.words : 0;
     }
 
-    // a blocking copy between shards' devices (the on-request reorder)
+    // a blocking copy between shards' devices (the on-request reorder).  Every
+    // copy goes on a stream of its own device that is then waited for: a
+    // device-to-device hipMemcpy / hipMemcpyPeer may return before the bytes
+    // have landed, and the reorder's kernels run on another, non-blocking
+    // stream that the null stream does not order (the shards' streams are idle
+    // here: the step has been joined)
     int copy_now(uint32_t i, uint32_t j, void* dst, const void* src, size_t bytes) {
         if (!bytes) return TM_OK;
         const uint8_t l = link[i * G + j];
         if (l == TM_LINK_STAGED) {
             std::vector<uint8_t> tmp(bytes);
             SH_HIP(hipSetDevice(dev[i]));
-            SH_HIP(hipMemcpy(tmp.data(), src, bytes, hipMemcpyDeviceToHost));
+            SH_HIP(hipMemcpyAsync(tmp.data(), src, bytes, hipMemcpyDeviceToHost, ss[i]));
+            SH_HIP(hipStreamSynchronize(ss[i]));
             SH_HIP(hipSetDevice(dev[j]));
-            SH_HIP(hipMemcpy(dst, tmp.data(), bytes, hipMemcpyHostToDevice));
+            SH_HIP(hipMemcpyAsync(dst, tmp.data(), bytes, hipMemcpyHostToDevice, ss[j]));
         } else if (l == TM_LINK_PEER) {
             SH_HIP(hipSetDevice(dev[j]));
-            SH_HIP(hipMemcpyPeer(dst, dev[j], src, dev[i], bytes));
+            SH_HIP(hipMemcpyPeerAsync(dst, dev[j], src, dev[i], bytes, ss[j]));
         } else {
             SH_HIP(hipSetDevice(dev[j]));
-            SH_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToDevice));
+            SH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ss[j]));
         }
+        SH_HIP(hipStreamSynchronize(ss[j]));
         return TM_OK;
     }
 
