@@ -134,6 +134,34 @@ class SessionInboxes(C.Structure):
                 ("msg", C.POINTER(C.c_uint8)), ("subids", C.POINTER(C.c_uint32)), ("kernel_ms", C.c_float)]
 
 
+TM_SESS_DISCONNECTED, TM_SESS_STORE_QOS0, TM_SESS_HOST = 1, 2, 4
+TM_SESS_UNBOUNDED = 0xFFFFFFFF
+TM_WINDOW_DEVICE = 1
+(TM_DISP_SEND0, TM_DISP_SEND, TM_DISP_QUEUED, TM_DISP_DROP_QOS0, TM_DISP_DROP_FULL, TM_DISP_HOST,
+ TM_DISP_COUNT) = range(7)
+
+
+class SessionState(C.Structure):
+    _fields_ = [("subscriber", C.c_uint32), ("next_pkt_id", C.c_uint32), ("flags", C.c_uint32),
+                ("inflight_free", C.c_uint32), ("mqueue_len", C.c_uint32), ("mqueue_max", C.c_uint32)]
+
+
+class WindowOpts(C.Structure):
+    _fields_ = [("sessions", C.POINTER(SessionState)), ("n_sessions", C.c_uint32), ("defaults", SessionState),
+                ("flags", C.c_uint32)]
+
+
+class WindowRecord(C.Structure):
+    _fields_ = [("next_pkt_id", C.c_uint32), ("n_inflight", C.c_uint32), ("n_queued", C.c_uint32),
+                ("n_dropped_old", C.c_uint32)]
+
+
+class SessionWindow(C.Structure):
+    _fields_ = [("inboxes", SessionInboxes), ("disp", C.POINTER(C.c_uint8)), ("packet_ids", C.POINTER(C.c_uint16)),
+                ("records", C.POINTER(WindowRecord)), ("totals", C.c_uint64 * TM_DISP_COUNT),
+                ("kernel_ms", C.c_float), ("pad0", C.c_uint32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -257,6 +285,7 @@ SIGNATURES = {
     "tm_set_subopts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32, C.POINTER(SubOpts)]),
     "tm_get_subopts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.POINTER(SubOpts)]),
     "tm_batch_deliver": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(SessionInboxes)]),
+    "tm_batch_window": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(WindowOpts), C.POINTER(SessionWindow)]),
     "tm_match_routes_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Routes)]),
     "tm_trie_insert_many": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_trie_delete_many": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(C.c_uint64)]),

@@ -44,7 +44,7 @@ static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_TRUE, ATOM_FALSE, ATOM_UNDEFINED, 
     ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH,
     ATOM_ALLOW, ATOM_DENY, ATOM_NOMATCH, ATOM_NONE, ATOM_ALL, ATOM_CLIENT, ATOM_USER, ATOM_IPADDR, ATOM_AND, ATOM_OR,
     ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB, ATOM_RANDOM, ATOM_ROUND_ROBIN, ATOM_HASH, ATOM_UPGRADE_QOS,
-    ATOM_NL_ALL;
+    ATOM_NL_ALL, ATOM_DISCONNECTED, ATOM_STORE_QOS0, ATOM_HOST, ATOM_UNBOUNDED, ATOM_DISP[TM_DISP_COUNT];
 
 /* set while a match callback runs on the engine's completion thread */
 static __thread int in_engine_callback;
@@ -651,15 +651,22 @@ static int get_bool(ERL_NIF_TERM t, unsigned* out) {
  * delivery left out, each list in mailbox order.  Retain, Retained and NL are
  * true | false, SubIdent 0 = none.  A delivery is a 5-tuple around the
  * {PublishIndex0, Filter} pair of deliver_batch rather than a flat 6-tuple. */
+static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM pubs, ERL_NIF_TERM flags,
+                                  const tm_window_opts* wo);
 static ERL_NIF_TERM nif_session_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    (void)argc;
+    return session_batch(env, argv[0], argv[1], argv[2], NULL);
+}
+
+/* the body of session_deliver_batch/3 and, with wo, of session_window_batch/4 */
+static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM pubs, ERL_NIF_TERM flags,
+                                  const tm_window_opts* wo) {
     engine_res* r;
     unsigned n, nf;
-    (void)argc;
-    if (!get_engine(env, argv[0], &r) || !enif_get_list_length(env, argv[1], &n) ||
-        !enif_get_list_length(env, argv[2], &nf))
+    if (!get_engine(env, eng, &r) || !enif_get_list_length(env, pubs, &n) || !enif_get_list_length(env, flags, &nf))
         return enif_make_badarg(env);
     tm_deliver_opts o = {NULL, NULL, TM_DELIVER_SUBIDS};
-    ERL_NIF_TERM head, tail = argv[2];
+    ERL_NIF_TERM head, tail = flags;
     for (unsigned i = 0; i < nf; i++) {
         if (!enif_get_list_cell(env, tail, &head, &tail)) return enif_make_badarg(env);
         if (enif_is_identical(head, ATOM_UPGRADE_QOS)) o.flags |= TM_DELIVER_UPGRADE_QOS;
@@ -674,7 +681,7 @@ static ERL_NIF_TERM nif_session_deliver_batch(ErlNifEnv* env, int argc, const ER
     ERL_NIF_TERM out;
     int ok = from && msg && offs && bins;
     uint64_t total = 0;
-    tail = argv[1];
+    tail = pubs;
     for (unsigned i = 0; ok && i < n; i++) {
         const ERL_NIF_TERM* el;
         int arity;
@@ -703,10 +710,16 @@ static ERL_NIF_TERM nif_session_deliver_batch(ErlNifEnv* env, int argc, const ER
     o.msg = msg;
     tm_batch* b;
     tm_session_inboxes si;
+    tm_session_window sw;
     packed p;
     int rc = run_batch(r->e, buf, offs, n, &b);
     enif_free(buf); enif_free(offs);
-    if (!rc) rc = tm_batch_deliver(r->e, b, &o, &si);
+    if (!rc && wo) {
+        rc = tm_batch_window(r->e, b, &o, wo, &sw);
+        si = sw.inboxes;
+    } else if (!rc) {
+        rc = tm_batch_deliver(r->e, b, &o, &si);
+    }
     enif_free(from); enif_free(msg);
     if (rc) {
         if (b) tm_batch_free(r->e, b);
@@ -742,18 +755,94 @@ static ERL_NIF_TERM nif_session_deliver_batch(ErlNifEnv* env, int argc, const ER
             const uint32_t* u = bsearch(&si.filter_ids[q], uniq, nu, sizeof(uint32_t), cmp_u32);
             if (!u || !live[u - uniq]) continue;   /* deleted meanwhile and its id reused */
             const uint8_t m = si.msg[q];
-            box = enif_make_list_cell(
-                env,
+            ERL_NIF_TERM dl =
                 enif_make_tuple5(env, enif_make_tuple2(env, enif_make_uint(env, si.publishes[q]), term[u - uniq]),
                                  enif_make_uint(env, m & 3u), (m & TM_MSG_RETAIN) ? ATOM_TRUE : ATOM_FALSE,
-                                 (m & TM_MSG_NL) ? ATOM_TRUE : ATOM_FALSE, enif_make_uint(env, si.subids[q])),
-                box);
+                                 (m & TM_MSG_NL) ? ATOM_TRUE : ATOM_FALSE, enif_make_uint(env, si.subids[q]));
+            if (wo) {
+                const uint8_t d = sw.disp[q] < TM_DISP_COUNT ? sw.disp[q] : TM_DISP_HOST;
+                dl = enif_make_tuple3(env, ATOM_DISP[d],
+                                      d == TM_DISP_SEND ? enif_make_uint(env, sw.packet_ids[q]) : ATOM_UNDEFINED, dl);
+            }
+            box = enif_make_list_cell(env, dl, box);
         }
-        out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, si.subscribers[s]), box), out);
+        const ERL_NIF_TERM sub = enif_make_uint(env, si.subscribers[s]);
+        if (wo) {
+            const tm_window_record* w = &sw.records[s];
+            out = enif_make_list_cell(
+                env,
+                enif_make_tuple3(env, sub,
+                                 enif_make_tuple3(env, enif_make_uint(env, w->next_pkt_id),
+                                                  enif_make_uint(env, w->n_dropped_old), enif_make_uint(env, w->n_queued)),
+                                 box),
+                out);
+        } else {
+            out = enif_make_list_cell(env, enif_make_tuple2(env, sub, box), out);
+        }
     }
     packed_free(&p);
     enif_free(uniq); enif_free(term); enif_free(live);
     tm_batch_free(r->e, b);
+    return out;
+}
+
+/* {SubId, NextPktId, [disconnected | store_qos0 | host], InflightFree | unbounded, MqueueLen, MqueueMax} */
+static int get_session(ErlNifEnv* env, ERL_NIF_TERM t, tm_session_state* s) {
+    const ERL_NIF_TERM* el;
+    int arity;
+    unsigned nf;
+    ERL_NIF_TERM head, tail;
+    memset(s, 0, sizeof *s);
+    if (!enif_get_tuple(env, t, &arity, &el) || arity != 6 || !enif_get_uint(env, el[0], &s->subscriber) ||
+        !enif_get_uint(env, el[1], &s->next_pkt_id) || !enif_get_list_length(env, el[2], &nf) ||
+        !enif_get_uint(env, el[4], &s->mqueue_len) || !enif_get_uint(env, el[5], &s->mqueue_max))
+        return 0;
+    if (enif_is_identical(el[3], ATOM_UNBOUNDED)) s->inflight_free = TM_SESS_UNBOUNDED;
+    else if (!enif_get_uint(env, el[3], &s->inflight_free) || s->inflight_free == TM_SESS_UNBOUNDED) return 0;
+    tail = el[2];
+    for (unsigned i = 0; i < nf; i++) {
+        if (!enif_get_list_cell(env, tail, &head, &tail)) return 0;
+        if (enif_is_identical(head, ATOM_DISCONNECTED)) s->flags |= TM_SESS_DISCONNECTED;
+        else if (enif_is_identical(head, ATOM_STORE_QOS0)) s->flags |= TM_SESS_STORE_QOS0;
+        else if (enif_is_identical(head, ATOM_HOST)) s->flags |= TM_SESS_HOST;
+        else return 0;
+    }
+    return 1;
+}
+
+/* session_window_batch(Engine, Publishes, {DefaultSession, [Session]}, Flags)
+ *   -> [{SubId, {NextPktId, NDroppedOld, NQueued}, [{Disp, PacketId | undefined, Delivery}]}]
+ * session_deliver_batch/3 of (Engine, Publishes, Flags), then what
+ * emqx_channel:handle_deliver/2 (src/emqx_channel.erl:657-680) decides for
+ * every delivery, on the device (tm_batch_window): Disp = send0 | send |
+ * queued | dropped_qos0 | dropped_queue_full | host, PacketId an integer for
+ * send.  A Session is {SubId, NextPktId, [disconnected | store_qos0 | host],
+ * InflightFree | unbounded, MqueueLen, MqueueMax}, the list ascending by
+ * SubId; DefaultSession (its SubId ignored) is the session of a subscriber not
+ * listed.  Delivery is session_deliver_batch/3's 5-tuple; the result uses
+ * tuples of 2, 3 and 5 elements only. */
+static ERL_NIF_TERM nif_session_window_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    const ERL_NIF_TERM* el;
+    int arity;
+    unsigned ns;
+    tm_window_opts wo;
+    (void)argc;
+    memset(&wo, 0, sizeof wo);
+    if (!enif_get_tuple(env, argv[2], &arity, &el) || arity != 2 || !get_session(env, el[0], &wo.defaults) ||
+        !enif_get_list_length(env, el[1], &ns))
+        return enif_make_badarg(env);
+    tm_session_state* ss = enif_alloc(sizeof(tm_session_state) * (ns ? ns : 1));
+    if (!ss) return err(env, TM_ENOMEM);
+    ERL_NIF_TERM head, tail = el[1];
+    for (unsigned i = 0; i < ns; i++)
+        if (!enif_get_list_cell(env, tail, &head, &tail) || !get_session(env, head, &ss[i])) {
+            enif_free(ss);
+            return enif_make_badarg(env);
+        }
+    wo.sessions = ns ? ss : NULL;
+    wo.n_sessions = ns;
+    const ERL_NIF_TERM out = session_batch(env, argv[0], argv[1], argv[3], &wo);
+    enif_free(ss);
     return out;
 }
 
@@ -1290,6 +1379,16 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     ATOM_HASH = enif_make_atom(env, "hash");
     ATOM_UPGRADE_QOS = enif_make_atom(env, "upgrade_qos");
     ATOM_NL_ALL = enif_make_atom(env, "nl_all");
+    ATOM_DISCONNECTED = enif_make_atom(env, "disconnected");
+    ATOM_STORE_QOS0 = enif_make_atom(env, "store_qos0");
+    ATOM_HOST = enif_make_atom(env, "host");
+    ATOM_UNBOUNDED = enif_make_atom(env, "unbounded");
+    ATOM_DISP[TM_DISP_SEND0] = enif_make_atom(env, "send0");
+    ATOM_DISP[TM_DISP_SEND] = enif_make_atom(env, "send");
+    ATOM_DISP[TM_DISP_QUEUED] = enif_make_atom(env, "queued");
+    ATOM_DISP[TM_DISP_DROP_QOS0] = enif_make_atom(env, "dropped_qos0");
+    ATOM_DISP[TM_DISP_DROP_FULL] = enif_make_atom(env, "dropped_queue_full");
+    ATOM_DISP[TM_DISP_HOST] = ATOM_HOST;
     return 0;
 }
 
@@ -1312,6 +1411,7 @@ static ErlNifFunc funcs[] = {
     {"dispatch_batch", 2, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"deliver_batch", 2, nif_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"session_deliver_batch", 3, nif_session_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"session_window_batch", 4, nif_session_window_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_routes_batch", 2, nif_match_routes_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"rules_match", 4, nif_rules_match, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"topic_match", 2, nif_topic_match, 0},

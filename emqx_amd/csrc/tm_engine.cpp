@@ -830,6 +830,60 @@ int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_
     }
 }
 
+// one tm_session_state of tm_window_opts; which = its index, -1 for defaults
+static int session_check(const tm_session_state* s, long which) {
+    const char* bad = nullptr;
+    if (s->next_pkt_id < 1 || s->next_pkt_id > 65535) bad = "next_pkt_id outside 1..65535";
+    else if (s->flags & ~(TM_SESS_DISCONNECTED | TM_SESS_STORE_QOS0 | TM_SESS_HOST)) bad = "unknown session flag";
+    else if (s->mqueue_max && s->mqueue_len > s->mqueue_max) bad = "mqueue_len above mqueue_max";
+    if (!bad) return TM_OK;
+    if (which < 0) snprintf(last_error(), 512, "tm_batch_window: defaults: %s", bad);
+    else snprintf(last_error(), 512, "tm_batch_window: sessions[%ld] (subscriber %u): %s", which, s->subscriber, bad);
+    return TM_EINVAL;
+}
+
+int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
+                    tm_session_window* out) {
+    // the arguments are checked first, so a host-only engine reports them too
+    if (!e) return TM_EINVAL;
+    if (!out || !dopts || !wopts) {
+        snprintf(last_error(), 512, "tm_batch_window: %s is NULL", !out ? "out" : !dopts ? "dopts" : "wopts");
+        return TM_EINVAL;
+    }
+    if (dopts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS)) {
+        snprintf(last_error(), 512, "tm_batch_window: unknown deliver flag");
+        return TM_EINVAL;
+    }
+    if (wopts->flags & ~TM_WINDOW_DEVICE) {
+        snprintf(last_error(), 512, "tm_batch_window: unknown window flag");
+        return TM_EINVAL;
+    }
+    if (wopts->n_sessions && !wopts->sessions) {
+        snprintf(last_error(), 512, "tm_batch_window: sessions is NULL with n_sessions = %u", wopts->n_sessions);
+        return TM_EINVAL;
+    }
+    if (int rc = session_check(&wopts->defaults, -1)) return rc;
+    for (uint32_t i = 0; i < wopts->n_sessions; ++i) {
+        if (int rc = session_check(&wopts->sessions[i], (long)i)) return rc;
+        if (i && wopts->sessions[i].subscriber <= wopts->sessions[i - 1].subscriber) {
+            snprintf(last_error(), 512, "tm_batch_window: sessions[%u] (subscriber %u) not above sessions[%u] (%u)", i,
+                     wopts->sessions[i].subscriber, i - 1, wopts->sessions[i - 1].subscriber);
+            return TM_EINVAL;
+        }
+    }
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    int rc = e->use(b->rep);
+    if (rc) return rc;
+    try {
+        return e->batch_window(b, dopts, wopts, out);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
 int tm_batch_routes(tm_engine* e, tm_batch* b, tm_routes* out) {
     if (!e || !b || !out) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;   // host-only engine

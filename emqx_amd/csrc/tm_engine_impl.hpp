@@ -546,6 +546,23 @@ struct tm_batch {
         Event dev0, dev1;   // around the delivery kernels
     } dlv;
 
+    // the session's send window (tm_batch_window): the uploaded session table
+    // and its pinned staging, the head bits, per-inbox and per-wave scratch, and
+    // the result with its pinned mirror
+    struct Window {
+        DevBuf<uint32_t> d_sess, d_heads, d_hbase, d_wcount, d_wbs, d_tot, d_wdisp;
+        DevBuf<uint4> d_st, d_rec;
+        DevBuf<uint8_t> d_disp;
+        DevBuf<uint16_t> d_pid;
+        DevBuf<unsigned long long> d_totals;
+        PinBuf<uint32_t> h_sess, h_tot;
+        PinBuf<uint4> h_rec;
+        PinBuf<uint8_t> h_disp;
+        PinBuf<uint16_t> h_pid;
+        PinBuf<unsigned long long> h_totals;
+        Event wev0, wev1;   // around the window kernels
+    } win;
+
     static constexpr size_t HDR_FIXED = ((size_t)XG_WORD + TICKET_GROUPS * TICKET_STRIDE) * 4;
     static size_t hdr_bytes(size_t n) { return HDR_FIXED + n * 12; }
     // the replica (device copy of the trie) the batch runs on; fixed for the
@@ -635,6 +652,7 @@ struct tm_batch {
         sh = {};
         inbox = {};
         dlv = {};
+        win = {};
         dtab_dirty = true;
         end_recorded = false;
         graph.reset();
@@ -1891,6 +1909,8 @@ struct tm_engine {
     int sync_subopts(Replica& R);
     // tm_batch_deliver: the batch's inboxes after ignore_local/3 and enrich_subopts/3
     int batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_inboxes* out);
+    // tm_batch_window: batch_deliver, then every delivery's disposition and packet id
+    int batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w, tm_session_window* out);
 
     // do_unsubscribe/4 (:179-191) + handle_cast({unsubscribed, Topic}) (:463-469):
     // the last subscriber of a topic deletes the node's route.

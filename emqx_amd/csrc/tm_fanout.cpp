@@ -739,6 +739,105 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
     return TM_OK;
 }
 
+static_assert(WIN_DISCONNECTED == TM_SESS_DISCONNECTED && WIN_STORE_QOS0 == TM_SESS_STORE_QOS0 && WIN_HOST == TM_SESS_HOST,
+              "TM_SESS_* flags");
+static_assert(WIN_NDISP == TM_DISP_COUNT && TM_DISP_SEND0 == 0 && TM_DISP_SEND == 1 && TM_DISP_QUEUED == 2 &&
+                  TM_DISP_DROP_QOS0 == 3 && TM_DISP_DROP_FULL == 4 && TM_DISP_HOST == 5,
+              "TM_DISP_* as tm_window_classify stores them");
+static_assert(sizeof(tm_session_state) == WIN_SESSION_WORDS * 4 && std::has_unique_object_representations_v<tm_session_state>,
+              "tm_session_state is uploaded as six words");
+static_assert(sizeof(tm_window_opts) == 40 && std::has_unique_object_representations_v<tm_window_opts>,
+              "tm_window_opts has implicit padding");
+static_assert(sizeof(tm_window_record) == sizeof(uint4) && std::has_unique_object_representations_v<tm_window_record>,
+              "tm_window_record is the kernels' uint4");
+static_assert(sizeof(tm_session_window) == sizeof(tm_session_inboxes) + 3 * sizeof(void*) + 8 * TM_DISP_COUNT + 8,
+              "tm_session_window has implicit padding");
+
+int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w, tm_session_window* out) {
+    const bool device = w->flags & TM_WINDOW_DEVICE;
+    tm_deliver_opts dopt = *o;
+    dopt.flags = (o->flags & ~TM_DELIVER_DEVICE) | (device ? TM_DELIVER_DEVICE : 0u);
+    *out = tm_session_window{};
+    int rc;
+    if ((rc = batch_deliver(b, &dopt, &out->inboxes))) return rc;   // returns with the stream idle
+    Replica& R = *b->rep;
+    const hipStream_t stream = R.stream;
+    tm_batch::Window& wn = b->win;
+    // where batch_deliver left the result on the device, whichever copy it returned
+    const bool can_drop = o->from && nl_entries > 0;
+    const uint32_t* d_sub = can_drop ? b->dlv.d_sub.p : b->inbox.d_sub.p;
+    const uint32_t* d_off = can_drop ? b->dlv.d_off.p : b->inbox.d_off.p;
+    const uint32_t D = (uint32_t)out->inboxes.n_deliveries, nsub = out->inboxes.n_subscribers, ns = w->n_sessions;
+    const size_t dd = std::max<size_t>(D, 1), rr = std::max<size_t>(nsub, 1);
+    if ((rc = wn.d_disp.reserve(dd))) return rc;
+    if ((rc = wn.d_pid.reserve(dd))) return rc;
+    if ((rc = wn.d_rec.reserve(rr))) return rc;
+    if (!device) {
+        if ((rc = wn.h_disp.reserve(dd))) return rc;
+        if ((rc = wn.h_pid.reserve(dd))) return rc;
+        if ((rc = wn.h_rec.reserve(rr))) return rc;
+    }
+    out->disp = device ? wn.d_disp.p : wn.h_disp.p;
+    out->packet_ids = device ? wn.d_pid.p : wn.h_pid.p;
+    out->records = (const tm_window_record*)(device ? wn.d_rec.p : wn.h_rec.p);
+    if (!D || !nsub) return TM_OK;   // nothing left to send: every total 0
+    const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
+    const size_t nheads = (size_t)2 * (((size_t)D + 63) / 64);
+    WindowArgs a{};
+    a.nwaves = ntiles * (INBOX_TILE / 1024);
+    if ((rc = wn.d_sess.reserve(std::max<size_t>((size_t)ns * WIN_SESSION_WORDS, 1)))) return rc;
+    if ((rc = wn.h_sess.reserve(std::max<size_t>((size_t)ns * WIN_SESSION_WORDS, 1)))) return rc;
+    if ((rc = wn.d_heads.reserve(nheads))) return rc;
+    if ((rc = wn.d_st.reserve(rr))) return rc;
+    if ((rc = wn.d_hbase.reserve(rr))) return rc;
+    if ((rc = wn.d_wcount.reserve((size_t)a.nwaves + 1))) return rc;
+    if ((rc = wn.d_wbs.reserve((size_t)scan_block_count(a.nwaves) + 1))) return rc;
+    if ((rc = wn.d_wdisp.reserve((size_t)a.nwaves * 8))) return rc;
+    if ((rc = wn.d_tot.reserve(2))) return rc;
+    if ((rc = wn.h_tot.reserve(2))) return rc;
+    if ((rc = wn.d_totals.reserve(WIN_NDISP))) return rc;
+    if ((rc = wn.h_totals.reserve(WIN_NDISP))) return rc;
+    if ((rc = wn.wev0.create())) return rc;
+    if ((rc = wn.wev1.create())) return rc;
+    a.subscribers = d_sub; a.off = d_off; a.msg = b->dlv.d_msg.p; a.sess = wn.d_sess.p;
+    a.D = D; a.R = nsub; a.NS = ns;
+    memcpy(a.dflt, &w->defaults, sizeof a.dflt);
+    a.heads = wn.d_heads.p; a.st = wn.d_st.p; a.hbase = wn.d_hbase.p;
+    a.wcount = wn.d_wcount.p; a.wbs = wn.d_wbs.p; a.d_tot = wn.d_tot.p;
+    a.disp = wn.d_disp.p; a.pid = wn.d_pid.p; a.rec = wn.d_rec.p;
+    a.wdisp = wn.d_wdisp.p; a.totals = wn.d_totals.p;
+    if (ns) {   // uploaded per call: acks change the sessions on the host between any two calls
+        memcpy(wn.h_sess.p, w->sessions, (size_t)ns * sizeof(tm_session_state));
+        HIP_OK(hipMemcpyAsync(wn.d_sess.p, wn.h_sess.p, (size_t)ns * sizeof(tm_session_state), hipMemcpyHostToDevice, stream));
+    }
+    HIP_OK(hipMemsetAsync(wn.d_heads.p, 0, nheads * 4, stream));
+    HIP_OK(hipMemsetAsync(wn.d_tot.p, 0, 8, stream));
+    HIP_OK(hipEventRecord(wn.wev0.e, stream));
+    HIP_OK(launch_window(a, stream));
+    HIP_OK(hipEventRecord(wn.wev1.e, stream));
+    HIP_OK(hipMemcpyAsync(wn.h_tot.p, wn.d_tot.p, 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipMemcpyAsync(wn.h_totals.p, wn.d_totals.p, WIN_NDISP * 8, hipMemcpyDeviceToHost, stream));
+    if (!device) {
+        HIP_OK(hipMemcpyAsync(wn.h_disp.p, wn.d_disp.p, D, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(wn.h_pid.p, wn.d_pid.p, (size_t)D * 2, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipMemcpyAsync(wn.h_rec.p, wn.d_rec.p, (size_t)nsub * 16, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    HIP_OK(hipEventElapsedTime(&out->kernel_ms, wn.wev0.e, wn.wev1.e));
+    if (wn.h_tot.p[1]) {
+        snprintf(last_error(), 512, "tm_batch_window: %u indices past %u deliveries, %u inboxes or %u sessions", wn.h_tot.p[1],
+                 D, nsub, ns);
+        return TM_EIO;
+    }
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < WIN_NDISP; ++k) sum += out->totals[k] = wn.h_totals.p[k];
+    if (sum != D) {
+        snprintf(last_error(), 512, "tm_batch_window: dispositions of %llu of %u deliveries", (unsigned long long)sum, D);
+        return TM_EIO;
+    }
+    return TM_OK;
+}
+
 int tm_engine::rules_match(Replica& R, const uint8_t* names, const uint64_t* noffs, uint32_t n, const uint8_t* rules,
                 const uint64_t* roffs, uint32_t r, bool dollar_rule, uint32_t* bits) {
     const hipStream_t stream = R.stream;

@@ -453,6 +453,38 @@ struct DeliverArgs {
     uint32_t* o_subid;             // D, or null
 };
 
+// The session's send window (tm_batch_window) over the arrays tm_batch_deliver
+// left: the (compacted) inbox heads, offsets and delivery bytes.  An inbox's
+// index for delivery q is a count of inbox heads at or before q: `heads` holds
+// one bit per delivery (set per inbox from its offset), a wave finds the heads
+// before its first pair by one search of `off` and counts bits after that.
+// WIN_* are TM_SESS_* (tm_fanout.cpp asserts them).
+constexpr uint32_t WIN_DISCONNECTED = 1u, WIN_STORE_QOS0 = 2u, WIN_HOST = 4u, WIN_FLAGS = 7u;
+constexpr uint32_t WIN_SESSION_WORDS = 6;   // tm_session_state as u32 words
+constexpr uint32_t WIN_NDISP = 6;           // TM_DISP_COUNT
+struct WindowArgs {
+    const uint32_t* subscribers;   // R
+    const uint32_t* off;           // R + 1
+    const uint8_t* msg;            // D: bits 0-1 the enriched QoS
+    const uint32_t* sess;          // NS x {subscriber, next_pkt_id, flags, inflight_free, mqueue_len, mqueue_max}
+    uint32_t D, R, NS, nwaves;     // nwaves = 4 ceil(D / INBOX_TILE)
+    uint32_t dflt[WIN_SESSION_WORDS];   // the session of a subscriber not in sess
+    uint32_t* heads;               // 2 ceil(D / 64) words, zeroed: bit q = an inbox starts at delivery q
+    // R: {P | flags << 16, F, L, M} after tm_window_state; {P | flags << 16,
+    // base, base-relative end of SEND, end of DROP_FULL} after tm_window_plan
+    uint4* st;
+    uint32_t* hbase;               // R: counted deliveries of the head's wave before the head
+    uint32_t* wcount;              // nwaves + 1: counted deliveries per wave, scanned in place (+ wbs)
+    uint32_t* wbs;
+    uint32_t* d_tot;               // [0] counted deliveries of the batch, [1] indices out of range
+    uint8_t* disp;                 // D
+    uint16_t* pid;                 // D
+    uint4* rec;                    // R: tm_window_record
+    uint32_t* wdisp;               // nwaves x 8: deliveries per disposition and wave
+    unsigned long long* totals;    // WIN_NDISP
+};
+static_assert(std::has_unique_object_representations_v<WindowArgs>, "WindowArgs has implicit padding");
+
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
 struct RulesArgs {
     const uint32_t* nwords;   // name word ids (rule dictionary; unknown = W_UNKNOWN)
@@ -546,6 +578,9 @@ hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s);
 // compaction into o_*
 hipError_t launch_deliver_flags(const DeliverArgs& a, bool drop, hipStream_t s);
 hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s);
+// window: state per inbox, counts per wave, the scan, the plan per inbox
+// (writes rec), the disposition and packet id of every delivery, the totals
+hipError_t launch_window(const WindowArgs& a, hipStream_t s);
 hipError_t launch_fan_globalize(const FanArgs& a, hipStream_t s);   // block-relative moff -> global
 uint32_t fan_scan_tile();   // match entries per scan block
 uint32_t fan_fill_tile();   // deliveries per fill block

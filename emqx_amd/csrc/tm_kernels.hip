@@ -2549,6 +2549,198 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_scatter(DeliverArgs a)
     }
 }
 
+// ------------------------------------- the session's send window (tm_batch_window)
+//
+// emqx_session:deliver/2 (src/emqx_session.erl:421-457) and enqueue/2
+// (:459-472) with emqx_mqueue:in/2 (src/emqx_mqueue.erl:148-168) over what
+// tm_batch_deliver left.  The reference folds over an inbox; here a delivery's
+// outcome follows from its rank among the inbox's *counted* deliveries (QoS > 0
+// in a connected inbox, "enters the queue" in a disconnected one) and from the
+// inbox's total of them.  Same tiles as the deliver kernels: wave w of tile t
+// owns deliveries [4096 t + 1024 w, + 1024), 64 per round.
+//   state     per inbox: one search of the uploaded session table (or the
+//             defaults), and the inbox's bit in `heads` (one atomicOr per inbox
+//             on a word of 32 deliveries; none on the deliveries of an inbox)
+//   count     per wave: its counted deliveries; the lane on an inbox head
+//             stores the wave's count before it
+//   scan      the waves' counts (the project's two-level scan).  Per wave, not
+//             per tile: a head's base is then scanned[its wave] + its stored
+//             count with no second pass over the tile and no barrier
+//   plan      per inbox: base, total (the next head's base, or the grand
+//             total), the closed form of the fold -> the inbox's record and
+//             the two rank thresholds
+//   classify  per delivery: rank = scanned position - base -> disp, packet id;
+//             per-wave disposition counts, summed by tm_window_totals
+// No kernel waits for another workgroup.
+
+// the heads before the wave's first delivery: off[r] < wbase, r < R
+__device__ __forceinline__ uint32_t win_heads_before(const WindowArgs& a, uint32_t wbase) {
+    uint32_t lo = 0, hi = a.R;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.off[mid] < wbase) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint64_t win_head_mask(const WindowArgs& a, uint64_t q0) {   // q0: the round's first delivery
+    if (q0 >= a.D) return 0ull;
+    const uint64_t i = (q0 >> 6) * 2;
+    return (uint64_t)a.heads[i] | (uint64_t)a.heads[i + 1] << 32;
+}
+__device__ __forceinline__ bool win_counted(uint32_t flags, uint32_t qos) {
+    if (flags & WIN_HOST) return false;
+    return qos > 0 || (flags & (WIN_DISCONNECTED | WIN_STORE_QOS0)) == (WIN_DISCONNECTED | WIN_STORE_QOS0);
+}
+__device__ __forceinline__ uint32_t win_scanned(const WindowArgs& a, uint32_t gw) {
+    return a.wcount[gw] + a.wbs[gw / SCAN_TILE];
+}
+
+__global__ __launch_bounds__(256) void tm_window_state(WindowArgs a) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint32_t S = a.subscribers[r];
+    uint32_t lo = 0, hi = a.NS;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.sess[(uint64_t)mid * WIN_SESSION_WORDS] < S) lo = mid + 1; else hi = mid;
+    }
+    uint4 s;
+    if (lo < a.NS && a.sess[(uint64_t)lo * WIN_SESSION_WORDS] == S) {
+        const uint32_t* e = a.sess + (uint64_t)lo * WIN_SESSION_WORDS;
+        s = make_uint4((e[1] & 0xFFFFu) | (e[2] & WIN_FLAGS) << 16, e[3], e[4], e[5]);
+    } else {
+        s = make_uint4((a.dflt[1] & 0xFFFFu) | (a.dflt[2] & WIN_FLAGS) << 16, a.dflt[3], a.dflt[4], a.dflt[5]);
+    }
+    a.st[r] = s;
+    const uint32_t o = a.off[r];
+    if (o < a.D) atomicOr(a.heads + (o >> 5), 1u << (o & 31u));
+    else atomicAdd(a.d_tot + 1, 1u);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_window_count(WindowArgs a) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    if (wbase >= a.D) {
+        if (lane == 0) a.wcount[gw] = 0;
+        return;
+    }
+    uint32_t hb = win_heads_before(a, (uint32_t)wbase);
+    uint32_t run = 0, bad = 0;
+#pragma unroll 2
+    for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+        const uint64_t q = wbase + r * 64 + lane;
+        const bool on = q < a.D;
+        const uint64_t hm = win_head_mask(a, wbase + r * 64);
+        const bool head = (hm >> lane) & 1ull;
+        const uint32_t ri = hb + inbox_mbcnt(hm) + (head ? 1u : 0u) - 1u;   // heads at or before me, less one
+        hb += (uint32_t)__popcll(hm);
+        const bool ok = on && ri < a.R;
+        if (on && !ok) ++bad;
+        const uint32_t flags = ok ? a.st[ri].x >> 16 : WIN_HOST;
+        const uint32_t qos = ok ? a.msg[q] & MSG_QOS : 0u;
+        const uint64_t cm = __ballot(ok && win_counted(flags, qos));
+        if (ok && head) a.hbase[ri] = run + inbox_mbcnt(cm);
+        run += (uint32_t)__popcll(cm);
+    }
+    if (lane == 0) a.wcount[gw] = run;
+    if (bad) atomicAdd(a.d_tot + 1, bad);
+}
+
+__global__ __launch_bounds__(256) void tm_window_plan(WindowArgs a) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint32_t o = a.off[r], on = r + 1 < a.R ? a.off[r + 1] : a.D;
+    if (o >= a.D || on > a.D || on <= o) {   // tm_window_state counted it; nothing of this inbox is classified
+        a.st[r] = make_uint4(WIN_HOST << 16, 0u, 0u, 0u);
+        a.rec[r] = make_uint4(0u, 0u, 0u, 0u);
+        if (o < a.D) atomicAdd(a.d_tot + 1, 1u);
+        return;
+    }
+    const uint32_t base = win_scanned(a, o / INBOX_WAVE_PAIRS) + a.hbase[r];
+    const uint32_t next = r + 1 < a.R ? win_scanned(a, on / INBOX_WAVE_PAIRS) + a.hbase[r + 1] : a.d_tot[0];
+    const uint32_t tot = next - base;   // counted deliveries of the inbox
+    const uint4 s = a.st[r];
+    const uint32_t P = s.x & 0xFFFFu, flags = s.x >> 16, F = s.y, L = s.z, M = s.w;
+    if (flags & WIN_HOST) {
+        a.st[r] = make_uint4(s.x, base, 0u, 0u);
+        a.rec[r] = make_uint4(P, 0u, 0u, 0u);
+        return;
+    }
+    const uint32_t nsend = (flags & WIN_DISCONNECTED) ? 0u : min(F, tot);
+    const uint32_t E = tot - nsend;   // deliveries that enter the queue
+    const uint64_t over = (uint64_t)L + E;
+    const uint64_t drops = (M && over > M) ? over - M : 0ull;
+    const uint32_t dold = (uint32_t)min<uint64_t>(drops, L);
+    const uint32_t dnew = (uint32_t)min<uint64_t>(drops - dold, E);
+    a.st[r] = make_uint4(s.x, base, nsend, nsend + dnew);
+    a.rec[r] = make_uint4((P - 1u + nsend % 65535u) % 65535u + 1u, nsend, E - dnew, dold);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_window_classify(WindowArgs a) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    uint32_t tot[WIN_NDISP] = {};
+    if (wbase < a.D) {
+        uint32_t hb = win_heads_before(a, (uint32_t)wbase);
+        uint32_t run = win_scanned(a, gw), bad = 0;
+#pragma unroll 2
+        for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+            const uint64_t q = wbase + r * 64 + lane;
+            const bool on = q < a.D;
+            const uint64_t hm = win_head_mask(a, wbase + r * 64);
+            const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
+            hb += (uint32_t)__popcll(hm);
+            const bool ok = on && ri < a.R;
+            if (on && !ok) ++bad;
+            const uint4 pl = ok ? a.st[ri] : make_uint4(WIN_HOST << 16, 0u, 0u, 0u);
+            const uint32_t P = pl.x & 0xFFFFu, flags = pl.x >> 16;
+            const uint32_t qos = ok ? a.msg[q] & MSG_QOS : 0u;
+            const bool counted = ok && win_counted(flags, qos);
+            const uint64_t cm = __ballot(counted);
+            const uint32_t rank = run + inbox_mbcnt(cm) - pl.y;
+            run += (uint32_t)__popcll(cm);
+            uint32_t d, id = 0;
+            if (flags & WIN_HOST) d = 5u;                                   // TM_DISP_HOST
+            else if (!counted) d = (flags & WIN_DISCONNECTED) ? 3u : 0u;    // TM_DISP_DROP_QOS0 : TM_DISP_SEND0
+            else if (rank < pl.z) { d = 1u; id = (P - 1u + rank % 65535u) % 65535u + 1u; }   // TM_DISP_SEND
+            else d = rank < pl.w ? 4u : 2u;                                 // TM_DISP_DROP_FULL : TM_DISP_QUEUED
+            if (on) {
+                a.disp[q] = (uint8_t)d;
+                a.pid[q] = (uint16_t)id;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < WIN_NDISP; ++k) tot[k] += (uint32_t)__popcll(__ballot(on && d == k));
+        }
+        if (bad) atomicAdd(a.d_tot + 1, bad);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < WIN_NDISP; ++k) a.wdisp[(uint64_t)gw * 8 + k] = tot[k];
+    }
+}
+static_assert(WIN_NDISP <= 8, "a wave's disposition counts fit its eight words");
+
+// the waves' disposition counts -> totals (one block), as tm_stats_reduce sums the walk's
+__global__ __launch_bounds__(256) void tm_window_totals(WindowArgs a) {
+    __shared__ unsigned long long sh[4][WIN_NDISP];
+    unsigned long long v[WIN_NDISP] = {};
+    for (uint32_t i = threadIdx.x; i < a.nwaves; i += 256)
+#pragma unroll
+        for (uint32_t k = 0; k < WIN_NDISP; ++k) v[k] += a.wdisp[(uint64_t)i * 8 + k];
+#pragma unroll
+    for (uint32_t k = 0; k < WIN_NDISP; ++k) {
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < WIN_NDISP) {
+        const uint32_t k = threadIdx.x;
+        a.totals[k] = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
+    }
+}
+
 // ------------------------------------------ batched predicate (emqx_topic:match/2)
 
 // One thread per name, all rules: the word-by-word clauses of
@@ -4247,6 +4439,21 @@ hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s) {
     if (e != hipSuccess) return e;
     if ((e = launch_scan(sn, s, a.d_tot + 1)) != hipSuccess) return e;
     hipLaunchKernelGGL(tm_deliver_scatter, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_window(const WindowArgs& a, hipStream_t s) {
+    if (!a.D || !a.R || !a.nwaves) return hipGetLastError();
+    const uint32_t ntiles = a.nwaves / (INBOX_BLOCK / 64);
+    hipLaunchKernelGGL(tm_window_state, dim3((a.R + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_window_count, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    ScanArgs sc{};
+    sc.count = a.wcount; sc.row_off = a.wcount; sc.block_sums = a.wbs; sc.n = a.nwaves;   // in place
+    const hipError_t e = launch_scan(sc, s, a.d_tot);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(tm_window_plan, dim3((a.R + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_window_classify, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tm_window_totals, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -237,7 +237,94 @@ class Batch:
         return ((N.TM_DELIVER_UPGRADE_QOS if upgrade_qos else 0) | (N.TM_DELIVER_NL_ALL if nl_all else 0)
                 | (N.TM_DELIVER_SUBIDS if subids else 0))
 
+    def window(self, sessions=None, defaults=None, from_=None, msg=None, upgrade_qos: bool = False,
+               nl_all: bool = False, subids: bool = False):
+        """The session's send window (tm_batch_window): deliver() of the same
+        options, then every delivery's disposition and packet id.  sessions:
+        iterable of dicts {subscriber, next_pkt_id, flags, inflight_free,
+        mqueue_len, mqueue_max} (missing keys as in defaults), ascending by
+        subscriber; defaults: one such dict for subscribers not listed
+        (missing: next_pkt_id 1, connected, unbounded window, empty unbounded
+        queue) -> (deliver()'s 6-tuple, disp u8[D'], packet_ids u16[D'],
+        records u32[R', 4] = next_pkt_id / n_inflight / n_queued /
+        n_dropped_old); window_info holds totals[TM_DISP_*], kernel_ms,
+        deliver_kernel_ms and n_dropped_no_local."""
+        w, _keep = self._window(sessions, defaults, from_, msg, self._deliver_flags(upgrade_qos, nl_all, subids), 0)
+        d = w.inboxes
+        r, t = int(d.n_subscribers), int(d.n_deliveries)
+        cp = lambda p, k, ty=np.uint32: (np.ctypeslib.as_array(p, shape=(k,)).copy() if k  # noqa: E731
+                                         else np.zeros(0, ty))
+        self._window_info(w)
+        rec = (np.ctypeslib.as_array(C.cast(w.records, C.POINTER(C.c_uint32)), shape=(r, 4)).copy() if r
+               else np.zeros((0, 4), np.uint32))
+        return ((cp(d.subscribers, r), cp(d.inbox_offsets, r + 1), cp(d.publishes, t), cp(d.filter_ids, t),
+                 cp(d.msg, t, np.uint8), cp(d.subids, t) if subids else None),
+                cp(w.disp, t, np.uint8), cp(w.packet_ids, t, np.uint16), rec)
+
+    def window_device(self, sessions=None, defaults=None, from_=None, msg=None, upgrade_qos: bool = False,
+                      nl_all: bool = False, subids: bool = False):
+        """TM_WINDOW_DEVICE: -> (n_subscribers, n_deliveries, device ptrs
+        subscribers / offsets / publishes / filter_ids / msg / subids (None
+        without subids) / disp / packet_ids / records); window_info as window()."""
+        w, _keep = self._window(sessions, defaults, from_, msg, self._deliver_flags(upgrade_qos, nl_all, subids),
+                                N.TM_WINDOW_DEVICE)
+        d = w.inboxes
+        ptr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        self._window_info(w)
+        return (int(d.n_subscribers), int(d.n_deliveries), ptr(d.subscribers), ptr(d.inbox_offsets),
+                ptr(d.publishes), ptr(d.filter_ids), ptr(d.msg), ptr(d.subids) if subids else None,
+                ptr(w.disp), ptr(w.packet_ids), ptr(w.records))
+
+    def _window_info(self, w):
+        self.window_info = {"totals": [int(x) for x in w.totals], "kernel_ms": float(w.kernel_ms),
+                            "deliver_kernel_ms": float(w.inboxes.kernel_ms),
+                            "n_dropped_no_local": int(w.inboxes.n_dropped_no_local)}
+
+    SESSION_DEFAULTS = {"subscriber": 0, "next_pkt_id": 1, "flags": 0, "inflight_free": N.TM_SESS_UNBOUNDED,
+                        "mqueue_len": 0, "mqueue_max": 0}
+
+    @classmethod
+    def _session(cls, s, base) -> "N.SessionState":
+        vals = dict(base)
+        unknown = set(s or {}) - set(cls.SESSION_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown session fields {sorted(unknown)}")
+        vals.update({k: int(v) for k, v in (s or {}).items()})
+        for k, v in vals.items():   # ctypes would wrap a value past the field's width before the C range check
+            if not 0 <= v <= 0xFFFFFFFF:
+                raise ValueError(f"session field {k} = {v} out of range")
+        return N.SessionState(**vals)
+
+    def _window(self, sessions, defaults, from_, msg, dflags: int, wflags: int):
+        o, keep = self._deliver_opts(from_, msg, dflags)
+        wo = N.WindowOpts()
+        wo.flags = wflags
+        wo.defaults = self._session(defaults, self.SESSION_DEFAULTS)
+        base = {k: int(getattr(wo.defaults, k)) for k in self.SESSION_DEFAULTS}
+        if isinstance(sessions, np.ndarray):   # u32[n, 6], the struct's words
+            tab = np.ascontiguousarray(sessions, dtype=np.uint32).reshape(-1, 6)
+            wo.n_sessions = len(tab)
+            if len(tab):
+                keep.append(tab)
+                wo.sessions = C.cast(tab.ctypes.data, C.POINTER(N.SessionState))
+        else:
+            ss = [self._session(s, base) for s in (sessions or [])]
+            wo.n_sessions = len(ss)
+            if ss:
+                arr = (N.SessionState * len(ss))(*ss)
+                keep.append(arr)
+                wo.sessions = C.cast(arr, C.POINTER(N.SessionState))
+        w = N.SessionWindow()
+        N.check(self.eng.L.tm_batch_window(self.eng.h, self.h, C.byref(o), C.byref(wo), C.byref(w)), "tm_batch_window")
+        return w, keep
+
     def _deliver(self, from_, msg, flags: int):
+        o, keep = self._deliver_opts(from_, msg, flags)
+        d = N.SessionInboxes()
+        N.check(self.eng.L.tm_batch_deliver(self.eng.h, self.h, C.byref(o), C.byref(d)), "tm_batch_deliver")
+        return d, keep
+
+    def _deliver_opts(self, from_, msg, flags: int):
         o = N.DeliverOpts()
         o.flags = flags
         keep = []
@@ -251,9 +338,7 @@ class Batch:
                 a = np.zeros(1, ty)
             keep.append(a)
             setattr(o, name, a.ctypes.data)
-        d = N.SessionInboxes()
-        N.check(self.eng.L.tm_batch_deliver(self.eng.h, self.h, C.byref(o), C.byref(d)), "tm_batch_deliver")
-        return d, keep
+        return o, keep
 
     def _inboxes(self, flags: int) -> "N.Inboxes":
         d = N.Inboxes()

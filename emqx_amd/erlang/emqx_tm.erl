@@ -26,6 +26,7 @@
         , dispatch_batch/2
         , deliver_batch/2
         , session_deliver_batch/3
+        , session_window_batch/4
         , match_routes_batch/2
         , rules_match/4
         , acl_new/2
@@ -160,6 +161,25 @@ deliver_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
 -spec(session_deliver_batch(reference(), [publish()], [upgrade_qos | nl_all])
       -> [{non_neg_integer(), [delivery()]}] | {error, term()}).
 session_deliver_batch(_Engine, _Publishes, _Flags) -> erlang:nif_error(nif_not_loaded).
+
+%% session_deliver_batch/3, then what emqx_channel:handle_deliver/2
+%% (src/emqx_channel.erl:657-680) decides for every delivery, on the device
+%% (tm_batch_window): emqx_session:deliver/2 (src/emqx_session.erl:421-457) for
+%% a connected session -- packet ids from NextPktId, the inflight window, the
+%% mqueue once it is full -- and enqueue/2 (:459-472) for a disconnected one.
+%% Sessions = {Default, [Session]}, the list ascending by SubId; Default (its
+%% SubId ignored) stands for a subscriber not listed.  host = a session with a
+%% priority table: left to the caller, every delivery comes back as host.
+%% Per subscriber: {SubId, {NextPktId, NDroppedOld, NQueued}, Sends}; the
+%% caller pops NDroppedOld messages off the front of the queue it holds and
+%% appends the deliveries marked queued, in order.
+-type(session() :: {non_neg_integer(), 1..65535, [disconnected | store_qos0 | host],
+                    non_neg_integer() | unbounded, non_neg_integer(), non_neg_integer()}).
+-type(disp() :: send0 | send | queued | dropped_qos0 | dropped_queue_full | host).
+-spec(session_window_batch(reference(), [publish()], {session(), [session()]}, [upgrade_qos | nl_all])
+      -> [{non_neg_integer(), {1..65535, non_neg_integer(), non_neg_integer()},
+           [{disp(), 1..65535 | undefined, delivery()}]}] | {error, term()}).
+session_window_batch(_Engine, _Publishes, _Sessions, _Flags) -> erlang:nif_error(nif_not_loaded).
 
 %% Shared-subscription members (emqx_shared_sub's handle_call({subscribe |
 %% unsubscribe, Group, Topic, SubPid}) and cleanup_down/1,

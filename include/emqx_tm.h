@@ -574,6 +574,96 @@ typedef struct {
 } tm_session_inboxes;
 TM_API int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_session_inboxes* out);
 
+/* The session's send window, per subscriber: what emqx_channel:handle_deliver/2
+ * does with the list tm_batch_deliver leaves, one disposition per delivery.
+ * The call runs tm_batch_deliver(dopts) itself; inboxes.* ARE that call's
+ * arrays, nothing is reordered or compacted, and disp / packet_ids run
+ * parallel to them (D').  TM_DELIVER_DEVICE in dopts is ignored: inboxes.* are
+ * device pointers exactly when TM_WINDOW_DEVICE is set.  The session of inbox S is the entry of `sessions`
+ * with that subscriber, or `defaults`: (P, F, L, M, flags) = (next_pkt_id,
+ * inflight_free, mqueue_len, mqueue_max, flags).  qos = bits 0-1 of msg[q].
+ * Connected channel (src/emqx_channel.erl:672-677): emqx_session:deliver/2
+ * (src/emqx_session.erl:421-457).
+ *   QoS 0 -> TM_DISP_SEND0, packet id 0 for `undefined` (:440-441).
+ *   QoS 1/2, with a = the delivery's 0-based rank among the inbox's QoS > 0
+ *   deliveries: a < F -> TM_DISP_SEND with id ((P - 1 + a) mod 65535) + 1
+ *   (await/3 :535-537; next_pkt_id/1 :665-668 wraps 16#FFFF -> 1); otherwise
+ *   the window is full (emqx_inflight:is_full/1, src/emqx_inflight.erl:83-87;
+ *   it only fills during a batch, so it stays full) and the delivery enters
+ *   the queue with queue rank j = a - F (:446-451).  F = TM_SESS_UNBOUNDED: a
+ *   window of max size 0 is never full (src/emqx_inflight.erl:84-85).
+ *   The new next_pkt_id is ((P - 1 + min(F, A)) mod 65535) + 1, A = the
+ *   inbox's QoS > 0 deliveries.
+ * Disconnected channel (TM_SESS_DISCONNECTED; src/emqx_channel.erl:659-663):
+ * emqx_session:enqueue/2 (:459-472).  QoS 0 without TM_SESS_STORE_QOS0 ->
+ * TM_DISP_DROP_QOS0 (emqx_mqueue:in/2's first clause, src/emqx_mqueue.erl:
+ * 149-150); every other delivery enters the queue with its rank j among the
+ * entering ones.  next_pkt_id is unchanged.
+ * Queue (src/emqx_mqueue.erl:151-168, no priority table: PLen = len).  E
+ * deliveries enter.  M > 0: drops = max(0, L + E - M) in 64 bits -- a full
+ * queue drops its oldest for each message that enters (:160-165);
+ * n_dropped_old = min(drops, L) come off the front of the queue the host
+ * holds, and an entering delivery with j < drops - n_dropped_old was pushed
+ * out by a later one: TM_DISP_DROP_FULL.  The others are TM_DISP_QUEUED.
+ * M = 0 (?MAX_LEN_INFINITY): nothing drops.
+ * TM_SESS_HOST: every delivery of the inbox is TM_DISP_HOST; the record keeps
+ * P and holds zeros otherwise.
+ * Not here: priority tables (use TM_SESS_HOST), maybe_ack / maybe_nack of
+ * shared deliveries (not in the inboxes), message expiry.
+ * The call counts as a dispatch of the batch (pointer lifetime as
+ * tm_batch_deliver).  The session table is uploaded per call: a second call
+ * on the same waited batch with other sessions sees them.  Without
+ * TM_WINDOW_DEVICE the results are batch-owned pinned memory.
+ * Errors as tm_batch_deliver, and TM_EINVAL + tm_last_error() for sessions
+ * not strictly ascending by subscriber, a next_pkt_id outside 1..65535
+ * (defaults included), mqueue_len > mqueue_max with mqueue_max > 0, unknown
+ * session or window flags, NULL sessions with n_sessions > 0, NULL wopts.
+ * TM_ENODEV on a host-only engine.  TM_EIO + tm_last_error() if a kernel met
+ * an index past D', R' or n_sessions. */
+#define TM_SESS_DISCONNECTED 1u   /* conn_state = disconnected: the enqueue/2 path */
+#define TM_SESS_STORE_QOS0   2u   /* #mqueue.store_qos0 */
+#define TM_SESS_HOST         4u   /* leave this session to the host (it has a priority table) */
+#define TM_SESS_UNBOUNDED    0xFFFFFFFFu  /* inflight_free when the window's max size is 0 */
+#define TM_WINDOW_DEVICE     1u   /* no copy back: device pointers of the batch */
+#define TM_DISP_SEND0     0u  /* QoS 0: sent with packet id `undefined` */
+#define TM_DISP_SEND      1u  /* packet id assigned, inflight */
+#define TM_DISP_QUEUED    2u  /* in the mqueue when the batch ends */
+#define TM_DISP_DROP_QOS0 3u  /* 'delivery.dropped.qos0_msg' */
+#define TM_DISP_DROP_FULL 4u  /* entered the queue, pushed out as the oldest: 'delivery.dropped.queue_full' */
+#define TM_DISP_HOST      5u  /* TM_SESS_HOST */
+#define TM_DISP_COUNT     6u
+typedef struct {
+    uint32_t subscriber;    /* the caller's id, as in tm_subscribe */
+    uint32_t next_pkt_id;   /* 1..65535 */
+    uint32_t flags;         /* TM_SESS_* */
+    uint32_t inflight_free; /* max size - size of the inflight window, or TM_SESS_UNBOUNDED */
+    uint32_t mqueue_len;    /* #mqueue.len now */
+    uint32_t mqueue_max;    /* #mqueue.max_len; 0 = infinity */
+} tm_session_state;
+typedef struct {
+    const tm_session_state* sessions;  /* n_sessions, strictly ascending by subscriber; NULL when 0 */
+    uint32_t                n_sessions;
+    tm_session_state        defaults;  /* for a subscriber not listed (subscriber field ignored) */
+    uint32_t                flags;     /* TM_WINDOW_DEVICE */
+} tm_window_opts;
+typedef struct {
+    uint32_t next_pkt_id;    /* the new value */
+    uint32_t n_inflight;     /* deliveries that entered the window */
+    uint32_t n_queued;       /* deliveries of this batch in the queue at the end */
+    uint32_t n_dropped_old;  /* messages to pop from the front of the queue the host holds */
+} tm_window_record;
+typedef struct {
+    tm_session_inboxes      inboxes;      /* tm_batch_deliver(dopts)'s result (device pointers with TM_WINDOW_DEVICE) */
+    const uint8_t*          disp;         /* D': TM_DISP_* */
+    const uint16_t*         packet_ids;   /* D': 0 unless disp is TM_DISP_SEND */
+    const tm_window_record* records;      /* R' */
+    uint64_t                totals[TM_DISP_COUNT];   /* deliveries per disposition */
+    float                   kernel_ms;    /* device time of the window kernels only */
+    uint32_t                pad0;
+} tm_session_window;
+TM_API int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
+                           tm_session_window* out);
+
 /* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
 /* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
  * 287-305) of the local node.  group_dest = the aggregated dest id the caller
