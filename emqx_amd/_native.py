@@ -314,6 +314,9 @@ SIGNATURES = {
     "tm_shared_member_down": (C.c_int, [P, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_shared_members": (C.c_int, [P, U8P, SZ, C.c_uint32, P, C.c_uint32, C.POINTER(C.c_uint32)]),
     "tm_batch_dispatch_shared": (C.c_int, [P, P, C.POINTER(SharedOpts), C.POINTER(SharedDeliveries)]),
+    "tm_shared_subscribe_opts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.c_uint32, C.POINTER(SubOpts)]),
+    "tm_batch_shared_mode": (C.c_int, [P, P, C.POINTER(SharedOpts)]),
+    "tm_batch_inbox_groups": (C.c_int, [P, P, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32))]),
     "tm_acl_create": (C.c_int, [P, C.POINTER(AclRule), C.c_uint32, C.POINTER(P)]),
     "tm_acl_free": (None, [P, P]),
     "tm_acl_check": (C.c_int, [P, P, C.POINTER(AclClients), P, P, P, P, C.c_uint32, P, P]),

@@ -44,7 +44,7 @@ static ERL_NIF_TERM ATOM_OK, ATOM_ERROR, ATOM_TRUE, ATOM_FALSE, ATOM_UNDEFINED, 
     ATOM_EOVERFLOW, ATOM_NOT_FOUND, ATOM_WRITE, ATOM_DELETE_OBJECT, ATOM_EMQX_TM_MATCH,
     ATOM_ALLOW, ATOM_DENY, ATOM_NOMATCH, ATOM_NONE, ATOM_ALL, ATOM_CLIENT, ATOM_USER, ATOM_IPADDR, ATOM_AND, ATOM_OR,
     ATOM_EQ, ATOM_PUBLISH, ATOM_SUBSCRIBE, ATOM_PUBSUB, ATOM_RANDOM, ATOM_ROUND_ROBIN, ATOM_HASH, ATOM_UPGRADE_QOS,
-    ATOM_NL_ALL, ATOM_DISCONNECTED, ATOM_STORE_QOS0, ATOM_HOST, ATOM_UNBOUNDED, ATOM_DISP[TM_DISP_COUNT];
+    ATOM_NL_ALL, ATOM_SHARED_HASH, ATOM_SHARED_RANDOM, ATOM_SHARED_ROUND_ROBIN, ATOM_DISCONNECTED, ATOM_STORE_QOS0, ATOM_HOST, ATOM_UNBOUNDED, ATOM_DISP[TM_DISP_COUNT];
 
 /* set while a match callback runs on the engine's completion thread */
 static __thread int in_engine_callback;
@@ -575,25 +575,102 @@ static int cmp_u32(const void* a, const void* b) {
     return x < y ? -1 : x > y;
 }
 
+/* The strategy flag of deliver_batch/3, session_deliver_batch/3 and
+ * session_window_batch/4: shared_round_robin | {shared_random, Seed} |
+ * {shared_hash, [Key]} (one erlang:phash2(ClientId) per publish).  With one of
+ * them the batch is armed (tm_batch_shared_mode): the shared deliveries are in
+ * the inboxes, each as {PublishIndex0, {Filter, GroupDestId}} where an ordinary
+ * one is {PublishIndex0, Filter}.  1 = the term is such a flag (parsed into so;
+ * *keys is allocated for shared_hash, *nk its length), 0 = it is not, -1 = it
+ * is one and malformed. */
+static int get_shared_flag(ErlNifEnv* env, ERL_NIF_TERM t, tm_shared_opts* so, uint32_t** keys, unsigned* nk) {
+    const ERL_NIF_TERM* el;
+    int arity;
+    if (enif_is_identical(t, ATOM_SHARED_ROUND_ROBIN)) {
+        so->strategy = TM_SHARED_ROUND_ROBIN;
+        return 1;
+    }
+    if (!enif_get_tuple(env, t, &arity, &el) || arity != 2) return 0;
+    if (enif_is_identical(el[0], ATOM_SHARED_RANDOM)) {
+        unsigned seed;
+        if (!enif_get_uint(env, el[1], &seed)) return -1;
+        so->strategy = TM_SHARED_RANDOM;
+        so->seed = seed;
+        return 1;
+    }
+    if (!enif_is_identical(el[0], ATOM_SHARED_HASH)) return 0;
+    if (*keys || !enif_get_list_length(env, el[1], nk)) return -1;
+    uint32_t* k = enif_alloc(sizeof(uint32_t) * (*nk ? *nk : 1));
+    if (!k) return -1;
+    ERL_NIF_TERM l = el[1], h;
+    for (unsigned i = 0; i < *nk; ++i) {
+        unsigned v;
+        if (!enif_get_list_cell(env, l, &h, &l) || !enif_get_uint(env, h, &v)) {
+            enif_free(k);
+            return -1;
+        }
+        k[i] = v;
+    }
+    *keys = k;
+    so->strategy = TM_SHARED_HASH;
+    so->keys = k;
+    return 1;
+}
+
+/* {PublishIndex0, Filter}, or {PublishIndex0, {Filter, GroupDestId}} for a shared delivery */
+static ERL_NIF_TERM delivery_pair(ErlNifEnv* env, uint32_t publish, ERL_NIF_TERM filter, const uint32_t* grp, uint32_t q) {
+    if (grp && grp[q] != TM_NONE) filter = enif_make_tuple2(env, filter, enif_make_uint(env, grp[q]));
+    return enif_make_tuple2(env, enif_make_uint(env, publish), filter);
+}
+
 /* deliver_batch(Engine, [Topic]) -> [{SubId, [{PublishIndex0, Filter}]}]
  * The deliveries of dispatch_batch grouped by subscriber on the device
  * (tm_batch_inboxes): SubIds ascending, each with its deliveries in mailbox
  * order (src/emqx_broker.erl:298-302) -- the list emqx_misc:drain_deliver/1
  * (src/emqx_misc.erl:128-142) would collect.  The distinct filters are copied
- * out once (tm_filters_copy) and every delivery shares its filter's binary. */
+ * out once (tm_filters_copy) and every delivery shares its filter's binary.
+ * deliver_batch(Engine, [Topic], Flags): Flags = [] or one strategy flag
+ * (get_shared_flag) -- the shared deliveries are then in the inboxes too. */
 static ERL_NIF_TERM nif_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
     engine_res* r;
-    unsigned n;
+    unsigned n, nf = 0, nk = 0;
     uint8_t* buf;
     uint64_t* offs;
-    (void)argc;
-    if (!get_engine(env, argv[0], &r) || !pack_binaries(env, argv[1], &n, &buf, &offs)) return enif_make_badarg(env);
+    uint32_t* keys = NULL;
+    const uint32_t* grp = NULL;
+    tm_shared_opts so;
+    int armed = 0;
+    memset(&so, 0, sizeof so);
+    /* deliver_batch/3: Flags = [] | [shared_round_robin | {shared_random, Seed} | {shared_hash, [Key]}] */
+    if (argc == 3) {
+        ERL_NIF_TERM head, tail = argv[2];
+        if (!enif_get_list_length(env, argv[2], &nf)) return enif_make_badarg(env);
+        for (unsigned i = 0; i < nf; i++) {
+            if (!enif_get_list_cell(env, tail, &head, &tail) || armed ||
+                get_shared_flag(env, head, &so, &keys, &nk) != 1) {
+                enif_free(keys);
+                return enif_make_badarg(env);
+            }
+            armed = 1;
+        }
+    }
+    if (!get_engine(env, argv[0], &r) || !pack_binaries(env, argv[1], &n, &buf, &offs)) {
+        enif_free(keys);
+        return enif_make_badarg(env);
+    }
+    if (armed && so.strategy == TM_SHARED_HASH && nk != n) {
+        enif_free(keys); enif_free(buf); enif_free(offs);
+        return enif_make_badarg(env);
+    }
     tm_batch* b;
     tm_inboxes ib;
     packed p;
     int rc = run_batch(r->e, buf, offs, n, &b);
     enif_free(buf); enif_free(offs);
+    if (!rc && armed) rc = tm_batch_shared_mode(r->e, b, &so);
+    enif_free(keys);   /* copied at the call */
     if (!rc) rc = tm_batch_inboxes(r->e, b, 0, &ib);
+    if (!rc && armed) rc = tm_batch_inbox_groups(r->e, b, 0, &grp);
     if (rc) {
         if (b) tm_batch_free(r->e, b);
         return err(env, rc);
@@ -626,8 +703,7 @@ static ERL_NIF_TERM nif_deliver_batch(ErlNifEnv* env, int argc, const ERL_NIF_TE
         for (uint32_t q = ib.inbox_offsets[s + 1]; q-- > ib.inbox_offsets[s];) {
             const uint32_t* u = bsearch(&ib.filter_ids[q], uniq, nu, sizeof(uint32_t), cmp_u32);
             if (!u || !live[u - uniq]) continue;   /* deleted meanwhile and its id reused */
-            box = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, ib.publishes[q]), term[u - uniq]),
-                                      box);
+            box = enif_make_list_cell(env, delivery_pair(env, ib.publishes[q], term[u - uniq], grp, q), box);
         }
         out = enif_make_list_cell(env, enif_make_tuple2(env, enif_make_uint(env, ib.subscribers[s]), box), out);
     }
@@ -643,7 +719,8 @@ static int get_bool(ERL_NIF_TERM t, unsigned* out) {
     return 0;
 }
 
-/* session_deliver_batch(Engine, [{FromSubId | none, QoS, Retain, Retained, Topic}], [upgrade_qos | nl_all])
+/* session_deliver_batch(Engine, [{FromSubId | none, QoS, Retain, Retained, Topic}],
+ *                       [upgrade_qos | nl_all | StrategyFlag])   (StrategyFlag: get_shared_flag, at most one)
  *   -> [{SubId, [{{PublishIndex0, Filter}, QoS, Retain, NL, SubIdent}]}]
  * deliver_batch after emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693)
  * and emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529), on the
@@ -666,12 +743,28 @@ static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM
     if (!get_engine(env, eng, &r) || !enif_get_list_length(env, pubs, &n) || !enif_get_list_length(env, flags, &nf))
         return enif_make_badarg(env);
     tm_deliver_opts o = {NULL, NULL, TM_DELIVER_SUBIDS};
+    tm_shared_opts so;
+    uint32_t* keys = NULL;
+    const uint32_t* grp = NULL;
+    unsigned nk = 0;
+    int armed = 0;
+    memset(&so, 0, sizeof so);
     ERL_NIF_TERM head, tail = flags;
     for (unsigned i = 0; i < nf; i++) {
-        if (!enif_get_list_cell(env, tail, &head, &tail)) return enif_make_badarg(env);
-        if (enif_is_identical(head, ATOM_UPGRADE_QOS)) o.flags |= TM_DELIVER_UPGRADE_QOS;
+        int sf = 0;
+        if (!enif_get_list_cell(env, tail, &head, &tail)) sf = -1;
+        else if (enif_is_identical(head, ATOM_UPGRADE_QOS)) o.flags |= TM_DELIVER_UPGRADE_QOS;
         else if (enif_is_identical(head, ATOM_NL_ALL)) o.flags |= TM_DELIVER_NL_ALL;
-        else return enif_make_badarg(env);
+        else if (armed || (sf = get_shared_flag(env, head, &so, &keys, &nk)) != 1) sf = -1;
+        else armed = 1;
+        if (sf < 0) {
+            enif_free(keys);
+            return enif_make_badarg(env);
+        }
+    }
+    if (armed && so.strategy == TM_SHARED_HASH && nk != n) {
+        enif_free(keys);
+        return enif_make_badarg(env);
     }
     uint32_t* from = enif_alloc(sizeof(uint32_t) * (n ? n : 1));
     uint8_t* msg = enif_alloc(n ? n : 1);
@@ -700,7 +793,7 @@ static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM
     if (ok) buf = enif_alloc(total ? total : 1);
     if (!ok || !buf) {
         out = (have && !ok) ? enif_make_badarg(env) : err(env, TM_ENOMEM);
-        enif_free(from); enif_free(msg); enif_free(offs); enif_free(bins);
+        enif_free(from); enif_free(msg); enif_free(offs); enif_free(bins); enif_free(keys);
         return out;
     }
     offs[n] = total;
@@ -714,12 +807,15 @@ static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM
     packed p;
     int rc = run_batch(r->e, buf, offs, n, &b);
     enif_free(buf); enif_free(offs);
+    if (!rc && armed) rc = tm_batch_shared_mode(r->e, b, &so);
+    enif_free(keys);   /* copied at the call */
     if (!rc && wo) {
         rc = tm_batch_window(r->e, b, &o, wo, &sw);
         si = sw.inboxes;
     } else if (!rc) {
         rc = tm_batch_deliver(r->e, b, &o, &si);
     }
+    if (!rc && armed) rc = tm_batch_inbox_groups(r->e, b, 0, &grp);
     enif_free(from); enif_free(msg);
     if (rc) {
         if (b) tm_batch_free(r->e, b);
@@ -756,7 +852,7 @@ static ERL_NIF_TERM session_batch(ErlNifEnv* env, ERL_NIF_TERM eng, ERL_NIF_TERM
             if (!u || !live[u - uniq]) continue;   /* deleted meanwhile and its id reused */
             const uint8_t m = si.msg[q];
             ERL_NIF_TERM dl =
-                enif_make_tuple5(env, enif_make_tuple2(env, enif_make_uint(env, si.publishes[q]), term[u - uniq]),
+                enif_make_tuple5(env, delivery_pair(env, si.publishes[q], term[u - uniq], grp, q),
                                  enif_make_uint(env, m & 3u), (m & TM_MSG_RETAIN) ? ATOM_TRUE : ATOM_FALSE,
                                  (m & TM_MSG_NL) ? ATOM_TRUE : ATOM_FALSE, enif_make_uint(env, si.subids[q]));
             if (wo) {
@@ -895,6 +991,29 @@ static ERL_NIF_TERM nif_shared_subscribe(ErlNifEnv* env, int argc, const ERL_NIF
         !enif_get_uint(env, argv[2], &group) || !enif_get_uint(env, argv[3], &sub))
         return enif_make_badarg(env);
     int rc = tm_shared_subscribe(r->e, b.data, b.size, group, sub);
+    return rc ? err(env, rc) : ATOM_OK;
+}
+
+/* shared_subscribe(Engine, Topic, GroupDestId, SubId, {QoS, NL, RAP, RH, SubIdent}) -> ok
+ * emqx_broker:subscribe/3 with share => Group (src/emqx_broker.erl:127-136,
+ * 145-163) in front of shared_subscribe/4: the options go under {SubId, Topic}
+ * (tm_shared_subscribe_opts); a key that has options already only merges them. */
+static ERL_NIF_TERM nif_shared_subscribe_opts(ErlNifEnv* env, int argc, const ERL_NIF_TERM argv[]) {
+    engine_res* r;
+    ErlNifBinary b;
+    unsigned group, sub, v[5];
+    const ERL_NIF_TERM* t;
+    int arity;
+    (void)argc;
+    if (!get_engine(env, argv[0], &r) || !enif_inspect_binary(env, argv[1], &b) ||
+        !enif_get_uint(env, argv[2], &group) || !enif_get_uint(env, argv[3], &sub) ||
+        !enif_get_tuple(env, argv[4], &arity, &t) || arity != 5)
+        return enif_make_badarg(env);
+    for (int i = 0; i < 5; ++i)
+        if (!enif_get_uint(env, t[i], &v[i])) return enif_make_badarg(env);
+    if (v[0] > 2 || v[1] > 1 || v[2] > 1 || v[3] > 2 || v[4] > TM_SUBID_MAX) return enif_make_badarg(env);
+    const tm_subopts o = {(uint8_t)v[0], (uint8_t)v[1], (uint8_t)v[2], (uint8_t)v[3], v[4]};
+    int rc = tm_shared_subscribe_opts(r->e, b.data, b.size, group, sub, &o);
     return rc ? err(env, rc) : ATOM_OK;
 }
 
@@ -1383,6 +1502,9 @@ static int load(ErlNifEnv* env, void** priv, ERL_NIF_TERM info) {
     ATOM_STORE_QOS0 = enif_make_atom(env, "store_qos0");
     ATOM_HOST = enif_make_atom(env, "host");
     ATOM_UNBOUNDED = enif_make_atom(env, "unbounded");
+    ATOM_SHARED_HASH = enif_make_atom(env, "shared_hash");
+    ATOM_SHARED_RANDOM = enif_make_atom(env, "shared_random");
+    ATOM_SHARED_ROUND_ROBIN = enif_make_atom(env, "shared_round_robin");
     ATOM_DISP[TM_DISP_SEND0] = enif_make_atom(env, "send0");
     ATOM_DISP[TM_DISP_SEND] = enif_make_atom(env, "send");
     ATOM_DISP[TM_DISP_QUEUED] = enif_make_atom(env, "queued");
@@ -1410,6 +1532,7 @@ static ErlNifFunc funcs[] = {
     {"subscriber_down", 3, nif_subscriber_down, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"dispatch_batch", 2, nif_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"deliver_batch", 2, nif_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"deliver_batch", 3, nif_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"session_deliver_batch", 3, nif_session_deliver_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"session_window_batch", 4, nif_session_window_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"match_routes_batch", 2, nif_match_routes_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},
@@ -1418,6 +1541,7 @@ static ErlNifFunc funcs[] = {
     {"acl_new", 2, nif_acl_new, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"acl_check", 4, nif_acl_check, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"shared_subscribe", 4, nif_shared_subscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
+    {"shared_subscribe", 5, nif_shared_subscribe_opts, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"shared_unsubscribe", 4, nif_shared_unsubscribe, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"shared_member_down", 2, nif_shared_member_down, ERL_NIF_DIRTY_JOB_IO_BOUND},
     {"shared_dispatch_batch", 4, nif_shared_dispatch_batch, ERL_NIF_DIRTY_JOB_IO_BOUND},

@@ -769,6 +769,19 @@ int tm_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t s
     }
 }
 
+int tm_shared_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest, uint32_t subscriber,
+                             const tm_subopts* opts) {
+    if (!e || (!topic && len)) return TM_EINVAL;
+    const tm_subopts o = opts ? *opts : tm_subopts{};
+    if (int rc = subopts_check("tm_shared_subscribe_opts", &o, SUBOPT_ALL)) return rc;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    try {
+        return e->shared_subscribe_opts(topic, len, group_dest, subscriber, o);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
 int tm_set_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, uint32_t mask,
                    const tm_subopts* opts) {
     if (!e || (!topic && len)) return TM_EINVAL;

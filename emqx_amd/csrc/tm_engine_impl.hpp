@@ -520,17 +520,37 @@ struct tm_batch {
         PinBuf<unsigned long long> h_gtot64;
         PinBuf<uint32_t> h_gkeys, h_grow, h_gfid, h_ggrp, h_gsub;
         Event gev[4];   // around count + scan + rows, around the pick
+        DevBuf<uint32_t> d_gent;   // armed inboxes: the match entry of every pick
     } sh;
 
     // per-subscriber inboxes (tm_batch_inboxes): the sort's second key array and
-    // both payload arrays (the first key array is fan.d_fout), the pass table,
+    // both payload arrays (the first key array is fan.d_fout; d_mkey when armed), the pass table,
     // the finish's head counts, and the result with its pinned mirror
     struct Inbox {
         DevBuf<uint32_t> d_val0, d_key1, d_val1, d_pubof, d_hist, d_hbs, d_hcount, d_hcbs, d_R;
         DevBuf<uint32_t> d_pub, d_fid, d_sub, d_off;
         PinBuf<uint32_t> h_R, h_pub, h_fid, h_sub, h_off;
         Event iev0, iev1;   // around the inbox kernels
+        // armed batch (tm_batch_shared_mode): the merged list L' as the sort's
+        // first input (d_mkey, d_mval), one record per merged position, the
+        // groups of the result and the merge's error count
+        DevBuf<uint32_t> d_mkey, d_mval, d_grp, d_merr;
+        DevBuf<uint4> d_mrec;
+        PinBuf<uint32_t> h_grp;
+        const uint32_t* key0 = nullptr;   // the sort's first key array of the last call (fan.d_fout or d_mkey)
+        bool merged = false;         // the last inboxes / deliver / window call ran armed
+        bool grp_host = false;       // h_grp holds the last call's groups
+        const uint32_t* d_groups = nullptr;   // the last call's groups on the device (after deliver's compaction: dlv.d_grp)
+        uint32_t n_groups = 0;       // their count
     } inbox;
+
+    // tm_batch_shared_mode: armed -> inboxes / deliver / window work on L'
+    struct SharedMode {
+        bool armed = false;
+        uint32_t strategy = 0;
+        uint64_t seed = 0;
+        std::vector<uint32_t> keys;   // TM_SHARED_HASH: copied at the call
+    } shmode;
 
     // what the session sends (tm_batch_deliver): the per-call inputs (from,
     // msg) and their pinned staging, the per-inbox and per-delivery scratch,
@@ -540,6 +560,7 @@ struct tm_batch {
         DevBuf<uint8_t> d_min, d_own, d_emsg;
         DevBuf<uint2> d_rng;
         DevBuf<uint32_t> d_sub, d_off, d_pub, d_fid, d_subid;
+        DevBuf<uint32_t> d_grp;   // armed batch: the groups after the compaction
         DevBuf<uint8_t> d_msg;
         PinBuf<uint32_t> h_from, h_tot, h_sub, h_off, h_pub, h_fid, h_subid;
         PinBuf<uint8_t> h_min, h_msg;
@@ -1901,6 +1922,17 @@ struct tm_engine {
     // *out = the options of (topic, sub); TM_ENOENT when not subscribed, TM_EIO
     // + tm_last_error() if the table is out of step with the bag
     int find_subopts(const uint8_t* t, size_t len, uint32_t sub, tm_subopts** out);
+    // options a shared subscribe stored (the reference's `share` key of the
+    // SubOpts map, src/emqx_broker.erl:145-163): subscriber -> (topic, group,
+    // options).  A (subscriber, topic) has at most one entry here or in opts_of.
+    struct SharedOpt {
+        std::string topic;
+        uint32_t group;
+        tm_subopts o;
+    };
+    std::unordered_map<uint32_t, std::vector<SharedOpt>> shared_opts_of;
+    // deletes the entry of (sub, topic) owned by group, if there is one
+    void shared_opts_erase(const std::string& k, uint32_t group, uint32_t sub);
     // subscribe/3 (:127-136): new -> subscribe + store; subscribed already -> merge
     int subscribe_opts(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest, const tm_subopts& o);
     // set_subopts/2 (:388-393) for the fields of mask
@@ -1956,6 +1988,8 @@ struct tm_engine {
     std::vector<uint2> h_gupd;                // per slot: {member count, epoch}
 
     int shared_subscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub);
+    // subscribe/3 with share => Group: Existed -> merge only; else store, then shared_subscribe
+    int shared_subscribe_opts(const uint8_t* t, size_t len, uint32_t group, uint32_t sub, const tm_subopts& o);
     int shared_unsubscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub);
     int shared_member_down(uint32_t sub, uint64_t* n_removed);
     int shared_members(const uint8_t* t, size_t len, uint32_t group, uint32_t* buf, uint32_t cap, uint32_t* n);
@@ -1963,7 +1997,11 @@ struct tm_engine {
     // uploaded to a replica holding an older build, whose cursors are then folded
     int sync_shared(Replica& R);
     // tm_batch_dispatch_shared: one picked delivery per (publish, filter, group)
-    int batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_shared_deliveries* out);
+    // entries (armed tm_batch_inboxes): the pick also writes every delivery's
+    // match entry into b->sh.d_gent, and slots it leaves unwritten hold NONE
+    int batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_shared_deliveries* out, bool entries = false);
+    // tm_batch_inbox_groups: the groups of the batch's last inboxes / deliver / window call
+    int batch_inbox_groups(tm_batch* b, uint32_t flags, const uint32_t** groups);
 
     // tm_rules_match: rules tokenised with their own dictionary, names against it
     int rules_match(Replica& R, const uint8_t* names, const uint64_t* noffs, uint32_t n, const uint8_t* rules,

@@ -135,9 +135,17 @@ int tm_engine::subscribe(const uint8_t* t, size_t len, uint32_t sub, uint32_t no
 
 int tm_engine::find_subopts(const uint8_t* t, size_t len, uint32_t sub, tm_subopts** out) {
     *out = nullptr;
+    const std::string k((const char*)t, len);
+    // an entry a shared subscribe stored (tm_shared_subscribe_opts)
+    auto shi = shared_opts_of.find(sub);
+    if (shi != shared_opts_of.end())
+        for (auto& e : shi->second)
+            if (e.topic == k) {
+                *out = &e.o;
+                return TM_OK;
+            }
     auto it = topics_of.find(sub);
     if (it == topics_of.end()) return TM_ENOENT;
-    const std::string k((const char*)t, len);
     auto ti = std::find(it->second.begin(), it->second.end(), k);
     if (ti == it->second.end()) return TM_ENOENT;
     auto oit = opts_of.find(sub);
@@ -169,7 +177,13 @@ int tm_engine::set_subopts(const uint8_t* t, size_t len, uint32_t sub, uint32_t 
 int tm_engine::subscribe_opts(const uint8_t* t, size_t len, uint32_t sub, uint32_t node_dest, const tm_subopts& o) {
     std::string k((const char*)t, len);
     auto it = topics_of.find(sub);
-    if (it != topics_of.end() && std::find(it->second.begin(), it->second.end(), k) != it->second.end()) {
+    bool existed = it != topics_of.end() && std::find(it->second.begin(), it->second.end(), k) != it->second.end();
+    if (!existed) {   // options a shared subscribe stored under {SubPid, Topic}: Existed as well
+        auto shi = shared_opts_of.find(sub);
+        if (shi != shared_opts_of.end())
+            for (const auto& e : shi->second) existed = existed || e.topic == k;
+    }
+    if (existed) {
         // subscribed already: only the subopts change (:127-139) -- maps:merge(Old, New),
         // where New holds the four flags and a subid only when one was given (:139-142)
         const uint32_t mask = TM_SUBOPT_QOS | TM_SUBOPT_NL | TM_SUBOPT_RAP | TM_SUBOPT_RH | (o.subid ? TM_SUBOPT_SUBID : 0u);
@@ -426,19 +440,40 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     if (!b->done) return einval("tm_batch_inboxes: the batch has not been waited for");
     if (b->dedup) return einval("tm_batch_inboxes: a TM_BATCH_DEDUP batch (an inbox entry names a publish)");
     if (b->total > MAX_RESULT) return TM_EOVERFLOW;
+    // armed (tm_batch_shared_mode): the sort runs over L', the fan-out's
+    // deliveries merged with one pick per (entry, group)
+    const bool armed = b->shmode.armed;
+    if (armed && b->shmode.strategy == TM_SHARED_HASH && b->shmode.keys.size() != b->n)
+        return einval("tm_batch_inboxes: the batch was re-prepared since tm_batch_shared_mode copied its keys");
     tm_deliveries dl{};
     int rc;
-    if ((rc = batch_dispatch(b, TM_DISPATCH_DEVICE, &dl, true))) return rc;   // returns with the stream idle
+    // returns with the stream idle
+    if ((rc = batch_dispatch(b, TM_DISPATCH_DEVICE | (armed ? TM_DISPATCH_MATCH_OFFSETS : 0u), &dl, true))) return rc;
     Replica& R = *b->rep;
     const hipStream_t stream = R.stream;
     tm_batch::Inbox& ib = b->inbox;
+    ib.merged = false;
+    ib.grp_host = false;
+    ib.d_groups = nullptr;
+    ib.n_groups = 0;
+    ib.key0 = b->fan.d_fout.p;
     const uint32_t n = b->n, m = (uint32_t)b->total;
-    const uint32_t D = (uint32_t)dl.n_deliveries;   // <= MAX_RESULT (batch_dispatch checked)
+    const uint32_t D0 = (uint32_t)dl.n_deliveries;   // <= MAX_RESULT (batch_dispatch checked)
+    uint32_t DS = 0;                                  // shared deliveries
+    if (armed) {
+        const tm_shared_opts so{b->shmode.strategy, TM_SHARED_DEVICE, b->shmode.keys.data(), b->shmode.seed};
+        tm_shared_deliveries sd{};
+        if ((rc = batch_dispatch_shared(b, &so, &sd, true))) return rc;   // returns with the stream idle
+        if ((uint64_t)D0 + sd.n_deliveries > MAX_RESULT) return TM_EOVERFLOW;
+        DS = (uint32_t)sd.n_deliveries;
+    }
+    const uint32_t D = D0 + DS;
     const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
     const uint32_t bits = max_sub ? 32u - (uint32_t)__builtin_clz(max_sub) : 0u;
     const uint32_t passes = std::max(1u, (bits + 7) / 8);
     // a subscriber with a delivery has a subscription: R <= both
-    const uint32_t rcap = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(D, topics_of.size()));
+    const uint32_t rcap = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>(D, topics_of.size() + (armed ? shared_topics_of.size() : 0)));
     const size_t dd = std::max<size_t>(D, 1), nh = (size_t)256 * ntiles;
     if ((rc = ib.d_key1.reserve(dd))) return rc;
     if ((rc = ib.d_val1.reserve(dd))) return rc;
@@ -448,7 +483,8 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     if ((rc = ib.d_hcount.reserve((size_t)ntiles + 1))) return rc;
     if ((rc = ib.d_hcbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
     if ((rc = ib.d_R.reserve(1))) return rc;
-    if ((rc = ib.h_R.reserve(1))) return rc;
+    if ((rc = ib.h_R.reserve(2))) return rc;
+    ib.h_R.p[1] = 0;
     if ((rc = ib.d_pub.reserve(dd))) return rc;
     if ((rc = ib.d_fid.reserve(dd))) return rc;
     if ((rc = ib.d_sub.reserve(rcap))) return rc;
@@ -462,17 +498,47 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     a.hist = ib.d_hist.p; a.hbs = ib.d_hbs.p; a.rcap = rcap; a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
     a.d_R = ib.d_R.p; a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
     a.inbox_offsets = ib.d_off.p;
+    MergeArgs ma{};
+    if (armed) {
+        if ((rc = ib.d_mkey.reserve(dd))) return rc;
+        if ((rc = ib.d_mval.reserve(dd))) return rc;
+        if ((rc = ib.d_mrec.reserve(dd))) return rc;
+        if ((rc = ib.d_grp.reserve(dd))) return rc;
+        if ((rc = ib.d_merr.reserve(1))) return rc;
+        ma.fsub = b->fan.d_fout.p; ma.fent = ib.d_val0.p; ma.nd = D0;
+        ma.gsub = b->sh.d_gsub.p; ma.ggrp = b->sh.d_ggrp.p; ma.gent = b->sh.d_gent.p; ma.ns = DS;
+        ma.m = m; ma.moff = b->fan.d_moff.p; ma.eoff = b->sh.es.eoff.p; ma.bsums = b->sh.es.bsums.p;
+        ma.pub_of = ib.d_pubof.p; ma.ids = b->dcsr.d_ids.p;
+        ma.cap = D; ma.key = ib.d_mkey.p; ma.val = ib.d_mval.p; ma.rec = ib.d_mrec.p;
+        ma.err = ib.d_merr.p;
+        a.key0 = ib.d_mkey.p; a.val0 = ib.d_mval.p;
+        a.mrec = ib.d_mrec.p; a.groups = ib.d_grp.p;
+        ib.key0 = ib.d_mkey.p;
+        ib.merged = true;
+        ib.d_groups = ib.d_grp.p;
+        ib.n_groups = D;
+    }
     uint32_t nsub = 0;
     float ms = 0.f;
     if (D) {
         HIP_OK(hipEventRecord(ib.iev0.e, stream));
         HIP_OK(launch_inbox_pubof(a, stream));
+        if (armed) {   // behind pubof: the merge stores every delivery's publish
+            HIP_OK(hipMemsetAsync(ib.d_merr.p, 0, 4, stream));
+            HIP_OK(launch_inbox_merge(ma, stream));
+        }
         HIP_OK(launch_inbox_sort(a, stream));
         HIP_OK(launch_inbox_finish(a, stream));
         HIP_OK(hipEventRecord(ib.iev1.e, stream));
         HIP_OK(hipMemcpyAsync(ib.h_R.p, ib.d_R.p, 4, hipMemcpyDeviceToHost, stream));
+        if (armed) HIP_OK(hipMemcpyAsync(ib.h_R.p + 1, ib.d_merr.p, 4, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         HIP_OK(hipEventElapsedTime(&ms, ib.iev0.e, ib.iev1.e));
+        if (ib.h_R.p[1]) {   // a group route without a member cannot happen under the engine lock
+            snprintf(last_error(), 512, "tm_batch_inboxes: %u of %u + %u deliveries without a member or out of place in the merge",
+                     ib.h_R.p[1], D0, DS);
+            return TM_EIO;
+        }
         nsub = ib.h_R.p[0];
         if (nsub == 0 || nsub > rcap) {
             snprintf(last_error(), 512, "inconsistent inboxes: %u subscribers for %u deliveries (capacity %u)", nsub, D, rcap);
@@ -520,29 +586,38 @@ int tm_engine::sync_subopts(Replica& R) {
     const size_t nn = nd.size();
     if (subopts_dirty || subopts_version != version || subopts_nn != nn || h_tstart.empty()) {
         h_tsub.clear();
-        h_tsub.reserve(topics_of.size());
+        h_tsub.reserve(topics_of.size() + shared_opts_of.size());
         for (const auto& kv : topics_of) h_tsub.push_back(kv.first);
+        for (const auto& kv : shared_opts_of)
+            if (!topics_of.count(kv.first)) h_tsub.push_back(kv.first);
         std::sort(h_tsub.begin(), h_tsub.end());
         h_tstart.assign(h_tsub.size() + 1, 0);
         h_tnode.clear();
         h_tval.clear();
-        h_tnode.reserve(sub_entries);
-        h_tval.reserve(sub_entries);
+        h_tnode.reserve(sub_entries + shared_opts_of.size());
+        h_tval.reserve(sub_entries + shared_opts_of.size());
         std::vector<std::pair<uint32_t, uint32_t>> row;
+        static const std::vector<std::string> no_topics;
+        static const std::vector<tm_subopts> no_opts;
         for (size_t s = 0; s < h_tsub.size(); ++s) {
-            const auto& ts = topics_of[h_tsub[s]];
-            const auto& os = opts_of[h_tsub[s]];
+            const auto tit = topics_of.find(h_tsub[s]);
+            const auto oit = opts_of.find(h_tsub[s]);
+            const auto& ts = tit == topics_of.end() ? no_topics : tit->second;
+            const auto& os = oit == opts_of.end() ? no_opts : oit->second;
             if (os.size() != ts.size()) {
                 snprintf(last_error(), 512, "subscriber %u: %zu topics, %zu option entries", h_tsub[s], ts.size(), os.size());
                 return TM_EIO;
             }
             row.clear();
-            for (size_t i = 0; i < ts.size(); ++i) {
-                const uint32_t n = node_of((const uint8_t*)ts[i].data(), ts[i].size());
-                if (n == NONE || n >= nn) continue;   // not in the trie: no route, no dispatch (sync_subs)
-                const tm_subopts& o = os[i];
+            auto add = [&](const std::string& t, const tm_subopts& o) {
+                const uint32_t n = node_of((const uint8_t*)t.data(), t.size());
+                if (n == NONE || n >= nn) return;   // not in the trie: no route, no dispatch (sync_subs)
                 row.emplace_back(n, o.subid << SO_SUBID_SHIFT | (o.rap ? SO_RAP : 0u) | (o.nl ? SO_NL : 0u) | (o.qos & SO_QOS));
-            }
+            };
+            for (size_t i = 0; i < ts.size(); ++i) add(ts[i], os[i]);
+            const auto shi = shared_opts_of.find(h_tsub[s]);
+            if (shi != shared_opts_of.end())
+                for (const auto& e : shi->second) add(e.topic, e.o);
             std::sort(row.begin(), row.end());
             h_tstart[s] = (uint32_t)h_tnode.size();
             for (const auto& e : row) {
@@ -632,7 +707,8 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
     if ((rc = dv.dev0.create())) return rc;
     if ((rc = dv.dev1.create())) return rc;
     DeliverArgs a{};
-    a.keys = ibx.passes & 1 ? ib.d_key1.p : b->fan.d_fout.p;   // where the sort left the pairs
+    a.keys = ibx.passes & 1 ? ib.d_key1.p : ib.key0;   // where the sort left the pairs
+    a.groups = ib.merged ? ib.d_grp.p : nullptr;
     a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
     a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
     a.D = D; a.R = nsub; a.n = n; a.ntiles = ntiles;
@@ -665,6 +741,10 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
         if ((rc = dv.d_off.reserve((size_t)nsub + 1))) return rc;
         if ((rc = dv.d_pub.reserve(dd))) return rc;
         if ((rc = dv.d_fid.reserve(dd))) return rc;
+        if (ib.merged) {
+            if ((rc = dv.d_grp.reserve(dd))) return rc;
+            a.o_grp = dv.d_grp.p;
+        }
         a.own = dv.d_own.p; a.emsg = dv.d_emsg.p; a.esubid = want_subids ? dv.d_esubid.p : nullptr;
         a.kcount = dv.d_kcount.p; a.kbs = dv.d_kbs.p; a.ncount = dv.d_ncount.p; a.nbs = dv.d_nbs.p;
         a.o_sub = dv.d_sub.p; a.o_off = dv.d_off.p; a.o_pub = dv.d_pub.p; a.o_fid = dv.d_fid.p;
@@ -697,6 +777,11 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
     out->n_subscribers = rleft;
     out->n_deliveries = left;
     out->n_dropped_no_local = D - left;
+    if (ib.merged && can_drop) {   // tm_batch_inbox_groups: compacted alike
+        ib.d_groups = dv.d_grp.p;
+        ib.n_groups = left;
+        ib.grp_host = false;
+    }
     if (device) {
         out->subscribers = can_drop ? dv.d_sub.p : ib.d_sub.p;
         out->inbox_offsets = can_drop ? dv.d_off.p : ib.d_off.p;

@@ -360,6 +360,7 @@ struct SharedArgs {
     uint32_t* out_grp;
     uint32_t* out_sub;
     uint64_t cap;             // capacity of the three
+    uint32_t* out_ent;        // armed inboxes (tm_batch_shared_mode): match entry of delivery i, else null
 };
 
 // Per-subscriber inboxes (tm_batch_inboxes): the batch's deliveries, which the
@@ -399,6 +400,41 @@ struct InboxArgs {
     uint32_t* filter_ids;     // D
     uint32_t* subscribers;    // rcap
     uint32_t* inbox_offsets;  // rcap + 1
+    // armed batch (tm_batch_shared_mode): the sort runs over the merged list L',
+    // D = ordinary + shared deliveries; the payload of a pair is its position
+    // in L' and the finish reads one 16-B record from there
+    const uint4* mrec;        // D: {publish, filter id, group | NONE, match entry} of merged position v, or
+                              // null (payload = entry)
+    uint32_t* groups;         // D: group of every delivery of the result
+};
+
+// L' of an armed batch (tm_batch_shared_mode): ordinary delivery d of entry j
+// lands at d + (picks of the entries before j), pick s of entry j behind the
+// ordinary run of j, at moff[j + 1] + s.  One thread per delivery of either
+// kind; key / val are the sort's first input, rec[pos] = {publish, filter id,
+// group | NONE, entry} is what the finish reads back through the payload (one
+// 16-B load per delivery instead of a chain of gathers).  err counts picks
+// without a member and positions past cap.
+struct MergeArgs {
+    const uint32_t* fsub;     // nd: the fan-out's subscribers
+    const uint32_t* fent;     // nd: their match entries
+    uint32_t nd;              // ordinary deliveries
+    const uint32_t* gsub;     // ns: the picks' subscribers, groups, entries
+    const uint32_t* ggrp;
+    const uint32_t* gent;
+    uint32_t ns;              // shared deliveries
+    uint32_t m;               // match entries
+    const uint64_t* moff;     // m + 1: first ordinary delivery of entry j (global)
+    const uint32_t* eoff;     // m + 1: picks before entry j (block-local + bsums)
+    const uint32_t* bsums;
+    const uint32_t* pub_of;   // m: publish of entry j (tm_inbox_pubof ran before)
+    const uint32_t* ids;      // m: filter id of entry j
+    uint32_t cap;             // nd + ns
+    uint32_t pad0;
+    uint32_t* key;            // cap
+    uint32_t* val;
+    uint4* rec;
+    uint32_t* err;
 };
 
 // What the session sends (tm_batch_deliver): the inboxes above after
@@ -451,6 +487,10 @@ struct DeliverArgs {
     uint32_t* o_fid;               // D
     uint8_t* o_msg;                // D
     uint32_t* o_subid;             // D, or null
+    // armed batch (tm_batch_shared_mode): the group of every delivery, NONE for
+    // an ordinary one; a shared delivery without options passes through
+    const uint32_t* groups;        // D, or null
+    uint32_t* o_grp;               // D: groups after the compaction (with groups)
 };
 
 // The session's send window (tm_batch_window) over the arrays tm_batch_deliver
@@ -573,6 +613,7 @@ hipError_t launch_fan_fill(const FanArgs& a, hipStream_t s);   // a.out_j set: a
 hipError_t launch_inbox_pubof(const InboxArgs& a, hipStream_t s);
 hipError_t launch_inbox_sort(const InboxArgs& a, hipStream_t s);
 hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s);
+hipError_t launch_inbox_merge(const MergeArgs& a, hipStream_t s);   // armed batch: L' from the fan-out and the picks
 // deliver: the options of every delivery and its enriched byte (drop: also
 // own / first); then, when something can drop, count + scans + the stable
 // compaction into o_*

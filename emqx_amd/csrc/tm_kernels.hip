@@ -1658,6 +1658,7 @@ __global__ __launch_bounds__(256) void tm_shared_pick(SharedArgs a) {
         a.out_fid[o] = f;
         a.out_grp[o] = run.x;
         a.out_sub[o] = (cnt && mi < a.nmem) ? a.mem[mi] : NONE;
+        if (a.out_ent) a.out_ent[o] = i;
     }
 }
 // A new build of the tables reached the replica: upd[s] = {member count, owner
@@ -2162,6 +2163,41 @@ __global__ __launch_bounds__(256) void tm_inbox_pubof(InboxArgs a) {
     a.pub_of[j] = lo;
 }
 
+// The merged list L' of an armed batch (tm_batch_shared_mode): within a match
+// entry the {To, node()} route precedes every {To, Group} route
+// (src/emqx_broker.erl:255-261), so entry j holds its ordinary run and then
+// its picks.  Delivery-parallel, whatever the skew of the entries: thread t <
+// nd moves ordinary delivery t of entry j = fent[t] up by the picks of the
+// entries before j; thread nd + s puts pick s (of entry gent[s]) behind the
+// ordinary run of its entry, i.e. at moff[j + 1] + s.  Reads are coalesced,
+// writes are runs.  Every position of [0, cap) is written once when the
+// inputs are consistent; anything else is counted in err and written nowhere.
+__global__ __launch_bounds__(256) void tm_inbox_merge(MergeArgs a) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (uint64_t)a.nd + a.ns) return;
+    uint32_t S, j, g;
+    uint64_t pos;
+    if (t < a.nd) {
+        S = a.fsub[t];
+        j = a.fent[t];
+        g = NONE;
+        if (j >= a.m) { atomicAdd(a.err, 1u); return; }
+        pos = t + a.eoff[j] + a.bsums[j / SCAN_TILE];
+    } else {
+        const uint32_t s = (uint32_t)(t - a.nd);
+        S = a.gsub[s];
+        j = a.gent[s];
+        g = a.ggrp[s];
+        // a group route without a member cannot happen under the engine lock
+        if (S == NONE || j >= a.m) { atomicAdd(a.err, 1u); return; }
+        pos = a.moff[j + 1] + s;
+    }
+    if (pos >= a.cap) { atomicAdd(a.err, 1u); return; }
+    a.key[pos] = S;
+    a.val[pos] = (uint32_t)pos;
+    a.rec[pos] = make_uint4(a.pub_of[j], a.ids[j], g, j);
+}
+
 // hist[d * ntiles + tile] = pairs of the tile whose digit (key >> shift) & 255 is d
 __global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_hist(InboxArgs a, const uint32_t* keys, uint32_t* hist,
                                                              uint32_t shift) {
@@ -2267,7 +2303,10 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_scatter(InboxArgs a, con
 }
 
 // The sorted pairs -> (publish, filter) of every delivery, and the inbox heads
-// (the first delivery of every subscriber) of the tile counted.
+// (the first delivery of every subscriber) of the tile counted.  MERGED (an
+// armed batch): the payload is a position of L'; publish, filter and group are
+// that position's record.
+template <bool MERGED>
 __global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_finish(InboxArgs a, const uint32_t* keys, const uint32_t* vals) {
     __shared__ uint32_t hw[INBOX_BLOCK / 64];
     const uint32_t t = threadIdx.x;
@@ -2282,11 +2321,28 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_inbox_finish(InboxArgs a, cons
         kp[k] = (q < a.D && q) ? keys[q - 1] : ~ky[k];
     }
     uint32_t p[INBOX_TILE / INBOX_BLOCK], f[INBOX_TILE / INBOX_BLOCK];
+    if constexpr (MERGED) {
+        uint4 rc[INBOX_TILE / INBOX_BLOCK];
 #pragma unroll
-    for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
-        const bool ok = j[k] < a.m;
-        p[k] = ok ? a.pub_of[j[k]] : NONE;
-        f[k] = ok ? a.ids[j[k]] : NONE;
+        for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+            const uint64_t q = tbase + k * INBOX_BLOCK + t;
+            const uint32_t v = j[k];
+            rc[k] = (q < a.D && v < a.D) ? a.mrec[v] : make_uint4(NONE, NONE, NONE, NONE);
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+            const uint64_t q = tbase + k * INBOX_BLOCK + t;
+            p[k] = rc[k].x;
+            f[k] = rc[k].y;
+            if (q < a.D) a.groups[q] = rc[k].z;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
+            const bool ok = j[k] < a.m;
+            p[k] = ok ? a.pub_of[j[k]] : NONE;
+            f[k] = ok ? a.ids[j[k]] : NONE;
+        }
     }
 #pragma unroll
     for (uint32_t k = 0; k < INBOX_TILE / INBOX_BLOCK; ++k) {
@@ -2396,14 +2452,18 @@ __global__ __launch_bounds__(256) void tm_deliver_range(DeliverArgs a) {
     if (lo < a.NS && a.tsub[lo] == S) {
         g.y = min(a.tstart[lo + 1], a.T);
         g.x = min(a.tstart[lo], g.y);
-    } else {
+    } else if (!a.groups) {
         atomicAdd(a.err, 1u);   // a subscriber of the fan-out without options: TM_EIO
-    }
+    }   // armed batch: a member without options is legal; tm_deliver_flags decides per delivery
     a.rng[r] = g;
     a.first[r] = NONE;
 }
 
-template <bool DROP>
+// GRP (an armed batch): a shared delivery whose (subscriber, filter) has no
+// options passes through -- get_subopts/2 gives [] and enrich_subopts([], Msg, _)
+// leaves the message alone (src/emqx_session.erl:500-509): the publish's QoS
+// and retain flag, no TM_MSG_NL, subid 0, never own.
+template <bool DROP, bool GRP>
 __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_flags(DeliverArgs a) {
     __shared__ uint32_t hw[INBOX_BLOCK / 64];
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -2422,6 +2482,7 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_flags(DeliverArgs a) {
         const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
         hb += (uint32_t)__popcll(hm);
         bool ok = on && ri < a.R;
+        bool pass = false;
         uint32_t v = 0, p = NONE;
         if (ok) {
             p = a.publishes[q];
@@ -2433,14 +2494,16 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_flags(DeliverArgs a) {
                 const uint32_t mid = lo + (hi - lo) / 2;
                 if (a.tnode[mid] < f) lo = mid + 1; else hi = mid;
             }
-            if (lo < end && a.tnode[lo] == f) v = a.tval[lo]; else ok = false;
+            if (lo < end && a.tnode[lo] == f) v = a.tval[lo];
+            else if (GRP && a.groups[q] != NONE) pass = true;
+            else ok = false;
             if (p >= a.n) ok = false;
         }
         if (on && !ok) ++bad;
         const uint32_t pm = (ok && a.msg) ? a.msg[p] : 0u;
         const uint32_t sq = v & SO_QOS, pq = pm & MSG_QOS;
-        const uint32_t qos = upgrade ? max(sq, pq) : min(sq, pq);
-        const bool retain = (pm & MSG_RETAIN) && ((v & SO_RAP) || (pm & MSG_RETAINED));
+        const uint32_t qos = pass ? pq : upgrade ? max(sq, pq) : min(sq, pq);
+        const bool retain = (pm & MSG_RETAIN) && (pass || (v & SO_RAP) || (pm & MSG_RETAINED));
         if (on) {
             a.emsg[q] = (uint8_t)(qos | (retain ? MSG_RETAIN : 0u) | ((v & SO_NL) ? MSG_NL : 0u));
             if (a.esubid) a.esubid[q] = v >> SO_SUBID_SHIFT;
@@ -2500,6 +2563,7 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_count(DeliverArgs a) {
 }
 static_assert(INBOX_BLOCK / 64 == 4, "four waves per tile");
 
+template <bool GRP>
 __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_scatter(DeliverArgs a) {
     __shared__ uint32_t kw[INBOX_BLOCK / 64], nw[INBOX_BLOCK / 64];
     const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -2531,6 +2595,7 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_deliver_scatter(DeliverArgs a)
                 a.o_fid[pos] = a.filter_ids[q];
                 a.o_msg[pos] = a.emsg[q];
                 if (a.o_subid) a.o_subid[pos] = a.esubid[q];
+                if (GRP) a.o_grp[pos] = a.groups[q];
                 if (fl & DLV_HEAD) {
                     const uint32_t i = nb + inbox_mbcnt(hm);
                     if (i < a.R) {
@@ -4406,11 +4471,18 @@ hipError_t launch_inbox_sort(const InboxArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+hipError_t launch_inbox_merge(const MergeArgs& a, hipStream_t s) {
+    const uint64_t tot = (uint64_t)a.nd + a.ns;
+    if (tot) hipLaunchKernelGGL(tm_inbox_merge, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s) {
     if (!a.D || !a.ntiles) return hipGetLastError();
     const uint32_t* keys = a.passes & 1 ? a.key1 : a.key0;
     const uint32_t* vals = a.passes & 1 ? a.val1 : a.val0;
-    hipLaunchKernelGGL(tm_inbox_finish, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys, vals);
+    if (a.mrec) hipLaunchKernelGGL(tm_inbox_finish<true>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys, vals);
+    else hipLaunchKernelGGL(tm_inbox_finish<false>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a, keys, vals);
     ScanArgs sa{};
     sa.count = a.hcount; sa.row_off = a.hcount; sa.block_sums = a.hcbs; sa.n = a.ntiles;   // in place
     const hipError_t e = launch_scan(sa, s, a.d_R);
@@ -4422,10 +4494,15 @@ hipError_t launch_inbox_finish(const InboxArgs& a, hipStream_t s) {
 hipError_t launch_deliver_flags(const DeliverArgs& a, bool drop, hipStream_t s) {
     if (!a.D || !a.R || !a.ntiles) return hipGetLastError();
     hipLaunchKernelGGL(tm_deliver_range, dim3((a.R + 255) / 256), dim3(256), 0, s, a);
-    if (drop)
-        hipLaunchKernelGGL(tm_deliver_flags<true>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    if (a.groups) {
+        if (drop)
+            hipLaunchKernelGGL((tm_deliver_flags<true, true>), dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+        else
+            hipLaunchKernelGGL((tm_deliver_flags<false, true>), dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    } else if (drop)
+        hipLaunchKernelGGL((tm_deliver_flags<true, false>), dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
     else
-        hipLaunchKernelGGL(tm_deliver_flags<false>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+        hipLaunchKernelGGL((tm_deliver_flags<false, false>), dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 
@@ -4438,7 +4515,8 @@ hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s) {
     hipError_t e = launch_scan(sk, s, a.d_tot);
     if (e != hipSuccess) return e;
     if ((e = launch_scan(sn, s, a.d_tot + 1)) != hipSuccess) return e;
-    hipLaunchKernelGGL(tm_deliver_scatter, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    if (a.groups) hipLaunchKernelGGL(tm_deliver_scatter<true>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    else hipLaunchKernelGGL(tm_deliver_scatter<false>, dim3(a.ntiles), dim3(INBOX_BLOCK), 0, s, a);
     return hipGetLastError();
 }
 

@@ -44,8 +44,52 @@ int tm_engine::shared_subscribe(const uint8_t* t, size_t len, uint32_t group, ui
     run->members.push_back(sub);
     shared_topics_of[sub].emplace_back(std::move(k), group);
     ++shared_entries;
+    max_sub = std::max(max_sub, sub);   // a member's deliveries are sorted with the others (armed inboxes)
     shared_dirty = true;
     return TM_OK;
+}
+
+int tm_engine::shared_subscribe_opts(const uint8_t* t, size_t len, uint32_t group, uint32_t sub, const tm_subopts& o) {
+    tm_subopts* cur;
+    const int frc = find_subopts(t, len, sub, &cur);
+    if (frc == TM_OK) {
+        // {SubPid, Topic} has options already, of either kind: the `true -> %% Existed`
+        // branch (src/emqx_broker.erl:129-135) -- only the options merge
+        const uint32_t mask = TM_SUBOPT_QOS | TM_SUBOPT_NL | TM_SUBOPT_RAP | TM_SUBOPT_RH | (o.subid ? TM_SUBOPT_SUBID : 0u);
+        return set_subopts(t, len, sub, mask, o);
+    }
+    if (frc != TM_ENOENT) return frc;
+    // the options first, taken back if the subscribe fails or throws
+    shared_opts_of[sub].push_back(SharedOpt{std::string((const char*)t, len), group, o});
+    int rc;
+    try {
+        rc = shared_subscribe(t, len, group, sub);
+    } catch (...) {
+        rc = TM_ENOMEM;
+    }
+    if (rc) {
+        auto it = shared_opts_of.find(sub);
+        it->second.pop_back();
+        if (it->second.empty()) shared_opts_of.erase(it);
+        return rc;
+    }
+    nl_entries += o.nl;
+    subopts_dirty = true;
+    return TM_OK;
+}
+
+void tm_engine::shared_opts_erase(const std::string& k, uint32_t group, uint32_t sub) {
+    auto it = shared_opts_of.find(sub);
+    if (it == shared_opts_of.end()) return;
+    auto& v = it->second;
+    for (auto e = v.begin(); e != v.end(); ++e)
+        if (e->group == group && e->topic == k) {
+            nl_entries -= e->o.nl;
+            v.erase(e);
+            subopts_dirty = true;
+            break;
+        }
+    if (v.empty()) shared_opts_of.erase(it);
 }
 
 int tm_engine::shared_unsubscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub) {
@@ -62,6 +106,7 @@ int tm_engine::shared_unsubscribe(const uint8_t* t, size_t len, uint32_t group, 
     mem.erase(mi);
     --shared_entries;
     shared_dirty = true;
+    shared_opts_erase(k, group, sub);   // ets:delete(?SUBOPTION, {SubPid, Topic}) (src/emqx_broker.erl:179-183)
     auto ti = shared_topics_of.find(sub);
     if (ti != shared_topics_of.end()) {
         auto& ts = ti->second;
@@ -170,7 +215,7 @@ int tm_engine::sync_shared(Replica& R) {
     return TM_OK;
 }
 
-int tm_engine::batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_shared_deliveries* out) {
+int tm_engine::batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_shared_deliveries* out, bool entries) {
     if (!b->done) return einval("tm_batch_dispatch_shared: the batch has not been waited for");
     if (b->dedup) return einval("tm_batch_dispatch_shared: a TM_BATCH_DEDUP batch (the pick is per publish)");
     const bool counts_only = o->flags & TM_SHARED_COUNT_ONLY;
@@ -225,6 +270,12 @@ int tm_engine::batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_sh
             a.keys = b->sh.d_gkeys.p;
         }
         a.out_fid = b->sh.d_gfid.p; a.out_grp = b->sh.d_ggrp.p; a.out_sub = b->sh.d_gsub.p; a.cap = total;
+        if (entries) {
+            if ((rc = b->sh.d_gent.reserve(std::max<uint64_t>(total, 1)))) return rc;
+            a.out_ent = b->sh.d_gent.p;
+            // a slot the pick leaves unwritten reads as a pick without a member: the merge counts it
+            if (total) HIP_OK(hipMemsetAsync(b->sh.d_gsub.p, 0xFF, total * 4, stream));
+        }
         HIP_OK(hipEventRecord(b->sh.gev[2].e, stream));
         if (total) HIP_OK(launch_shared_pick(a, stream));
         HIP_OK(hipEventRecord(b->sh.gev[3].e, stream));
@@ -302,6 +353,76 @@ int tm_shared_members(tm_engine* e, const uint8_t* topic, size_t len, uint32_t g
     std::lock_guard<std::recursive_mutex> g(e->mu);
     try {
         return e->shared_members(topic, len, group_dest, buf, cap, n);
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+int tm_engine::batch_inbox_groups(tm_batch* b, uint32_t flags, const uint32_t** groups) {
+    tm_batch::Inbox& ib = b->inbox;
+    if (!b->shmode.armed || !ib.merged)
+        return einval("tm_batch_inbox_groups: the batch is not armed, or no inboxes / deliver / window call ran armed");
+    if (flags & TM_INBOX_DEVICE) {
+        *groups = ib.d_groups;
+        return TM_OK;
+    }
+    if (!ib.grp_host) {
+        const hipStream_t stream = b->rep->stream;
+        int rc;
+        if ((rc = ib.h_grp.reserve(std::max<size_t>(ib.n_groups, 1)))) return rc;
+        if (ib.n_groups)
+            HIP_OK(hipMemcpyAsync(ib.h_grp.p, ib.d_groups, (size_t)ib.n_groups * 4, hipMemcpyDeviceToHost, stream));
+        HIP_OK(hipStreamSynchronize(stream));
+        ib.grp_host = true;
+    }
+    *groups = ib.h_grp.p;
+    return TM_OK;
+}
+
+int tm_batch_shared_mode(tm_engine* e, tm_batch* b, const tm_shared_opts* opts) {
+    if (!e) return TM_EINVAL;
+    // the options are checked first, so a host-only engine reports them too
+    if (opts) {
+        if (opts->strategy > TM_SHARED_HASH) return einval("tm_batch_shared_mode: unknown strategy");
+        if (opts->flags & ~(TM_SHARED_COUNT_ONLY | TM_SHARED_DEVICE)) return einval("tm_batch_shared_mode: unknown flag");
+        if (opts->flags)
+            return einval("tm_batch_shared_mode: TM_SHARED_COUNT_ONLY / TM_SHARED_DEVICE have no meaning here");
+        if (opts->strategy == TM_SHARED_HASH && !opts->keys) return einval("tm_batch_shared_mode: TM_SHARED_HASH without keys");
+    }
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    if (!opts) {   // disarm: the batch behaves as before
+        b->shmode.armed = false;
+        b->shmode.keys.clear();
+        return TM_OK;
+    }
+    if (b->dedup) return einval("tm_batch_shared_mode: a TM_BATCH_DEDUP batch (the pick is per publish)");
+    try {
+        if (opts->strategy == TM_SHARED_HASH) b->shmode.keys.assign(opts->keys, opts->keys + b->n);
+        else b->shmode.keys.clear();
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+    b->shmode.strategy = opts->strategy;
+    b->shmode.seed = opts->seed;
+    b->shmode.armed = true;
+    return TM_OK;
+}
+
+int tm_batch_inbox_groups(tm_engine* e, tm_batch* b, uint32_t flags, const uint32_t** groups) {
+    if (!e) return TM_EINVAL;
+    if (!groups) return einval("tm_batch_inbox_groups: groups is NULL");
+    if (flags & ~TM_INBOX_DEVICE) return einval("tm_batch_inbox_groups: unknown flag");
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    int rc = e->use(b->rep);
+    if (rc) return rc;
+    try {
+        return e->batch_inbox_groups(b, flags, groups);
     } catch (...) {
         return TM_ENOMEM;
     }

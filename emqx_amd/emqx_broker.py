@@ -9,7 +9,9 @@ the whole publish path of a batch on the device: match (emqx_router:
 match_routes/1) then fan-out (dispatch/2 for every local route,
 tm_batch_dispatch).  The other local clause of do_route/2, {To, Group}
 (:245-248), is emqx_shared_sub.dispatch_batch (tm_batch_dispatch_shared);
-shared and non-shared subscribers share the pid -> u32 id map below.
+shared and non-shared subscribers share the pid -> u32 id map below, and
+deliver_batch(shared=...) returns both kinds in one mailbox per pid
+(tm_batch_shared_mode; mailboxes_shared is its host restatement).
 
 Subscriber pids are arbitrary hashable terms here, mapped to u32 ids.
 """
@@ -170,15 +172,45 @@ def mailboxes(rows):
     return boxes
 
 
-def deliver_batch(topic_list):
+def mailboxes_shared(rows, shared_rows):
+    """mailboxes() with the shared deliveries in them: route/2 folds over
+    aggre(match_routes(Topic)) (:209, 238-248), and within one filter To the
+    {To, node()} route precedes every {To, Group} route (lists:usort orders an
+    atom before a tuple, :255-261).  rows[i] = publish i's ordinary deliveries
+    [(To, pid)] (publish_batch), shared_rows[i] = its picked shared deliveries
+    [(To, Group, pid)] (emqx_shared_sub.dispatch_batch / _mirror), both with To
+    in Erlang binary order; merged filter by filter -> {pid: [(i, To, Group |
+    None)]} in arrival order.  With no shared row anywhere this is mailboxes()
+    with None appended to every entry.  Pure host code."""
+    boxes = {}
+    for i, (row, srow) in enumerate(zip(rows, shared_rows)):
+        for to in sorted({to for to, _ in row} | {to for to, _, _ in srow}):
+            for t, pid in row:
+                if t == to:
+                    boxes.setdefault(pid, []).append((i, to, None))
+            for t, group, pid in srow:
+                if t == to:
+                    boxes.setdefault(pid, []).append((i, to, group))
+    return boxes
+
+
+def deliver_batch(topic_list, shared=None):
     """publish_batch regrouped by subscriber on the device (tm_batch_inboxes):
     {pid: [(publish index, To)]}, every pid's list in mailbox order; equals
-    mailboxes(publish_batch(topic_list))."""
+    mailboxes(publish_batch(topic_list)).
+    shared = {"strategy": ..., "keys": ..., "seed": ...} arms the batch
+    (tm_batch_shared_mode): the result is {pid: [(publish index, To, Group |
+    None)]} and equals mailboxes_shared(publish_batch(topic_list),
+    emqx_shared_sub.dispatch_batch_mirror(topic_list, strategy, keys, seed))
+    for the hash and random strategies."""
     eng = R.engine()
     b = eng.prepare(topic_list)
     b.launch()
     b.wait()
+    if shared is not None:
+        b.shared_mode(shared["strategy"], keys=shared.get("keys"), seed=shared.get("seed", 0))
     subs, offs, pubs, fids = b.inboxes()
+    groups = b.inbox_groups() if shared is not None else None
     b.free()
     cache = {}
     out = {}
@@ -189,6 +221,10 @@ def deliver_batch(topic_list):
             f = cache.get(fid)
             if f is None:
                 f = cache[fid] = eng.filter_bytes(fid)
-            box.append((int(pubs[q]), f))
+            if groups is None:
+                box.append((int(pubs[q]), f))
+            else:
+                g = int(groups[q])
+                box.append((int(pubs[q]), f, None if g == 0xFFFFFFFF else R._agg_of[g][1]))
         out[_terms[int(s)]] = box
     return out

@@ -14,7 +14,10 @@ and deletes the group's route itself, this module only books it in the host
 route table), and `dispatch_batch` runs do_route({To, Group}, _)
 (src/emqx_broker.erl:245-248) for a batch on the device: one member per
 (publish, matched filter, group), picked by the random / round_robin / hash
-strategy (tm_batch_dispatch_shared).
+strategy (tm_batch_dispatch_shared).  subscribe(..., subopts=...) stores the
+member's subscription options too (tm_shared_subscribe_opts), and
+emqx_broker.deliver_batch(shared=...) puts the picked deliveries into the
+members' mailboxes (tm_batch_shared_mode).
 
 pick/5, do_pick/5, pick_subscriber/5 and do_pick_subscriber/5 below restate
 :229-275 clause by clause on the CPU; `dispatch_batch_mirror` is the batch
@@ -50,18 +53,33 @@ def clear():
     _rr.clear()
 
 
-def subscribe(group, topic: bytes, subpid, node=R.NODE):
-    """handle_call({subscribe, Group, Topic, SubPid}) (:297-305)."""
+def subscribe(group, topic: bytes, subpid, node=R.NODE, subopts=None):
+    """handle_call({subscribe, Group, Topic, SubPid}) (:297-305).
+    subopts ({qos, nl, rap, rh, subid}): emqx_broker:subscribe/3 with share =>
+    Group (src/emqx_broker.erl:127-136) in front of it -- the options are
+    stored under {SubPid, Topic} (tm_shared_subscribe_opts); when that key has
+    options already, shared or not, only they merge (the `Existed` branch,
+    :129-135) and the membership does not change."""
     topic = bytes(topic)
     key = (group, topic)
     dest = (group, node)
     gid, sid = R._agg_id(dest), B._sid(subpid)
     ms = _members.get(key)
     eng = R.engine()
+    if subopts is not None and eng.get_subopts(topic, sid) is not None:
+        eng.shared_subscribe_opts(topic, gid, sid, dict(subopts))   # Existed: merges, nothing else
+        return "ok"
+
+    def join():
+        if subopts is None:
+            eng.shared_subscribe(topic, gid, sid)
+        else:
+            eng.shared_subscribe_opts(topic, gid, sid, dict(subopts))
+
     if ms is None:                                    # not ets:member(?SHARED_SUBS, {Group, Topic})
         dests = R._routes.setdefault(topic, [])
         had = dest in dests                           # lists:member(Route, lookup_routes(Topic))
-        eng.shared_subscribe(topic, gid, sid)         # adds the route (topic, Group) with the first member
+        join()                                        # adds the route (topic, Group) with the first member
         if had:
             eng.route_delete(topic, gid)              # the table already held this route: one reference, not two
         else:
@@ -69,7 +87,7 @@ def subscribe(group, topic: bytes, subpid, node=R.NODE):
         ms = _members[key] = []
         _groups_of.setdefault(topic, []).append(group)
     else:
-        eng.shared_subscribe(topic, gid, sid)
+        join()
     if subpid not in ms:                              # a bag stores an identical object once
         ms.append(subpid)
         _of_pid.setdefault(subpid, []).append(key)

@@ -187,6 +187,33 @@ class Batch:
         return (int(d.n_deliveries), float(d.kernel_ms), ptr(d.row_offsets), ptr(d.filter_ids), ptr(d.groups),
                 ptr(d.subscribers))
 
+    def shared_mode(self, strategy, keys=None, seed: int = 0):
+        """Arms the batch (tm_batch_shared_mode): inboxes() / deliver() /
+        window() then work on the merged list of ordinary and shared
+        deliveries; strategy / keys / seed as dispatch_shared (the keys are
+        copied).  shared_mode(None) disarms."""
+        if strategy is None:
+            N.check(self.eng.L.tm_batch_shared_mode(self.eng.h, self.h, None), "tm_batch_shared_mode")
+            return
+        o, _keep = self._shared_opts(strategy, keys, seed, 0)
+        N.check(self.eng.L.tm_batch_shared_mode(self.eng.h, self.h, C.byref(o)), "tm_batch_shared_mode")
+
+    def inbox_groups(self):
+        """tm_batch_inbox_groups: u32[D'] parallel to publishes / filter_ids
+        of the last inboxes() / deliver() / window() call on the armed batch:
+        the group id of a shared delivery, TM_NONE for an ordinary one."""
+        count = getattr(self, "_last_deliveries", 0)
+        p = C.POINTER(C.c_uint32)()
+        N.check(self.eng.L.tm_batch_inbox_groups(self.eng.h, self.h, 0, C.byref(p)), "tm_batch_inbox_groups")
+        return np.ctypeslib.as_array(p, shape=(count,)).copy() if count else np.zeros(0, np.uint32)
+
+    def inbox_groups_device(self) -> int:
+        """TM_INBOX_DEVICE: the device pointer of the groups."""
+        p = C.POINTER(C.c_uint32)()
+        N.check(self.eng.L.tm_batch_inbox_groups(self.eng.h, self.h, N.TM_INBOX_DEVICE, C.byref(p)),
+                "tm_batch_inbox_groups")
+        return C.cast(p, C.c_void_p).value
+
     def inboxes(self):
         """Per-subscriber inboxes (tm_batch_inboxes): the deliveries of
         dispatch() grouped by subscriber, each inbox in mailbox order ->
@@ -316,12 +343,14 @@ class Batch:
                 wo.sessions = C.cast(arr, C.POINTER(N.SessionState))
         w = N.SessionWindow()
         N.check(self.eng.L.tm_batch_window(self.eng.h, self.h, C.byref(o), C.byref(wo), C.byref(w)), "tm_batch_window")
+        self._last_deliveries = int(w.inboxes.n_deliveries)
         return w, keep
 
     def _deliver(self, from_, msg, flags: int):
         o, keep = self._deliver_opts(from_, msg, flags)
         d = N.SessionInboxes()
         N.check(self.eng.L.tm_batch_deliver(self.eng.h, self.h, C.byref(o), C.byref(d)), "tm_batch_deliver")
+        self._last_deliveries = int(d.n_deliveries)
         return d, keep
 
     def _deliver_opts(self, from_, msg, flags: int):
@@ -343,13 +372,15 @@ class Batch:
     def _inboxes(self, flags: int) -> "N.Inboxes":
         d = N.Inboxes()
         N.check(self.eng.L.tm_batch_inboxes(self.eng.h, self.h, flags, C.byref(d)), "tm_batch_inboxes")
+        self._last_deliveries = int(d.n_deliveries)
         return d
 
-    def _dispatch_shared(self, strategy, keys, seed: int, flags: int) -> "N.SharedDeliveries":
+    def _shared_opts(self, strategy, keys, seed: int, flags: int):
         o = N.SharedOpts()
         o.strategy = N.SHARED_STRATEGIES.get(strategy, strategy) if isinstance(strategy, str) else int(strategy)
         o.flags = flags
         o.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        keep = []
         if keys is not None:
             k = np.ascontiguousarray(np.asarray(keys, dtype=np.uint32))
             if len(k) != self.n:
@@ -357,6 +388,11 @@ class Batch:
             if not len(k):
                 k = np.zeros(1, np.uint32)
             o.keys = k.ctypes.data
+            keep.append(k)
+        return o, keep
+
+    def _dispatch_shared(self, strategy, keys, seed: int, flags: int) -> "N.SharedDeliveries":
+        o, _keep = self._shared_opts(strategy, keys, seed, flags)
         d = N.SharedDeliveries()
         N.check(self.eng.L.tm_batch_dispatch_shared(self.eng.h, self.h, C.byref(o), C.byref(d)),
                 "tm_batch_dispatch_shared")
@@ -922,6 +958,15 @@ class Engine:
     # ---- shared subscriptions (emqx_shared_sub subscribe/unsubscribe/cleanup_down) --
     def shared_subscribe(self, topic: bytes, group_dest: int, sub: int):
         N.check(self.L.tm_shared_subscribe(self.h, topic, len(topic), group_dest, sub), "tm_shared_subscribe")
+
+    def shared_subscribe_opts(self, topic: bytes, group_dest: int, sub: int, opts=None):
+        """subscribe/3 with share => Group (tm_shared_subscribe_opts): the
+        options go under (sub, topic), owned by the membership.  If (sub,
+        topic) has options already, of either kind, only they merge and no
+        membership changes."""
+        o = self._subopts(opts)
+        N.check(self.L.tm_shared_subscribe_opts(self.h, topic, len(topic), group_dest, sub,
+                                                C.byref(o) if opts is not None else None), "tm_shared_subscribe_opts")
 
     def shared_unsubscribe(self, topic: bytes, group_dest: int, sub: int) -> bool:
         rc = self.L.tm_shared_unsubscribe(self.h, topic, len(topic), group_dest, sub)

@@ -25,6 +25,7 @@
         , subscriber_down/3
         , dispatch_batch/2
         , deliver_batch/2
+        , deliver_batch/3
         , session_deliver_batch/3
         , session_window_batch/4
         , match_routes_batch/2
@@ -34,6 +35,8 @@
         , acl_check/4
         , check_acl/4
         , shared_subscribe/4
+        , shared_subscribe/5
+        , shared_flag/2
         , shared_unsubscribe/4
         , shared_member_down/2
         , shared_dispatch_batch/4
@@ -149,16 +152,42 @@ dispatch_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
       -> [{non_neg_integer(), [{non_neg_integer(), binary()}]}] | {error, term()}).
 deliver_batch(_Engine, _Topics) -> erlang:nif_error(nif_not_loaded).
 
+%% deliver_batch/2 with the shared deliveries in the inboxes (emqx_shared_sub:
+%% do_dispatch/4 ends in the same SubPid ! {deliver, Topic, Msg},
+%% src/emqx_shared_sub.erl:135-158, shared_dispatch_ack_enabled = false).
+%% Flags = [] | [shared_flag()]: with a strategy flag every {To, Group} route of
+%% a publish delivers to one picked member, behind the ordinary subscribers of
+%% To (src/emqx_broker.erl:255-261), as {PublishIndex0, {To, GroupDestId}}.
+-type(shared_flag() :: shared_round_robin | {shared_random, non_neg_integer()} | {shared_hash, [non_neg_integer()]}).
+-spec(deliver_batch(reference(), [binary()], [shared_flag()])
+      -> [{non_neg_integer(), [{non_neg_integer(), binary() | {binary(), non_neg_integer()}}]}] | {error, term()}).
+deliver_batch(_Engine, _Topics, _Flags) -> erlang:nif_error(nif_not_loaded).
+
+%% The strategy flag of deliver_batch/3, session_deliver_batch/3 and
+%% session_window_batch/4 for a batch published by Froms (#message.from of
+%% every publish, in order): the hash keys are erlang:phash2(From), the
+%% reference's own (src/emqx_shared_sub.erl:267-268), as in shared_dispatch/3;
+%% random is seeded from the caller's rand state.
+-spec(shared_flag(random | round_robin | hash, [term()]) -> shared_flag()).
+shared_flag(hash, Froms) -> {shared_hash, [erlang:phash2(From) || From <- Froms]};
+shared_flag(random, _Froms) -> {shared_random, rand:uniform(16#100000000) - 1};
+shared_flag(round_robin, _Froms) -> shared_round_robin.
+
 %% deliver_batch/2 after emqx_channel:ignore_local/3 (src/emqx_channel.erl:682-693)
 %% and emqx_session:enrich_subopts/3 (src/emqx_session.erl:500-529), on the
 %% device: what each session sends.  A publish is {FromSubId | none, QoS,
 %% Retain, Retained, Topic}; a delivery is {{PublishIndex0, Filter}, QoS,
 %% Retain, NL, SubIdent} (SubIdent 0 = none), the inboxes that lost every
 %% delivery left out.  Flags: upgrade_qos (#session.upgrade_qos = true for the
-%% whole call), nl_all (drop every own delivery, not only the leading run).
+%% whole call), nl_all (drop every own delivery, not only the leading run), and
+%% at most one shared_flag(): the shared deliveries are then in the inboxes
+%% (deliver_batch/3), their pair {PublishIndex0, {Filter, GroupDestId}}; the
+%% options are those of {SubId, Filter} (shared_subscribe/5), and a member
+%% without any gets the publish as it is.
 -type(publish() :: {non_neg_integer() | none, 0..2, boolean(), boolean(), binary()}).
--type(delivery() :: {{non_neg_integer(), binary()}, 0..2, boolean(), boolean(), non_neg_integer()}).
--spec(session_deliver_batch(reference(), [publish()], [upgrade_qos | nl_all])
+-type(delivery() :: {{non_neg_integer(), binary() | {binary(), non_neg_integer()}}, 0..2, boolean(), boolean(),
+                     non_neg_integer()}).
+-spec(session_deliver_batch(reference(), [publish()], [upgrade_qos | nl_all | shared_flag()])
       -> [{non_neg_integer(), [delivery()]}] | {error, term()}).
 session_deliver_batch(_Engine, _Publishes, _Flags) -> erlang:nif_error(nif_not_loaded).
 
@@ -176,7 +205,7 @@ session_deliver_batch(_Engine, _Publishes, _Flags) -> erlang:nif_error(nif_not_l
 -type(session() :: {non_neg_integer(), 1..65535, [disconnected | store_qos0 | host],
                     non_neg_integer() | unbounded, non_neg_integer(), non_neg_integer()}).
 -type(disp() :: send0 | send | queued | dropped_qos0 | dropped_queue_full | host).
--spec(session_window_batch(reference(), [publish()], {session(), [session()]}, [upgrade_qos | nl_all])
+-spec(session_window_batch(reference(), [publish()], {session(), [session()]}, [upgrade_qos | nl_all | shared_flag()])
       -> [{non_neg_integer(), {1..65535, non_neg_integer(), non_neg_integer()},
            [{disp(), 1..65535 | undefined, delivery()}]}] | {error, term()}).
 session_window_batch(_Engine, _Publishes, _Sessions, _Flags) -> erlang:nif_error(nif_not_loaded).
@@ -188,6 +217,14 @@ session_window_batch(_Engine, _Publishes, _Sessions, _Flags) -> erlang:nif_error
 %% route, the last one deletes it.
 -spec(shared_subscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
 shared_subscribe(_Engine, _Topic, _GroupDestId, _SubId) -> erlang:nif_error(nif_not_loaded).
+
+%% emqx_broker:subscribe/3 with share => Group (src/emqx_broker.erl:127-136,
+%% 145-163) in front of shared_subscribe/4: SubOpts go under {SubId, Topic}, the
+%% key of a non-shared subscription's too; a key that has options already only
+%% merges them and joins no group (the `Existed` branch, :129-135).
+%% shared_unsubscribe/4 and shared_member_down/2 delete what this call stored.
+-spec(shared_subscribe(reference(), binary(), non_neg_integer(), non_neg_integer(), subopts()) -> ok | {error, term()}).
+shared_subscribe(_Engine, _Topic, _GroupDestId, _SubId, _SubOpts) -> erlang:nif_error(nif_not_loaded).
 
 -spec(shared_unsubscribe(reference(), binary(), non_neg_integer(), non_neg_integer()) -> ok | {error, term()}).
 shared_unsubscribe(_Engine, _Topic, _GroupDestId, _SubId) -> erlang:nif_error(nif_not_loaded).

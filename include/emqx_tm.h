@@ -489,7 +489,8 @@ TM_API int  tm_batch_dispatch(tm_engine* e, tm_batch* b, uint32_t flags, tm_deli
  * TM_INBOX_DEVICE: no copy back, the four arrays are device memory of the
  * batch; otherwise batch-owned pinned memory, valid likewise.  passes = 8-bit
  * radix passes run: max(1, ceil(bits of the largest subscriber id ever given
- * to tm_subscribe / 8)); 0 when there was nothing to sort.
+ * to tm_subscribe, tm_shared_subscribe or their _opts forms / 8)); 0 when
+ * there was nothing to sort.
  * n_topics = 0 or no delivery: n_subscribers = 0, inbox_offsets = {0}, rc 0.
  * TM_EINVAL + tm_last_error(): out NULL, an unknown flag, a batch not waited,
  * a TM_BATCH_DEDUP batch (an inbox entry names a publish, and a deduplicated
@@ -609,7 +610,8 @@ TM_API int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* op
  * TM_SESS_HOST: every delivery of the inbox is TM_DISP_HOST; the record keeps
  * P and holds zeros otherwise.
  * Not here: priority tables (use TM_SESS_HOST), maybe_ack / maybe_nack of
- * shared deliveries (not in the inboxes), message expiry.
+ * shared deliveries (they enter the inboxes of an armed batch as plain
+ * delivers, tm_batch_shared_mode), message expiry.
  * The call counts as a dispatch of the batch (pointer lifetime as
  * tm_batch_deliver).  The session table is uploaded per call: a second call
  * on the same waited batch with other sessions sees them.  Without
@@ -689,6 +691,26 @@ TM_API int  tm_shared_member_down(tm_engine* e, uint32_t subscriber, uint64_t* n
  * writes up to cap ids, *n = full count (0 for an unknown group or topic). */
 TM_API int  tm_shared_members(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest,
                               uint32_t* buf, uint32_t cap, uint32_t* n);
+/* emqx_broker:subscribe/3 with share => Group (src/emqx_broker.erl:127-136,
+ * 145-163): ?SUBOPTION has one entry per {SubPid, Topic}, shared or not, Topic
+ * being the filter without its $share/Group/ prefix, so the options are stored
+ * under (subscriber, topic) -- the table tm_batch_deliver searches -- marked
+ * as owned by the membership in group_dest (the `share` key); then the call
+ * does what tm_shared_subscribe does.  opts = NULL: the defaults.
+ * If (subscriber, topic) already has options, stored by tm_subscribe(_opts) or
+ * by an earlier shared subscribe of any group, the reference takes its
+ * `true -> %% Existed` branch (:129-135): ONLY the options merge, as
+ * tm_subscribe_opts merges them, and no membership changes -- the subscriber
+ * does not join group_dest.  Likewise tm_subscribe(_opts) on a (subscriber,
+ * topic) whose options a shared subscribe stored only merges.
+ * tm_shared_unsubscribe and tm_shared_member_down delete the options that a
+ * shared subscribe of that group stored (do_unsubscribe/3, :179-183), never
+ * those of a non-shared subscription; tm_get_subopts / tm_set_subopts work on
+ * such an entry unchanged.  tm_shared_subscribe stores no options: a member
+ * without an entry is legal (see tm_batch_shared_mode).  TM_EINVAL as
+ * tm_subscribe_opts.  Works on a host-only engine. */
+TM_API int  tm_shared_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t group_dest,
+                                     uint32_t subscriber, const tm_subopts* opts);
 
 /* dispatch(Group, To, Delivery) (:110-125) for every {To, Group} route of every
  * publish of a waited batch (do_route/2, src/emqx_broker.erl:245-248): one
@@ -750,6 +772,52 @@ typedef struct {
 } tm_shared_deliveries;
 TM_API int  tm_batch_dispatch_shared(tm_engine* e, tm_batch* b, const tm_shared_opts* opts,
                                      tm_shared_deliveries* out);
+
+/* Shared deliveries in the inboxes.  emqx_shared_sub:do_dispatch/4
+ * (src/emqx_shared_sub.erl:135-158, shared_dispatch_ack_enabled = false) ends
+ * in the same SubPid ! {deliver, Topic, Msg} as emqx_broker:dispatch/3, so a
+ * member's mailbox holds both kinds in one list, and ignore_local/3,
+ * enrich_subopts/3, next_pkt_id and the inflight window run over that list.
+ * tm_batch_shared_mode arms a prepared batch (opts = NULL disarms it; an
+ * unarmed batch behaves bit for bit as before).  While armed,
+ * tm_batch_inboxes, tm_batch_deliver and tm_batch_window on the batch work on
+ * the merged list L' instead of L: publishes in order; within a publish its
+ * match entries in match order; within a match entry first the subscribers of
+ * tm_batch_dispatch in subscription order (the {To, node()} route:
+ * lists:usort orders an atom before a tuple, src/emqx_broker.erl:255-261),
+ * then one picked member per group of tm_batch_dispatch_shared, in its order.
+ * The inbox of S is the subsequence of L' addressed to S.  n_deliveries is
+ * D + D_shared; TM_EOVERFLOW above 2^32 - 16 for the sum.  With no group
+ * anywhere L' is L.
+ * opts: strategy and seed as tm_batch_dispatch_shared; keys (TM_SHARED_HASH,
+ * n_topics host words) are COPIED at the call, so arm again after a
+ * re-prepare with another publish count (the calls return TM_EINVAL until
+ * then).  Each of the three calls runs the pick itself, as it runs the
+ * fan-out itself: with TM_SHARED_ROUND_ROBIN every call takes fresh cursor
+ * values, exactly as every tm_batch_dispatch_shared does (deliver + window on
+ * one batch are two picks; tm_batch_window alone is one), and which publish
+ * gets which cursor value is unordered.  An armed call also counts as a
+ * tm_batch_dispatch_shared of the batch for that call's pointer lifetime.
+ * Options: a shared delivery (S, To) looks up (S, To) in the table
+ * tm_batch_deliver searches.  A member without an entry is legal: its
+ * delivery passes through unenriched (get_subopts/2 = [], enrich_subopts([],
+ * Msg, _) leaves the message alone, src/emqx_session.erl:500-509) -- the
+ * publish's QoS and retain flag, no TM_MSG_NL, subid 0, never own.  A
+ * non-shared delivery without options stays TM_EIO.  A shared delivery with
+ * nl = 1 from its own publisher is own.  TM_EIO + tm_last_error() if a pick
+ * found a group without a member.
+ * TM_EINVAL + tm_last_error(): unknown strategy or flag, TM_SHARED_COUNT_ONLY
+ * or TM_SHARED_DEVICE (no meaning here), TM_SHARED_HASH without keys, a
+ * TM_BATCH_DEDUP batch.  TM_ENODEV on a host-only engine.
+ * Not here: dispatch_with_ack/3 (shared_dispatch_ack_enabled = true), sticky. */
+TM_API int  tm_batch_shared_mode(tm_engine* e, tm_batch* b, const tm_shared_opts* opts);
+/* groups[q] = the group id of delivery q of the batch's most recent
+ * tm_batch_inboxes / tm_batch_deliver / tm_batch_window call, TM_NONE for an
+ * ordinary delivery: parallel to that call's publishes / filter_ids, compacted
+ * with them after deliver's No Local drops.  TM_INBOX_DEVICE: a device
+ * pointer; otherwise batch-owned pinned memory; both valid as that call's
+ * arrays.  TM_EINVAL on an unarmed batch, or when no such call ran armed. */
+TM_API int  tm_batch_inbox_groups(tm_engine* e, tm_batch* b, uint32_t flags, const uint32_t** groups);
 
 /* ---- bulk load + filter-sharded mode ------------------ */
 /* emqx_trie:insert/1 over n filters (filters = concatenated bytes, offsets[n+1]).
