@@ -3278,8 +3278,8 @@ __global__ __launch_bounds__(DD_BLOCK) void tm_dedup_claim(DedupArgs a) {
 // Pass 2 (count): publish t is its topic's representative when its offset is
 // the slot's (an empty topic: the first of the empty publishes at that
 // offset).  Ballots -> repbits; per DD_TILE block the representatives and
-// their bytes -> bcount / bbytes (scanned next).  16 independent slot ->
-// table chains per thread in flight.
+// their bytes -> bcount / bbytes (scanned next).  4 independent slot ->
+// table chains per thread in flight (DD_PT publishes, 256 apart).
 constexpr uint32_t DD_PT = DD_TILE / 256;
 
 __global__ __launch_bounds__(256) void tm_dedup_count(DedupArgs a) {
@@ -3287,7 +3287,7 @@ __global__ __launch_bounds__(256) void tm_dedup_count(DedupArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t t0 = blockIdx.x * DD_TILE;
     // every load of a stage issued before the next stage's: slot + offsets,
-    // then the table (16 independent chains per thread)
+    // then the table (4 independent chains per thread)
     uint32_t sl[DD_PT];
     uint64_t o0[DD_PT], o1[DD_PT];
 #pragma unroll
@@ -3344,7 +3344,7 @@ __device__ __forceinline__ uint64_t block256_excl_scan(uint64_t v, uint64_t* sh,
     return base + incl - v;
 }
 
-// Pass 3 (compact), same blocks, 16 consecutive publishes per thread: every
+// Pass 3 (compact), same blocks, 4 consecutive publishes per thread (DD_PT): every
 // representative's row and byte offset (block base from the scans + its rank
 // in the block), its bytes copied into the tokeniser's input, and
 // srow[slot] = row, rrep[row] = publish for the expansion.  A thread's

@@ -64,6 +64,19 @@ class Batch:
                                               self.n, flags, C.byref(h)), "tm_batch_prepare_on")
         self.h = h
 
+    def reprepare(self, topics, dedup=False):
+        """tm_batch_prepare_ex in place: new publishes in the same handle (its
+        replica, stream and buffers are kept)."""
+        s = _pack(topics)
+        self.n = len(s)
+        buf = s.buf if s.buf.size else np.zeros(1, np.uint8)
+        self._buf = np.ascontiguousarray(buf)
+        self._offs = np.ascontiguousarray(s.offs, dtype=np.uint64)
+        N.check(self.eng.L.tm_batch_prepare_ex(self.eng.h, self._buf.ctypes.data, self._offs.ctypes.data, self.n,
+                                               N.TM_BATCH_DEDUP if dedup else 0, C.byref(self.h)),
+                "tm_batch_prepare_ex")
+        return self
+
     @property
     def replica(self) -> int:
         return int(self.eng.L.tm_batch_replica(self.eng.h, self.h))
