@@ -1447,6 +1447,8 @@ int tm_topic_validate(int is_name, const uint8_t* t, size_t len, const char** re
     return TM_OK;
 }
 
+uint64_t tm_debug_fan_big_limit(tm_engine* e) { return e ? e->fan_big_limit : 0; }
+
 int tm_debug_check(tm_engine* e, uint64_t* max_disp_out) {
     if (!e) return TM_EINVAL;
     std::lock_guard<std::recursive_mutex> g(e->mu);

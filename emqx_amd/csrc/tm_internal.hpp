@@ -961,6 +961,7 @@ struct Knobs {
     int row_cap = 0;               // TM_ROWCAP: fast-path row slots per topic (1..128)
     uint32_t slow_lds = 0;         // TM_SLOW_LDS: generic-path LDS stack entries (small: forces the global restart)
     uint64_t fan_big = 0;          // TM_FAN_BIG: fan-out scan blocks above this use u64 offsets
+    bool fan_big_set = false;      //   ... and whether it was given: 0 is a limit (every block with a delivery)
     uint64_t result_limit = 0;     // TM_RESULT_LIMIT: matches per batch
     uint64_t staging_min = 0;      // TM_STAGING_MIN: initial staging entries of a batch
     std::string shard_link;        // TM_SHARD_LINK (staged | peer | probe), TM_SHARD_STAGED=1
@@ -979,7 +980,10 @@ struct Knobs {
         k.dedup_weak_hash = on("TM_DEDUP_WEAK_HASH");
         if (const char* v = env("TM_ROWCAP")) k.row_cap = std::min(128, std::max(1, atoi(v)));
         if (const char* v = env("TM_SLOW_LDS")) k.slow_lds = (uint32_t)std::max(1, atoi(v));
-        if (const char* v = env("TM_FAN_BIG")) k.fan_big = std::min<uint64_t>(0xFFFFFFFFull, strtoull(v, nullptr, 10));
+        if (const char* v = env("TM_FAN_BIG")) {
+            k.fan_big = std::min<uint64_t>(0xFFFFFFFFull, strtoull(v, nullptr, 10));
+            k.fan_big_set = true;
+        }
         if (const char* v = env("TM_RESULT_LIMIT")) k.result_limit = strtoull(v, nullptr, 10);
         if (const char* v = env("TM_STAGING_MIN")) k.staging_min = std::max<uint64_t>(64, strtoull(v, nullptr, 10));
         if (on("TM_SHARD_STAGED")) k.shard_link = "staged";

@@ -7,7 +7,7 @@ int tm_engine::init(const tm_config* cfg, const int32_t* devices, uint32_t ndev)
     kn = Knobs::read();
     checked = kn.checked;
     if (kn.row_cap) row_cap = (uint32_t)kn.row_cap;
-    if (kn.fan_big) fan_big_limit = kn.fan_big;
+    if (kn.fan_big_set) fan_big_limit = kn.fan_big;
     if (kn.result_limit) result_limit = std::min<uint64_t>(MAX_RESULT, kn.result_limit);
     if (kn.staging_min) staging_min = kn.staging_min;
     threads = (cfg && cfg->host_threads) ? cfg->host_threads : default_threads(kn);

@@ -1237,6 +1237,12 @@ class Engine:
         N.check(self.L.tm_debug_check(self.h, C.byref(md)), "tm_debug_check")
         return int(md.value)
 
+    @property
+    def fan_big_limit(self) -> int:
+        """tm_debug_fan_big_limit: deliveries of a fan-out scan block above which
+        its match offsets are u64 (TM_FAN_BIG at creation, else 2^32 - 1)."""
+        return int(self.L.tm_debug_fan_big_limit(self.h))
+
 
 class ShardedBatch:
     """A publish batch of a ShardedGroup (tm_sharded_prepare / run / result)."""

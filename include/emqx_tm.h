@@ -1171,6 +1171,11 @@ TM_API int  tm_sharded_filter_copy(tm_sharded* s, uint32_t gid, uint8_t* buf, si
  * found by the lookup the kernels mirror.  TM_EIO + tm_last_error() on the
  * first violation; *max_disp_out (may be NULL) = the largest displacement. */
 TM_API int  tm_debug_check(tm_engine* e, uint64_t* max_disp_out);
+/* The fan-out's width limit (tests): a scan block of tm_batch_dispatch that
+ * delivers more keeps its match offsets as u64.  2^32 - 1 unless TM_FAN_BIG
+ * was set when the engine was created; 0 then means every block that has a
+ * delivery. */
+TM_API uint64_t tm_debug_fan_big_limit(tm_engine* e);
 /* Text of the last TM_EIO on this thread (HIP error string + call site). */
 TM_API const char* tm_last_error(void);
 TM_API const char* tm_build_info(void);
