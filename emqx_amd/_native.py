@@ -361,6 +361,7 @@ SIGNATURES = {
     "tm_sharded_filter_copy": (C.c_int, [P, C.c_uint32, P, SZ, C.POINTER(SZ)]),
     "tm_debug_check": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "tm_debug_fan_big_limit": (C.c_uint64, [P]),
+    "tm_debug_batch_slow": (C.c_int, [P, C.POINTER(C.c_uint32)]),
     "tm_last_error": (C.c_char_p, []),
     "tm_build_info": (C.c_char_p, []),
     "tm_device_count": (C.c_int, []),

@@ -1449,6 +1449,15 @@ int tm_topic_validate(int is_name, const uint8_t* t, size_t len, const char** re
 
 uint64_t tm_debug_fan_big_limit(tm_engine* e) { return e ? e->fan_big_limit : 0; }
 
+int tm_debug_batch_slow(tm_batch* b, uint32_t out[4]) {
+    if (!b || !out) return TM_EINVAL;
+    out[0] = (b->done && b->walk.h_ctrl) ? b->walk.h_ctrl[CTRL_SLOW_RESTARTS] : 0u;
+    out[1] = b->s_qcap;
+    out[2] = b->s_ocap;
+    out[3] = b->s_waves;
+    return TM_OK;
+}
+
 int tm_debug_check(tm_engine* e, uint64_t* max_disp_out) {
     if (!e) return TM_EINVAL;
     std::lock_guard<std::recursive_mutex> g(e->mu);

@@ -131,6 +131,7 @@ enum Ctrl : uint32_t {
     CTRL_SLOW_DONE = 3,
     CTRL_TILE_NEXT = 4,     // (unused: tail tickets live in MatchArgs.xtickets)
     CTRL_NROWS = 5,         // TM_BATCH_DEDUP on the device: distinct topics (rows) of the batch
+    CTRL_SLOW_RESTARTS = 6, // generic path: walks that outgrew the LDS stack and started again (tm_debug_batch_slow)
     CTRL_WORDS = 16
 };
 constexpr uint32_t ERR_STAGING = 1;      // staging capacity exceeded

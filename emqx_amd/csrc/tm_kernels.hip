@@ -1304,6 +1304,7 @@ __global__ __launch_bounds__(64) void tm_match_slow(MatchArgs a) {
                 __syncthreads();
             }
             if (spill) {
+                if (lane == 0) atomicAdd(&a.ctrl[CTRL_SLOW_RESTARTS], 1u);
                 in_lds = false;
                 __syncthreads();
                 continue;

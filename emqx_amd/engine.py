@@ -81,6 +81,14 @@ class Batch:
     def replica(self) -> int:
         return int(self.eng.L.tm_batch_replica(self.eng.h, self.h))
 
+    @property
+    def slow_info(self) -> dict:
+        """tm_debug_batch_slow: the generic path's restarts in the last launch
+        and its scratch sizes (entries per wave) and waves."""
+        out = (C.c_uint32 * 4)()
+        N.check(self.eng.L.tm_debug_batch_slow(self.h, out), "tm_debug_batch_slow")
+        return dict(zip(("restarts", "s_qcap", "s_ocap", "s_waves"), map(int, out)))
+
     def row_map(self):
         """-> (row_of uint32[n publishes], n_rows): result row of every publish."""
         p = C.POINTER(C.c_uint32)()

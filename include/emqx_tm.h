@@ -1176,6 +1176,12 @@ TM_API int  tm_debug_check(tm_engine* e, uint64_t* max_disp_out);
  * was set when the engine was created; 0 then means every block that has a
  * delivery. */
 TM_API uint64_t tm_debug_fan_big_limit(tm_engine* e);
+/* The generic path of a batch (tests): out = {walks of the last launch that
+ * outgrew the LDS probe stack and started again in global scratch, probe
+ * stack entries and row entries of a wave's global scratch (both grow 4x when
+ * a row exceeds them, and the batch is launched again), waves}.  The first is
+ * 0 until tm_batch_wait has returned. */
+TM_API int  tm_debug_batch_slow(tm_batch* b, uint32_t out[4]);
 /* Text of the last TM_EIO on this thread (HIP error string + call site). */
 TM_API const char* tm_last_error(void);
 TM_API const char* tm_build_info(void);
