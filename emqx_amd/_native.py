@@ -362,10 +362,20 @@ SIGNATURES = {
     "tm_debug_check": (C.c_int, [P, C.POINTER(C.c_uint64)]),
     "tm_debug_fan_big_limit": (C.c_uint64, [P]),
     "tm_debug_batch_slow": (C.c_int, [P, C.POINTER(C.c_uint32)]),
+    "tm_debug_upload_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "tm_debug_shadow_sync": (C.c_int, [P, C.c_int, C.POINTER(C.c_uint64)]),
+    "tm_debug_replica_diff": (C.c_int, [P, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]),
     "tm_last_error": (C.c_char_p, []),
     "tm_build_info": (C.c_char_p, []),
     "tm_device_count": (C.c_int, []),
 }
+
+# out[] of tm_debug_upload_info (TM_UPLOAD_*) and the rows of a table comparison (TM_DIFF_*)
+UPLOAD_INFO = ("slots", "dirty", "full_dirty", "dirty_f", "full_f_dirty", "nodes", "fbytes", "dict_keys", "dict_dirty",
+               "dict_gen", "dict_tails", "dict_arena", "needs_repack", "repacks", "fmeta_full", "fmeta_delta",
+               "fmeta_nodes", "keys_full", "keys_delta", "keys_scattered", "tail_pinned", "tail_pageable",
+               "slots_realloc", "uploads_full", "uploads_delta", "delta_slots")
+DIFF_TABLES = ("slots", "foff", "flen", "foff_dead", "flen_dead", "fbytes", "dkey", "tail", "arena")
 
 _lib = None
 

@@ -1202,6 +1202,47 @@ struct tm_engine {
 
     uint64_t version = 1;
     uint64_t uploads_full = 0, uploads_delta = 0, delta_slots = 0, graph_launches = 0;
+    // the upload path's other decisions, counted per replica like the three
+    // above (tm_debug_upload_info; tm_engine_stats keeps its layout): re-packs,
+    // filter metadata and dictionary keys copied whole / scattered, appended
+    // tails through the pinned staging / from pageable memory, d_slots
+    // reallocations
+    uint64_t up_repacks = 0, up_fmeta_full = 0, up_fmeta_delta = 0, up_fmeta_nodes = 0, up_keys_full = 0,
+             up_keys_delta = 0, up_keys_scattered = 0, up_tail_pinned = 0, up_tail_pageable = 0, up_slots_realloc = 0;
+    // tm_debug_shadow_sync (tests): a replica's seven tables in host memory,
+    // brought up to date from the gathered deltas by the rules of upload_to /
+    // sync_dict -- a vector's size stands for the device buffer's capacity,
+    // and a buffer that would be reallocated loses its contents (POISON).
+    // Empty until the first call; the staging of a host-only engine's
+    // gather lives here too.
+    struct Shadow {
+        static constexpr uint8_t POISON = 0xA5;
+        std::vector<Slot> slots;
+        std::vector<uint64_t> foff;
+        std::vector<uint32_t> flen;
+        std::vector<uint8_t> fbytes;
+        std::vector<DictKey> dkey;
+        std::vector<DictTail> tail;
+        std::vector<uint8_t> arena;
+        bool slots_made = false, dkey_made = false;   // (a replica's d_nslots / d_dict_n start at 0)
+        uint64_t fbytes_uploaded = 0, dict_gen = ~0ull;
+        size_t tails_uploaded = 0, arena_uploaded = 0;
+        std::vector<uint64_t> blob;
+        std::vector<uint32_t> dxidx;
+        std::vector<DictKey> dxval;
+        // DevBuf::alloc / reserve: a new block of n / max(n + n/4, MIN) elements
+        template <class T>
+        static void alloc(std::vector<T>& v, size_t n) {
+            v.clear();
+            v.resize(n);
+            if (n) memset(static_cast<void*>(v.data()), POISON, n * sizeof(T));
+        }
+        template <class T>
+        static void reserve(std::vector<T>& v, size_t n) {
+            if (n <= v.size() && !v.empty()) return;
+            alloc(v, std::max<size_t>(n + n / 4, 1024));
+        }
+    } shadow;
     bool frozen = false;           // TM_CFG_FROZEN_DICT: words only via tm_dict_load
     bool checked = false;          // TM_CHECKED=1: bounds-checked kernel variant
     uint32_t row_cap = 128;        // K: fast-path row slots per topic (TM_ROWCAP)
@@ -2038,6 +2079,35 @@ struct tm_engine {
     // with the calling thread's device set to `back` (or the first replica's).
     int sync_device(const Replica* back = nullptr);
 
+    // sync_device's three stages.  gather_deltas: the re-pack decision, the
+    // blob's layout, the slot / filter-metadata / dictionary delta gathers
+    // (their marks cleared) and the full-or-delta decisions, once for every
+    // replica; upload_to + sync_dict: one replica's copies and scatters;
+    // consume_deltas: the dirty sets emptied and each replica's upload event
+    // recorded (pageable / async: what upload_to reported per replica).
+    // tm_debug_shadow_sync runs the first and the last around a host-memory
+    // stand-in for a replica.
+    struct Gather {
+        bool slots_full = false, keys_full = false;
+        size_t nn = 0;   // node records when gathered
+    };
+    int gather_deltas(Gather& G);
+    int consume_deltas(const Gather& G, const std::vector<uint8_t>& pageable, const std::vector<uint8_t>& async);
+    // the shadow's share of an upload (between gather_deltas and consume_deltas)
+    void shadow_apply(const Gather& G);
+    // a copy of the seven tables (the shadow, or a replica's read back) and its
+    // comparison with the host's: tm_debug_shadow_sync / tm_debug_replica_diff
+    struct TableView {
+        const Slot* slots; size_t nslots;
+        const uint64_t* foff; size_t nfoff;
+        const uint32_t* flen; size_t nflen;
+        const uint8_t* fbytes; size_t nfbytes;
+        const DictKey* dkey; size_t ndkey;
+        const DictTail* tail; size_t ntail;
+        const uint8_t* arena; size_t narena;
+    };
+    void table_diff(const TableView& V, uint64_t* out) const;
+
     // one replica's share of sync_device: the staged deltas (or full tables)
     int upload_to(Replica& R, bool slots_full, bool keys_full, size_t nn, bool& pageable_used, bool& async_used);
     static constexpr size_t APP_MAX = 8u << 20;
@@ -2063,6 +2133,7 @@ struct tm_engine {
             pageable_used = true;
             HIP_OK(hipMemcpyAsync(R.tab.d_dkey.p, tab.data(), tab.size() * sizeof(DictKey), hipMemcpyHostToDevice, stream));
             R.d_dict_gen = dict.gen();
+            ++up_keys_full;
         } else if (!dx.empty()) {
             const size_t k = dx.size();
             if ((rc = R.tab.d_dxidx.reserve(k))) return rc;
@@ -2070,6 +2141,8 @@ struct tm_engine {
             HIP_OK(hipMemcpyAsync(R.tab.d_dxidx.p, h_dxidx.p, k * 4, hipMemcpyHostToDevice, stream));
             HIP_OK(hipMemcpyAsync(R.tab.d_dxval.p, h_dxval.p, k * sizeof(DictKey), hipMemcpyHostToDevice, stream));
             HIP_OK(launch_scatter_keys(R.tab.d_dkey.p, R.tab.d_dxidx.p, R.tab.d_dxval.p, (uint32_t)k, stream));
+            ++up_keys_delta;
+            up_keys_scattered += k;
             async_used = true;
         }
         if (R.tab.d_tail.cap < tl.size() + 1) {

@@ -1245,6 +1245,33 @@ class Engine:
         N.check(self.L.tm_debug_check(self.h, C.byref(md)), "tm_debug_check")
         return int(md.value)
 
+    def upload_info(self) -> dict:
+        """tm_debug_upload_info: what the delta-upload path has pending and
+        what it has done so far, by name (N.UPLOAD_INFO); uploads nothing."""
+        out = (C.c_uint64 * len(N.UPLOAD_INFO))()
+        N.check(self.L.tm_debug_upload_info(self.h, out), "tm_debug_upload_info")
+        return dict(zip(N.UPLOAD_INFO, (int(x) for x in out)))
+
+    @staticmethod
+    def _diff(out) -> dict:
+        return {t: (int(out[2 * i]), None if out[2 * i + 1] == 2 ** 64 - 1 else int(out[2 * i + 1]))
+                for i, t in enumerate(N.DIFF_TABLES)}
+
+    def shadow_sync(self, apply: bool = True) -> dict:
+        """tm_debug_shadow_sync: bring the engine's host-memory stand-in for a
+        replica up to date the way an upload would (apply), then compare it
+        with the host tables -> {table: (differing elements, first index)}."""
+        out = (C.c_uint64 * (2 * len(N.DIFF_TABLES)))()
+        N.check(self.L.tm_debug_shadow_sync(self.h, int(bool(apply)), out), "tm_debug_shadow_sync")
+        return self._diff(out)
+
+    def replica_diff(self, replica: int = 0, sync: bool = True) -> dict:
+        """tm_debug_replica_diff: (after a tm_sync, if sync) the replica's tables
+        read back and compared with the host's, as shadow_sync reports."""
+        out = (C.c_uint64 * (2 * len(N.DIFF_TABLES)))()
+        N.check(self.L.tm_debug_replica_diff(self.h, replica, int(bool(sync)), out), "tm_debug_replica_diff")
+        return self._diff(out)
+
     @property
     def fan_big_limit(self) -> int:
         """tm_debug_fan_big_limit: deliveries of a fan-out scan block above which

@@ -1182,6 +1182,72 @@ TM_API uint64_t tm_debug_fan_big_limit(tm_engine* e);
  * a row exceeds them, and the batch is launched again), waves}.  The first is
  * 0 until tm_batch_wait has returned. */
 TM_API int  tm_debug_batch_slow(tm_batch* b, uint32_t out[4]);
+/* The delta-upload path (tests).  tm_sync / a launch bring every replica's
+ * copy of the edge hash, the filter metadata and bytes and the word dictionary
+ * up to the host trie in three stages: gather (the re-pack decision, the dirty
+ * slots / filter nodes / dictionary keys staged once, full-or-delta decided),
+ * per-replica apply (copies and scatter kernels), consume (dirty sets
+ * emptied).  The three calls below look at that path from outside.
+ *
+ * tm_debug_upload_info: what is pending and what the path has done so far,
+ * read under the engine lock; uploads nothing.  out[TM_UPLOAD_*]; the counters
+ * count per replica applied to (the shadow below counts as one). */
+enum {
+    TM_UPLOAD_SLOTS = 0,        /* edge-hash slots on the host */
+    TM_UPLOAD_DIRTY,            /* slots listed for the next delta */
+    TM_UPLOAD_FULL_DIRTY,       /* 1: the next upload copies the whole edge hash */
+    TM_UPLOAD_DIRTY_F,          /* filter-metadata nodes listed for the next delta */
+    TM_UPLOAD_FULL_F_DIRTY,     /* 1: the next upload copies all filter metadata */
+    TM_UPLOAD_NODES,            /* node records (live or not) */
+    TM_UPLOAD_FBYTES,           /* bytes in the filter arena */
+    TM_UPLOAD_DICT_KEYS,        /* slots of the dictionary's key table */
+    TM_UPLOAD_DICT_DIRTY,       /* key slots listed for the next delta (a slot may be listed twice) */
+    TM_UPLOAD_DICT_GEN,         /* rebuilds of the key table */
+    TM_UPLOAD_DICT_TAILS,       /* dictionary tails */
+    TM_UPLOAD_DICT_ARENA,       /* bytes in the word arena */
+    TM_UPLOAD_NEEDS_REPACK,     /* 1: the next upload re-packs the edge hash first */
+    TM_UPLOAD_N_REPACKS,        /* counters from here on: re-packs */
+    TM_UPLOAD_N_FMETA_FULL,     /* filter metadata copied whole */
+    TM_UPLOAD_N_FMETA_DELTA,    /* ... scattered */
+    TM_UPLOAD_N_FMETA_NODES,    /* nodes in those scatters */
+    TM_UPLOAD_N_KEYS_FULL,      /* dictionary keys copied whole */
+    TM_UPLOAD_N_KEYS_DELTA,     /* ... scattered */
+    TM_UPLOAD_N_KEYS_SCATTERED, /* key slots in those scatters */
+    TM_UPLOAD_N_TAIL_PINNED,    /* appended tails copied through the pinned staging */
+    TM_UPLOAD_N_TAIL_PAGEABLE,  /* ... from pageable memory */
+    TM_UPLOAD_N_SLOTS_REALLOC,  /* edge-hash buffers (re)allocated */
+    TM_UPLOAD_N_FULL,           /* tm_engine_stats uploads_full / uploads_delta / delta_slots */
+    TM_UPLOAD_N_DELTA,
+    TM_UPLOAD_N_DELTA_SLOTS,
+    TM_UPLOAD_INFO_N
+};
+TM_API int  tm_debug_upload_info(tm_engine* e, uint64_t out[TM_UPLOAD_INFO_N]);
+/* A table comparison: out[2 * t] = elements of table t that differ from the
+ * host's over its live extent (every slot, every node record, the bytes in
+ * use; an element the copy has no room for differs), out[2 * t + 1] = the first
+ * such index, ~0 if none.  Filter metadata of nodes that are no filter now is
+ * counted apart: it is never read, and only the other rows must be 0. */
+enum {
+    TM_DIFF_SLOTS = 0, TM_DIFF_FOFF, TM_DIFF_FLEN, TM_DIFF_FOFF_DEAD, TM_DIFF_FLEN_DEAD, TM_DIFF_FBYTES,
+    TM_DIFF_DKEY, TM_DIFF_TAIL, TM_DIFF_ARENA, TM_DIFF_TABLES
+};
+/* tm_debug_shadow_sync (tests): the engine keeps a stand-in for a replica in
+ * host memory, empty until the first call.  apply != 0: the gather stage runs,
+ * its result is applied to the shadow as a replica would receive it (whole
+ * copies where the gather or a size change says so, the staged index / value
+ * pairs otherwise, the appended tails from the shadow's own marks, buffers
+ * regrown by the replicas' rules and losing their contents), and the consume
+ * stage runs.  Then, and alone with apply == 0, the shadow is compared with
+ * the host tables.  Works on a host-only engine; covers which slots are
+ * marked and which path is chosen, not the copies and scatter kernels.
+ * TM_EINVAL with apply != 0 on an engine with replicas: the dirty sets are
+ * consumed once. */
+TM_API int  tm_debug_shadow_sync(tm_engine* e, int apply, uint64_t out[2 * TM_DIFF_TABLES]);
+/* tm_debug_replica_diff (tests): with sync != 0 first what tm_sync does; then
+ * the replica's seven tables are copied back and compared as above.  TM_EIO +
+ * tm_last_error() if the replica's edge hash or dictionary key table has
+ * another size than the host's; TM_ENODEV on a host-only engine. */
+TM_API int  tm_debug_replica_diff(tm_engine* e, uint32_t replica, int sync, uint64_t out[2 * TM_DIFF_TABLES]);
 /* Text of the last TM_EIO on this thread (HIP error string + call site). */
 TM_API const char* tm_last_error(void);
 TM_API const char* tm_build_info(void);
