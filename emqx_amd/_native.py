@@ -360,6 +360,7 @@ SIGNATURES = {
     "tm_sharded_match_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Result)]),
     "tm_sharded_filter_copy": (C.c_int, [P, C.c_uint32, P, SZ, C.POINTER(SZ)]),
     "tm_debug_check": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "tm_debug_slots": (C.c_int, [P, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint64)]),
     "tm_debug_fan_big_limit": (C.c_uint64, [P]),
     "tm_debug_batch_slow": (C.c_int, [P, C.POINTER(C.c_uint32)]),
     "tm_debug_upload_info": (C.c_int, [P, C.POINTER(C.c_uint64)]),

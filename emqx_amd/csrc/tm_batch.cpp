@@ -707,7 +707,13 @@ int tm_engine::launch(tm_batch* b, bool csr, SlotTail* tail) {
     // at its first bucket with a free last slot all the same, and a value
     // that changes only at these steps keeps the captured launch graphs of
     // churned batches valid)
-    a.max_probe = max_disp <= 4 ? 4 : max_disp <= 8 ? 8 : max_disp <= 16 ? 16 : max_disp <= 48 ? 48 : max_disp;
+    // Every insert path bounds max_disp by MAX_PROBE_DISP before it returns; a
+    // table it could not bring under the bound is not launched against, and
+    // the clamp keeps the kernel argument inside the walk's displacement field
+    // whatever the host believes.
+    if (max_disp > MAX_PROBE_DISP) return probe_bound_error();
+    static_assert(MAX_PROBE_DISP >= 16, "the steps below end at the bound");
+    a.max_probe = max_disp <= 4 ? 4 : max_disp <= 8 ? 8 : max_disp <= 16 ? 16 : MAX_PROBE_DISP;
     a.root = root_rec();
     a.foff = R.tab.d_foff.p; a.flen = R.tab.d_flen.p; a.fbytes = R.tab.d_fbytes.p;
     a.words = b->tok.d_words.p; a.toff = b->tok.d_toff.p; a.tflags = b->tok.d_tflags.p; a.n = b->n;

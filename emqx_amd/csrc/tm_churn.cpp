@@ -73,6 +73,7 @@ int tm_engine::trie_insert_ids(const uint8_t* t, size_t len, const uint32_t* ids
     set_topic(p, t, len);   // write_trie_node(#trie_node{node_id = Topic, topic = Topic})
     if (M) ++M->version;
     else ++version;
+    if (!M && max_disp > MAX_PROBE_DISP) return probe_bound_error();   // (bound_probe_runs gave up)
     return TM_OK;
 }
 
@@ -428,7 +429,9 @@ void tm_engine::edge_phase(const std::vector<std::vector<Mut>*>& Ws) {
     // for the whole batch) is known now: the deletes free exactly ndel slots
     // and leave max_disp as it is.  Without one, the inserts' ranges are the
     // deletes' and everything is bucketed in one run below.
-    const auto need_rehash = [&](uint64_t used) { return (used + nins) * 4 > slots.size() * 3 || max_disp > 48; };
+    const auto need_rehash = [&](uint64_t used) {
+        return (used + nins) * 4 > slots.size() * 3 || max_disp > MAX_PROBE_DISP;
+    };
     const bool rehash_ahead = need_rehash(used_slots - ndel);
     unsigned T2 = 0;
     uint32_t RS = 0, R = 0;
@@ -502,7 +505,7 @@ void tm_engine::edge_phase(const std::vector<std::vector<Mut>*>& Ws) {
     const auto e1 = now();
     bool rehashed = false;
     if (need_rehash(used_slots)) {
-        rehash(std::max<size_t>((size_t)((live_edges + nins) / 0.55), slots.size() * (max_disp > 48 ? 2 : 1)));
+        rehash(std::max<size_t>((size_t)((live_edges + nins) / 0.55), slots.size() * (max_disp > MAX_PROBE_DISP ? 2 : 1)));
         rehashed = true;
     }
     const auto e2 = now();
@@ -553,7 +556,7 @@ void tm_engine::edge_phase(const std::vector<std::vector<Mut>*>& Ws) {
     for (unsigned w = 0; w < NB && nins; ++w)
         if (itail < edge_bins[w].ins.size())
             for (const auto& e : edge_bins[w].ins[itail]) insert_edge(e[0], e[1], e[2]);
-    if (max_disp > 48) rehash(std::max<size_t>((size_t)(live_edges / 0.55), slots.size() * 2));
+    bound_probe_runs();   // (past its tries: the call returns TM_EOVERFLOW, mutate_parallel / apply)
     tr_mark("e.itail");
     const auto e3 = now();
     // ---- summaries of the nodes whose record changed: by node (a node's
@@ -814,6 +817,7 @@ void tm_engine::par_finish(ParRun* const* runs, size_t nr) {
             version += m.version;
             R.done += m.done;
             if (m.rc && !R.rc) R.rc = m.rc;
+            if (!R.rc && max_disp > MAX_PROBE_DISP) R.rc = probe_bound_error();   // (the edge phase gave up)
             m.fresh_base = fb_end;   // (reused: this worker's bytes start here)
             fb_end += m.fb.size();
             df_at.push_back(df_end);

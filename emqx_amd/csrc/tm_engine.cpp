@@ -1517,6 +1517,21 @@ int tm_debug_check(tm_engine* e, uint64_t* max_disp_out) {
         return TM_EIO;
     }
     if (max_disp_out) *max_disp_out = md;
+    if (md > MAX_PROBE_DISP || e->max_disp > MAX_PROBE_DISP) {   // (what a launch reads: max_disp)
+        snprintf(last_error(), 512, "max_disp %u (farthest key: %llu buckets) exceeds the probe bound %u", e->max_disp,
+                 (unsigned long long)md, MAX_PROBE_DISP);
+        return TM_EIO;
+    }
+    return TM_OK;
+}
+
+int tm_debug_slots(tm_engine* e, uint32_t* out, uint64_t cap_slots, uint64_t* nbuckets_out) {
+    if (!e || !nbuckets_out || (!out && cap_slots)) return TM_EINVAL;
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    *nbuckets_out = e->nbuckets();
+    if (cap_slots < e->slots.size()) return TM_EOVERFLOW;
+    static_assert(sizeof(Slot) == 4 * sizeof(uint32_t), "a slot is four u32");
+    memcpy(out, e->slots.data(), e->slots.size() * sizeof(Slot));
     return TM_OK;
 }
 

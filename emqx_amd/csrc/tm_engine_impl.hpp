@@ -1354,8 +1354,8 @@ struct tm_engine {
             M->made_put((uint64_t)p << 32 | w, c);
             return NONE;
         }
-        if (!M && ((used_slots + 1) * 4 > slots.size() * 3 || max_disp > 48))   // (phase 2 checks capacity first)
-            rehash(std::max<size_t>((size_t)((live_edges + 1) / 0.55), slots.size() * (max_disp > 48 ? 2 : 1)));
+        if (!M && ((used_slots + 1) * 4 > slots.size() * 3 || max_disp > MAX_PROBE_DISP))   // (phase 2 checks capacity first)
+            rehash(std::max<size_t>((size_t)((live_edges + 1) / 0.55), slots.size() * (max_disp > MAX_PROBE_DISP ? 2 : 1)));
         uint32_t disp;
         bool was_empty;
         uint32_t i = place_slot(slots, p, w, disp, was_empty);
@@ -1372,7 +1372,30 @@ struct tm_engine {
         e.parent = p; e.word = w; e.child = c;
         nd[c].inslot = i;
         write_summary(c);
+        // (phase 2 of a parallel batch bounds the runs once, after its last insert)
+        if (!M && max_disp > MAX_PROBE_DISP) {
+            bound_probe_runs();
+            return nd[c].inslot;
+        }
         return i;
+    }
+
+    // Re-packs into twice the buckets while some key sits more than
+    // MAX_PROBE_DISP buckets from home, PROBE_REHASH_TRIES times at the most
+    // (TM_PROBE_TRIES lowers that for the tests).
+    // False if the last table still exceeds the bound: the inserting call then
+    // returns TM_EOVERFLOW, the keys stay (the host lookups find them), and no
+    // batch launches until a later insert or re-pack has brought the runs
+    // under the bound again (tm_engine::launch).
+    bool bound_probe_runs() {
+        for (uint32_t k = 0; k < kn.probe_tries && max_disp > MAX_PROBE_DISP; ++k)
+            rehash(std::max<size_t>((size_t)(live_edges / 0.55), slots.size() * 2));
+        return max_disp <= MAX_PROBE_DISP;
+    }
+    int probe_bound_error() const {
+        snprintf(last_error(), 512, "a key sits %u buckets from home, more than %u, after %u doublings of the table",
+                 max_disp, MAX_PROBE_DISP, kn.probe_tries);
+        return TM_EOVERFLOW;
     }
 
     // Removes the edge into c without tombstones.  The table keeps two

@@ -95,6 +95,15 @@ __host__ __device__ inline void slot_set_lsig(Slot& e, uint32_t sig) {
 }
 static_assert(sizeof(Slot) == 16, "slot is 16 bytes");
 constexpr uint32_t BUCKET = 4;   // slots per 64-B bucket
+// The probe-run bound: no live key sits more than this many buckets past its
+// home bucket whenever a launch can read the table.  An insert that places a
+// key further out re-packs into a table twice the size before it returns
+// (tm_engine::bound_probe_runs), the launch's max_probe is clamped to it, and
+// the tile walk's 6-bit displacement field (M_DISP_MASK) holds it.
+constexpr uint32_t MAX_PROBE_DISP = 48;
+// doublings an insert tries before it gives up with TM_EOVERFLOW (16x the
+// buckets: each doubling splits a run by one more leading bit of the hashes)
+constexpr uint32_t PROBE_REHASH_TRIES = 4;
 
 struct RootRec {
     uint32_t hterm;    // filter id of root/'#' or NONE
@@ -965,6 +974,7 @@ struct Knobs {
     bool fan_big_set = false;      //   ... and whether it was given: 0 is a limit (every block with a delivery)
     uint64_t result_limit = 0;     // TM_RESULT_LIMIT: matches per batch
     uint64_t staging_min = 0;      // TM_STAGING_MIN: initial staging entries of a batch
+    uint32_t probe_tries = PROBE_REHASH_TRIES;   // TM_PROBE_TRIES: doublings an insert tries for the probe bound (0: none)
     std::string shard_link;        // TM_SHARD_LINK (staged | peer | probe), TM_SHARD_STAGED=1
     // deployment knobs
     unsigned host_threads = 0;     // TM_HOST_THREADS: host workers when tm_config.host_threads is 0
@@ -987,6 +997,7 @@ struct Knobs {
         }
         if (const char* v = env("TM_RESULT_LIMIT")) k.result_limit = strtoull(v, nullptr, 10);
         if (const char* v = env("TM_STAGING_MIN")) k.staging_min = std::max<uint64_t>(64, strtoull(v, nullptr, 10));
+        if (const char* v = env("TM_PROBE_TRIES")) k.probe_tries = (uint32_t)std::min<int>(PROBE_REHASH_TRIES, std::max(0, atoi(v)));
         if (on("TM_SHARD_STAGED")) k.shard_link = "staged";
         else if (const char* v = env("TM_SHARD_LINK")) k.shard_link = v;
         if (const char* v = env("TM_HOST_THREADS")) k.host_threads = (unsigned)std::min(std::max(atoi(v), 0), 64);

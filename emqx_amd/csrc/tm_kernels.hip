@@ -48,8 +48,9 @@ constexpr uint32_t M_PLUS = 1u << 10;    // probe the '+' edge (else the literal
 constexpr uint32_t M_SKIPE = 1u << 11;   // don't emit the child's own topic (literal '#' dup)
 constexpr uint32_t M_DSTART = 1u << 12;  // $-rooted start probe: the node was already counted
 static_assert(FAST_MAX_DEPTH <= (int)M_LVL_MASK, "level field too narrow");
-constexpr uint32_t M_DISP_SHIFT = 13;    // bucket displacement of a continued probe (<= max_probe <= 48)
+constexpr uint32_t M_DISP_SHIFT = 13;    // bucket displacement of a continued probe (<= max_probe <= MAX_PROBE_DISP)
 constexpr uint32_t M_DISP_MASK = 0x3F;
+static_assert(MAX_PROBE_DISP <= M_DISP_MASK, "the displacement field holds every bounded probe run");
 // probe-entry marks written by the quad: FOUND | the child's literal signature
 // into the parent field, TAIL into the word field (never a parent / word id)
 constexpr uint32_t Q_FOUND = ~((1u << LSIG_BITS) - 1u);

@@ -60,6 +60,7 @@ int tm_engine::gather_deltas(Gather& G) {
     // target load so the walk's working set stays small (a full upload)
     if (needs_repack()) {
         rehash((size_t)(live_edges / target_load));
+        if (!bound_probe_runs()) return probe_bound_error();   // (the re-packed table is what launches read)
         rebuild_lext();   // (a full upload follows the re-pack anyway)
         ++up_repacks;
     }

@@ -1245,6 +1245,19 @@ class Engine:
         N.check(self.L.tm_debug_check(self.h, C.byref(md)), "tm_debug_check")
         return int(md.value)
 
+    def debug_slots(self):
+        """tm_debug_slots: the host edge hash as stored -> (nslots x 4 u32
+        array of parent, word, child, hash; bucket count).  Read-only; works
+        on a host-only engine."""
+        nb = C.c_uint64()
+        rc = self.L.tm_debug_slots(self.h, None, 0, C.byref(nb))
+        if rc != N.TM_EOVERFLOW:
+            N.check(rc, "tm_debug_slots")
+        out = np.empty((int(nb.value) * 4, 4), np.uint32)
+        N.check(self.L.tm_debug_slots(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.shape[0], C.byref(nb)),
+                "tm_debug_slots")
+        return out, int(nb.value)
+
     def upload_info(self) -> dict:
         """tm_debug_upload_info: what the delta-upload path has pending and
         what it has done so far, by name (N.UPLOAD_INFO); uploads nothing."""

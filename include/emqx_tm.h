@@ -154,7 +154,11 @@ TM_API int  tm_sync(tm_engine* e);
 TM_API int  tm_sync_async(tm_engine* e);
 
 /* ---- emqx_trie (src/emqx_trie.erl) ----------------------------------- */
-/* emqx_trie:insert/1 (:81-93): idempotent; add_path/1 (:145-158) semantics. */
+/* emqx_trie:insert/1 (:81-93): idempotent; add_path/1 (:145-158) semantics.
+ * TM_EOVERFLOW + tm_last_error() (here and from every other call that
+ * inserts): the edge hash could not be re-packed so that every key lies
+ * within 48 buckets of home (see tm_debug_check); the filter is inserted, and
+ * batches do not launch until a later insert has restored the bound. */
 TM_API int  tm_trie_insert(tm_engine* e, const uint8_t* topic, size_t len);
 /* emqx_trie:delete/1 (:107-116) + delete_path/1 (:190-204). */
 TM_API int  tm_trie_delete(tm_engine* e, const uint8_t* topic, size_t len);
@@ -1169,8 +1173,21 @@ TM_API int  tm_sharded_filter_copy(tm_sharded* s, uint32_t gid, uint8_t* buf, si
 /* Consistency check of the host edge hash (tests): slots of a bucket filled
  * in order, every key's probe run unbroken and within max_disp, every key
  * found by the lookup the kernels mirror.  TM_EIO + tm_last_error() on the
- * first violation; *max_disp_out (may be NULL) = the largest displacement. */
+ * first violation; *max_disp_out (may be NULL) = the largest displacement.
+ * A largest displacement above the probe bound (48 buckets, MAX_PROBE_DISP)
+ * is a violation too, reported last: *max_disp_out is set all the same.
+ * (An insert re-packs into twice the buckets, up to four times, until the
+ * bound holds; one that still cannot meet it returns TM_EOVERFLOW +
+ * tm_last_error(), its filter stays in the trie, and launches return
+ * TM_EOVERFLOW until a later insert or re-pack has restored the bound.) */
 TM_API int  tm_debug_check(tm_engine* e, uint64_t* max_disp_out);
+/* The host edge hash as it is stored (tests; read-only): *nbuckets_out = its
+ * bucket count (four 16-B slots each); the slots are copied to out as four
+ * u32 each -- parent, word, child, hash, flag and signature bits included, a
+ * free slot's parent 0xFFFFFFFF -- when cap_slots >= 4 * *nbuckets_out, else
+ * TM_EOVERFLOW (the bucket count is set all the same: call with out = NULL,
+ * cap_slots = 0 to size the buffer).  Works on a host-only engine. */
+TM_API int  tm_debug_slots(tm_engine* e, uint32_t* out, uint64_t cap_slots, uint64_t* nbuckets_out);
 /* The fan-out's width limit (tests): a scan block of tm_batch_dispatch that
  * delivers more keeps its match offsets as u64.  2^32 - 1 unless TM_FAN_BIG
  * was set when the engine was created; 0 then means every block that has a
