@@ -51,10 +51,26 @@ static_assert(FAST_MAX_DEPTH <= (int)M_LVL_MASK, "level field too narrow");
 constexpr uint32_t M_DISP_SHIFT = 13;    // bucket displacement of a continued probe (<= max_probe <= MAX_PROBE_DISP)
 constexpr uint32_t M_DISP_MASK = 0x3F;
 static_assert(MAX_PROBE_DISP <= M_DISP_MASK, "the displacement field holds every bounded probe run");
+// How a quad of lanes serves a probe's owner lane in the frontier loop (A/B
+// builds: python -m emqx_amd.build --variant NAME -DTM_QUAD_OWN=n):
+//   1  the owner sits in the quad that reads its bucket: the request reaches
+//      the quad by DPP, the found slot goes back whole (one ds_write_b128)
+//   2  the DPP requests of 1 with the report of 0 (measurement only)
+//   0  the protocol of rounds 1-10: probe 16r + q, request and report through
+//      the owner's LDS entry, field by field
+#ifndef TM_QUAD_OWN
+#define TM_QUAD_OWN 1
+#endif
+#if TM_QUAD_OWN != 1
 // probe-entry marks written by the quad: FOUND | the child's literal signature
 // into the parent field, TAIL into the word field (never a parent / word id)
 constexpr uint32_t Q_FOUND = ~((1u << LSIG_BITS) - 1u);
 constexpr uint32_t Q_TAIL = 0xFFFFFFFFu;
+#endif
+// A lane without a probe offers its quad this byte offset into the slot table:
+// with the three slots after it, it lies past every table that is read with
+// buffer loads (launch_match), so the loads return 0 without a memory access.
+constexpr uint32_t OFF_NONE = 0xFFFFFFC0u;
 
 // digit tables indexed by class (C_BELOW, C_BETWEEN, C_ABOVE, C_EMPTY):
 //   L = literal branch, H = '#' terminal, P = '+' branch; E = 0, L_lo = 1.
@@ -296,6 +312,18 @@ __device__ __forceinline__ uint32_t xor_lane32_bc(uint32_t v, uint32_t j) {
     case 4: return (uint32_t)__builtin_amdgcn_update_dpp(0, __builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true),
                                                          0x1B, 0xF, 0xF, true);
     default: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);
+    }
+}
+
+// The value of lane r of each quad in all four of its lanes: DPP
+// quad_perm:[r,r,r,r].  r is a compile-time constant once the rounds unroll.
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v, uint32_t r) {
+    const int x = (int)v;
+    switch (r) {
+    case 0: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x00, 0xF, 0xF, true);
+    case 1: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x55, 0xF, 0xF, true);
+    case 2: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0xAA, 0xF, 0xF, true);
+    default: return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0xFF, 0xF, 0xF, true);
     }
 }
 
@@ -660,16 +688,24 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
     // ---- frontier loop: LIFO stack, up to 64 probes per iteration
     //
     // Quad-cooperative probing: probe p (0..63) of an iteration is read by the
-    // quad of lanes 4q..4q+3 in round r (p = 16r + q), each lane loading one
-    // 16-B slot of the 64-B bucket, so a load instruction touches 16 cache
-    // lines instead of 64 (one L1 tag lookup per probe instead of four: the
-    // lookups, not the bytes, saturate the L1 at full occupancy).  The popped
-    // entries stay in their LDS slots during the probe: the owner lane writes
-    // the bucket index into its entry, the quads read it from there, and the
-    // matching lane writes the slot's child summary back for the owner.  A key
-    // that spilled past its home bucket is pushed again as a continuation
-    // (displacement + 1) rather than holding the whole wave for a dependent read.
+    // quad of lanes 4q..4q+3 in round r, each lane loading one 16-B slot of
+    // the 64-B bucket, so a load instruction touches 16 cache lines instead of
+    // 64 (one L1 tag lookup per probe instead of four: the lookups, not the
+    // bytes, saturate the L1 at full occupancy).  p = 4q + r: a probe's owner
+    // lane p sits in the quad that reads its bucket, and the quad takes the
+    // bucket, the parent and the word from its lane r by DPP quad_perm moves,
+    // with no LDS round trip between the hash and the bucket loads.  The
+    // popped entries stay in their LDS slots during the probe, and the quad
+    // reports through the owner's entry: the lane whose slot matches stores the
+    // slot over it whole, the lane of the bucket's last slot that slot's raw
+    // parent field into the word field.  A key that spilled past its home
+    // bucket is pushed again as a continuation (displacement + 1) rather than
+    // holding the whole wave for a dependent read.
+    // (TM_QUAD_OWN = 0: p = 16r + q, and the owner's bucket index goes through
+    // its entry as well.)
     const uint32_t qd = lane >> 2, qs = lane & 3;
+    // the entry of the probe that this lane's quad serves in round r
+    const auto q_of = [&](uint32_t r) -> uint32_t { return TM_QUAD_OWN ? 4 * qd + r : 16 * r + qd; };
     // The loop's wave-uniform operands get scalar registers of their own (the
     // empty asm defines them anew): as parts of the kernel-argument tuples
     // they were spilled to VGPR lanes with the tuples' cold parts and read
@@ -699,8 +735,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         // takes lane 0's entry along: every index derived from it (topic
         // lane, word offsets, row count) is then a live one, so the reads
         // below need no exec region of their own and `has` only gates what a
-        // lane pushes, emits and counts.  Its bucket store repeats lane 0's
-        // value at lane 0's address.
+        // lane pushes, emits and counts.
         const uint32_t idx = qn + (has ? lane : 0u);
         const uint4 e = L.q[idx];
         const uint32_t meta = e.x & 0x7FFFFFFFu;
@@ -709,11 +744,20 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         const uint32_t tl = meta & 63;
         const uint32_t lc = (meta >> M_LVL_SHIFT) & M_LVL_MASK;
         const uint32_t disp = (meta >> M_DISP_SHIFT) & M_DISP_MASK;
-        {
-            uint32_t hb = home_bucket(parent, pw, nbk) + disp;
-            if (hb >= nbk) hb -= nbk;
-            L.q[idx].x = hb;
-        }
+        uint32_t hb = home_bucket(parent, pw, nbk) + disp;
+        if (hb >= nbk) hb -= nbk;
+#if TM_QUAD_OWN
+        // What the owner offers its quad.  A lane without a probe offers a
+        // parent that no masked parent field equals, and a bucket that is
+        // safe to read: past the descriptor's range (reads 0, no memory
+        // access), or bucket 0 where the table is read with plain loads.  So
+        // the rounds need no validity test of their own.
+        if (CK) hb = (uint32_t)(CK_((uint64_t)hb * BUCKET + (BUCKET - 1), a.nslots, 1) / BUCKET);
+        const uint32_t o_par = has ? parent : SLOT_EMPTY;
+        const uint32_t o_bkt = BIG ? (has ? hb : 0u) : (has ? hb * (uint32_t)(BUCKET * sizeof(Slot)) : OFF_NONE);
+#else
+        L.q[idx].x = hb;   // (a lane without a probe repeats lane 0's value at lane 0's address)
+#endif
         // the slot table's descriptor, put together here from its scalars (the
         // asm keeps it from being hoisted: as a loop-invariant 4-dword tuple it
         // was spilled and read back lane by lane, with a hazard pad, every time)
@@ -723,7 +767,18 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         uint4 sl[4];
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
-            const uint32_t p = 16 * r + qd;
+#if TM_QUAD_OWN
+            rp[r] = quad_bcast(o_par, r);
+            rw[r] = quad_bcast(pw, r);
+            const uint32_t ob = quad_bcast(o_bkt, r);
+            if (!BIG) {
+                sl[r] = ld_b128(rsrc, ob + qs * (uint32_t)sizeof(Slot));
+            } else {
+                const u32x4_t g = ((gslots_t)(uint64_t)sbase)[(uint64_t)ob * BUCKET + qs];
+                sl[r] = uint4{g[0], g[1], g[2], g[3]};
+            }
+#else
+            const uint32_t p = q_of(r);
             const bool v = p < k;
             const uint4 rec = L.q[qn + (v ? p : 0u)];
             rp[r] = v ? rec.z : SLOT_EMPTY;
@@ -735,6 +790,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
                 const u32x4_t g = v ? ((gslots_t)(uint64_t)sbase)[si] : u32x4_t{0u, 0u, 0u, 0u};
                 sl[r] = uint4{g[0], g[1], g[2], g[3]};
             }
+#endif
         }
         // the topic's words are read while the buckets are in flight (the
         // barrier keeps the compiler from hoisting these LDS reads, and their
@@ -749,18 +805,57 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         const uint32_t w_here = word_at(CK_(base + lc - (at_end ? 1u : 0u), wlim, 11));
         const uint32_t w_prev = word_at(CK_(base + lc - 1, wlim, 10));
         // The quad reports to the owner through the owner's LDS entry, not
-        // through ballots: the matching lane writes the child summary and a
-        // FOUND mark, the lane of the bucket's last slot a TAIL mark when that
-        // slot is free (the probe run ends in this bucket).  Parent ids and
-        // word ids never equal the marks.  (rp is SLOT_EMPTY where the quad
-        // has no probe, which no masked parent field equals.)
+        // through ballots.  (rp is SLOT_EMPTY where the quad has no probe,
+        // which no masked parent field equals.)
+        uint32_t qs_now = qs;   // (compared here: the hoisted lane mask would be one more spilled pair)
+        asm volatile("" : "+v"(qs_now));
+#if TM_QUAD_OWN == 1
+        // The last slot's lane stores its slot's raw parent field into the
+        // word field of every round's entry, under one exec region for the
+        // four: SLOT_EMPTY there says that the probe run ends in this bucket.
+        // A quad without a probe (out-of-range load: reads 0) writes above the
+        // popped entries: when k < 64, qn is 0 after the pop and qn + p < 64
+        // is unused stack; when k = 64 every quad has a probe.
+        if (qs_now == 3) {
+#pragma unroll
+            for (uint32_t r = 0; r < 4; ++r) L.q[qn + q_of(r)].w = sl[r].x;
+        }
+        // Then the matching lane stores its slot over the entry, whole: a slot
+        // has the entry's shape, and the owner reads everything it needs off
+        // the slot's own fields.  A wave's LDS operations complete in order,
+        // so a match in the last slot overwrites that probe's tail word.
+#pragma unroll
+        for (uint32_t r = 0; r < 4; ++r) {
+            const bool m = (sl[r].x & ID_MASK) == rp[r] && (sl[r].y & WID_MASK) == rw[r];
+            if (m) L.q[qn + q_of(r)] = sl[r];
+        }
+        const uint4 res = L.q[idx];
+        // a row already longer than K goes to the generic path whole: its
+        // entries are not expanded further (C5 K = 1000: ~10k rows of ~1,000
+        // matches each stopped at K + 1 instead of walked to the end)
+        const bool live = has & (L.cnt[tl] <= rcap);
+        // An entry that still holds its parent was not found: a found one
+        // holds the slot's child field, and a child's id is never its parent's
+        // (new_node takes a free or a fresh id while the parent is live, ROOT
+        // is nobody's child; the flag bits lie above the 30-bit id).
+        const bool found = live & (res.z != parent);
+        const bool cont = live & !found & (res.w != SLOT_EMPTY) & (disp < maxp);
+        // the found child's summary (the slot's child and hash fields) and its
+        // literal signature (the top bits of the slot's key fields)
+        const uint32_t hz = res.z, hw = res.w;
+        const uint32_t lsig = slot_lsig(res.x, res.y);
+#else
+        // The matching lane writes the child summary and a FOUND mark, the
+        // lane of the bucket's last slot a TAIL mark when that slot is free
+        // (the probe run ends in this bucket).  Parent ids and word ids never
+        // equal the marks.
 #pragma unroll
         for (uint32_t r = 0; r < 4; ++r) {
             const bool m = (sl[r].x & ID_MASK) == rp[r] && (sl[r].y & WID_MASK) == rw[r];
             if (m) {
-                L.q[qn + 16 * r + qd].x = sl[r].z;
-                L.q[qn + 16 * r + qd].y = sl[r].w;
-                L.q[qn + 16 * r + qd].z = Q_FOUND | slot_lsig(sl[r].x, sl[r].y);
+                L.q[qn + q_of(r)].x = sl[r].z;
+                L.q[qn + q_of(r)].y = sl[r].w;
+                L.q[qn + q_of(r)].z = Q_FOUND | slot_lsig(sl[r].x, sl[r].y);
             }
         }
         // The last slot's lane writes the word field in every round, under one
@@ -769,11 +864,9 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         // word into a place above the popped ones: when k < 64, qn is 0 after
         // the pop and qn + p < 64 is unused stack; when k = 64 every quad has
         // a probe.
-        uint32_t qs_now = qs;   // (compared here: the hoisted lane mask would be one more spilled pair)
-        asm volatile("" : "+v"(qs_now));
         if (qs_now == 3) {
 #pragma unroll
-            for (uint32_t r = 0; r < 4; ++r) L.q[qn + 16 * r + qd].w = sl[r].x == SLOT_EMPTY ? Q_TAIL : rw[r];
+            for (uint32_t r = 0; r < 4; ++r) L.q[qn + q_of(r)].w = sl[r].x == SLOT_EMPTY ? Q_TAIL : rw[r];
         }
         const uint4 res = L.q[idx];
         // a row already longer than K goes to the generic path whole: its
@@ -784,6 +877,8 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         const bool cont = live & !found & (res.w != Q_TAIL) & (disp < maxp);
         // the found child's summary (bits of the slot's child and hash fields)
         const uint32_t hz = res.x, hw = res.y;
+        const uint32_t lsig = res.z;   // (the mark's bits lie above the signature's)
+#endif
         const uint32_t child = hz & ID_MASK, hterm = hw & ID_MASK;
         const bool n_topic = (hz & B_TOPIC) != 0, n_plus = (hz & B_PLUS) != 0;
         const bool n_hterm = (hw & B_HTERM) != 0, n_hash = (hw & B_HASH) != 0;
@@ -811,7 +906,7 @@ __device__ __forceinline__ void match_tile(const MatchArgs& a, LT& L, uint32_t t
         const uint64_t kA = key ^ ((uint64_t)(at_end ? (redigit ? 5u : 0u) : dig_H(cls)) << (at_end ? sp : sh));
         // a literal word whose signature bit is clear has no edge here
         // (and, for a node without a '#' child, its 30-bit signature)
-        const bool lit = (id != W_UNKNOWN) & (id != W_PLUS) & (((res.z >> lsig_pos(id)) & 1u) != 0) &
+        const bool lit = (id != W_UNKNOWN) & (id != W_PLUS) & (((lsig >> lsig_pos(id)) & 1u) != 0) &
                          (n_hash | (((hw >> lext_pos(id)) & 1u) != 0));
         const bool pL = found & !at_end & (id == W_HASH ? n_hash : lit);
         const bool pP = found & !at_end & n_plus;
@@ -4351,8 +4446,10 @@ static hipError_t launch_match_t(const MatchArgs& a, hipStream_t s, hipEvent_t e
 // last direct launch)
 hipError_t launch_match(const MatchArgs& a, hipStream_t s, hipEvent_t ev_a, hipEvent_t ev_b, bool checked,
                         unsigned ev_flags) {
-    // the edge hash is read with 32-bit-offset buffer loads unless it exceeds 4 GiB
-    const bool big = (uint64_t)a.nslots * sizeof(Slot) > 0xFFFFFFFFull;
+    // the edge hash is read with 32-bit-offset buffer loads unless it exceeds
+    // 4 GiB less a bucket: the walk's lanes without a probe read at OFF_NONE,
+    // which has to lie past the table (nslots * 16 + 64 <= 2^32)
+    const bool big = (uint64_t)a.nslots * sizeof(Slot) > (uint64_t)OFF_NONE;
     hipError_t e;
     if (checked) e = big ? launch_match_t<true, true>(a, s, ev_a, ev_b, ev_flags)
                          : launch_match_t<true, false>(a, s, ev_a, ev_b, ev_flags);
