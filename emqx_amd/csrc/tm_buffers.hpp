@@ -1,5 +1,6 @@
 // The owning types of everything the host code gets from the HIP runtime by
-// hand: a device block, a pinned host block, an event.  Each is move-only,
+// hand: a device block, a pinned host block, the two as a mirrored pair, an
+// event.  Each is move-only,
 // grows only, and gives its block back in reset() and in its destructor (the
 // runtime's return code ignored there: nothing can be done about it).  A
 // failed runtime call leaves its text in etm::error_buf() and returns TM_EIO.
@@ -7,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <utility>
 
 #include "../../include/emqx_tm.h"
@@ -111,6 +113,38 @@ using PortableBuf = PinBuf<T, hipHostMallocPortable>;
 // pinned bytes the device writes directly (tm_export_host): coherent, so a
 // kernel's stores are visible to the host once its completion is
 using CoherentBuf = PinBuf<uint8_t, hipHostMallocCoherent | hipHostMallocMapped, 4096>;
+
+// A device block and its pinned mirror: an array that crosses the bus, as a
+// result read back (fetch) or an input sent up (stage).  The two sides, the
+// copy's length and the pointer a caller is handed are kept in agreement here.
+// The copies are enqueued on the caller's stream and never waited for.
+template <class T>
+struct Mirror {
+    DevBuf<T> d;
+    PinBuf<T> h;
+
+    // the device side only, never empty: a length of 0 still yields a block
+    int reserve(size_t n) { return d.reserve(std::max<size_t>(n, 1)); }
+    // the pinned side sized for n elements (never empty either) and the
+    // device's first n copied into it; a call that never fetches pins nothing
+    int fetch(size_t n, hipStream_t s) {
+        if (int rc = h.reserve(std::max<size_t>(n, 1))) return rc;
+        if (n) BUF_HIP(hipMemcpyAsync(h.p, d.p, n * sizeof(T), hipMemcpyDeviceToHost, s));
+        return TM_OK;
+    }
+    // both sides sized for n elements, src[0..n) copied to the device through
+    // the pinned side
+    int stage(const T* src, size_t n, hipStream_t s) {
+        if (int rc = reserve(n)) return rc;
+        if (int rc = h.reserve(std::max<size_t>(n, 1))) return rc;
+        if (n) {
+            memcpy(h.p, src, n * sizeof(T));
+            BUF_HIP(hipMemcpyAsync(d.p, h.p, n * sizeof(T), hipMemcpyHostToDevice, s));
+        }
+        return TM_OK;
+    }
+    const T* view(bool device) const { return device ? d.p : h.p; }
+};
 
 // An event, created by the first create() with that call's flags.
 struct Event {

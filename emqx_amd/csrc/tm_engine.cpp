@@ -706,38 +706,18 @@ int tm_subscriber_down(tm_engine* e, uint32_t subscriber, uint32_t node_dest, ui
 int tm_batch_dispatch(tm_engine* e, tm_batch* b, uint32_t flags, tm_deliveries* out) {
     if (!e || !b || !out) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;   // host-only engine
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_dispatch(b, flags, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_dispatch(b, flags, out); });
 }
 
 int tm_batch_inboxes(tm_engine* e, tm_batch* b, uint32_t flags, tm_inboxes* out) {
     // the arguments are checked first, so a host-only engine reports them too
     if (!e) return TM_EINVAL;
-    if (!out) {
-        snprintf(last_error(), 512, "tm_batch_inboxes: out is NULL");
-        return TM_EINVAL;
-    }
-    if (flags & ~TM_INBOX_DEVICE) {
-        snprintf(last_error(), 512, "tm_batch_inboxes: unknown flag");
-        return TM_EINVAL;
-    }
+    if (!out) return einval("tm_batch_inboxes: out is NULL");
+    if (flags & ~TM_INBOX_DEVICE) return einval("tm_batch_inboxes: unknown flag");
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_inboxes(b, flags, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_inboxes(b, flags, out); });
 }
 
 uint32_t tm_inbox_tile(void) { return INBOX_TILE; }
@@ -750,9 +730,7 @@ static int subopts_check(const char* fn, const tm_subopts* o, uint32_t mask) {
     else if ((mask & TM_SUBOPT_RAP) && o->rap > 1) bad = "rap > 1";
     else if ((mask & TM_SUBOPT_RH) && o->rh > 2) bad = "rh > 2";
     else if ((mask & TM_SUBOPT_SUBID) && o->subid > TM_SUBID_MAX) bad = "subid above 268435455";
-    if (!bad) return TM_OK;
-    snprintf(last_error(), 512, "%s: %s", fn, bad);
-    return TM_EINVAL;
+    return bad ? einval("%s: %s", fn, bad) : TM_OK;
 }
 static constexpr uint32_t SUBOPT_ALL = TM_SUBOPT_QOS | TM_SUBOPT_NL | TM_SUBOPT_RAP | TM_SUBOPT_RH | TM_SUBOPT_SUBID;
 
@@ -785,14 +763,8 @@ int tm_shared_subscribe_opts(tm_engine* e, const uint8_t* topic, size_t len, uin
 int tm_set_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, uint32_t mask,
                    const tm_subopts* opts) {
     if (!e || (!topic && len)) return TM_EINVAL;
-    if (mask & ~SUBOPT_ALL) {
-        snprintf(last_error(), 512, "tm_set_subopts: unknown mask bit");
-        return TM_EINVAL;
-    }
-    if (!opts) {
-        snprintf(last_error(), 512, "tm_set_subopts: opts is NULL");
-        return TM_EINVAL;
-    }
+    if (mask & ~SUBOPT_ALL) return einval("tm_set_subopts: unknown mask bit");
+    if (!opts) return einval("tm_set_subopts: opts is NULL");
     if (int rc = subopts_check("tm_set_subopts", opts, mask)) return rc;
     std::lock_guard<std::recursive_mutex> g(e->mu);
     try {
@@ -804,10 +776,7 @@ int tm_set_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subs
 
 int tm_get_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subscriber, tm_subopts* out) {
     if (!e || (!topic && len)) return TM_EINVAL;
-    if (!out) {
-        snprintf(last_error(), 512, "tm_get_subopts: out is NULL");
-        return TM_EINVAL;
-    }
+    if (!out) return einval("tm_get_subopts: out is NULL");
     std::lock_guard<std::recursive_mutex> g(e->mu);
     try {
         tm_subopts* o;
@@ -822,25 +791,13 @@ int tm_get_subopts(tm_engine* e, const uint8_t* topic, size_t len, uint32_t subs
 int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_session_inboxes* out) {
     // the arguments are checked first, so a host-only engine reports them too
     if (!e) return TM_EINVAL;
-    if (!out || !opts) {
-        snprintf(last_error(), 512, "tm_batch_deliver: %s is NULL", out ? "opts" : "out");
-        return TM_EINVAL;
-    }
-    if (opts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS)) {
-        snprintf(last_error(), 512, "tm_batch_deliver: unknown flag");
-        return TM_EINVAL;
-    }
+    if (!out || !opts) return einval("tm_batch_deliver: %s is NULL", out ? "opts" : "out");
+    if (opts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS))
+        return einval("tm_batch_deliver: unknown flag");
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_deliver(b, opts, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_deliver(b, opts, out); });
 }
 
 // one tm_session_state of tm_window_opts; which = its index, -1 for defaults
@@ -850,64 +807,38 @@ static int session_check(const tm_session_state* s, long which) {
     else if (s->flags & ~(TM_SESS_DISCONNECTED | TM_SESS_STORE_QOS0 | TM_SESS_HOST)) bad = "unknown session flag";
     else if (s->mqueue_max && s->mqueue_len > s->mqueue_max) bad = "mqueue_len above mqueue_max";
     if (!bad) return TM_OK;
-    if (which < 0) snprintf(last_error(), 512, "tm_batch_window: defaults: %s", bad);
-    else snprintf(last_error(), 512, "tm_batch_window: sessions[%ld] (subscriber %u): %s", which, s->subscriber, bad);
-    return TM_EINVAL;
+    if (which < 0) return einval("tm_batch_window: defaults: %s", bad);
+    return einval("tm_batch_window: sessions[%ld] (subscriber %u): %s", which, s->subscriber, bad);
 }
 
 int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
                     tm_session_window* out) {
     // the arguments are checked first, so a host-only engine reports them too
     if (!e) return TM_EINVAL;
-    if (!out || !dopts || !wopts) {
-        snprintf(last_error(), 512, "tm_batch_window: %s is NULL", !out ? "out" : !dopts ? "dopts" : "wopts");
-        return TM_EINVAL;
-    }
-    if (dopts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS)) {
-        snprintf(last_error(), 512, "tm_batch_window: unknown deliver flag");
-        return TM_EINVAL;
-    }
-    if (wopts->flags & ~TM_WINDOW_DEVICE) {
-        snprintf(last_error(), 512, "tm_batch_window: unknown window flag");
-        return TM_EINVAL;
-    }
-    if (wopts->n_sessions && !wopts->sessions) {
-        snprintf(last_error(), 512, "tm_batch_window: sessions is NULL with n_sessions = %u", wopts->n_sessions);
-        return TM_EINVAL;
-    }
+    if (!out || !dopts || !wopts)
+        return einval("tm_batch_window: %s is NULL", !out ? "out" : !dopts ? "dopts" : "wopts");
+    if (dopts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS))
+        return einval("tm_batch_window: unknown deliver flag");
+    if (wopts->flags & ~TM_WINDOW_DEVICE) return einval("tm_batch_window: unknown window flag");
+    if (wopts->n_sessions && !wopts->sessions)
+        return einval("tm_batch_window: sessions is NULL with n_sessions = %u", wopts->n_sessions);
     if (int rc = session_check(&wopts->defaults, -1)) return rc;
     for (uint32_t i = 0; i < wopts->n_sessions; ++i) {
         if (int rc = session_check(&wopts->sessions[i], (long)i)) return rc;
-        if (i && wopts->sessions[i].subscriber <= wopts->sessions[i - 1].subscriber) {
-            snprintf(last_error(), 512, "tm_batch_window: sessions[%u] (subscriber %u) not above sessions[%u] (%u)", i,
-                     wopts->sessions[i].subscriber, i - 1, wopts->sessions[i - 1].subscriber);
-            return TM_EINVAL;
-        }
+        if (i && wopts->sessions[i].subscriber <= wopts->sessions[i - 1].subscriber)
+            return einval("tm_batch_window: sessions[%u] (subscriber %u) not above sessions[%u] (%u)", i,
+                          wopts->sessions[i].subscriber, i - 1, wopts->sessions[i - 1].subscriber);
     }
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_window(b, dopts, wopts, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_window(b, dopts, wopts, out); });
 }
 
 int tm_batch_routes(tm_engine* e, tm_batch* b, tm_routes* out) {
     if (!e || !b || !out) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;   // host-only engine
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_routes(b, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_routes(b, out); });
 }
 
 int tm_match_routes_batch(tm_engine* e, const uint8_t* topics, const uint64_t* offsets, uint32_t n, tm_routes* out) {

@@ -35,6 +35,7 @@
 #include <algorithm>
 #include <cctype>
 #include <atomic>
+#include <cstdarg>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -70,6 +71,15 @@ namespace etm_host {
 
 // text of the last TM_EIO on this thread (one buffer for every module: etm::error_buf)
 inline char* last_error() { return error_buf(); }
+
+// TM_EINVAL, its reason left for tm_last_error()
+__attribute__((format(printf, 1, 2))) inline int einval(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(last_error(), 512, fmt, ap);
+    va_end(ap);
+    return TM_EINVAL;
+}
 
 // word hash (tm_internal.hpp hw_*; the device tokeniser computes the same)
 inline uint64_t hash_word(const uint8_t* p, size_t n, uint32_t seed = HW_SEED) {
@@ -397,23 +407,30 @@ struct tm_batch {
 
     // per-entry counts scanned into per-row totals (tm_batch_routes,
     // tm_batch_dispatch_shared): counts, their exclusive scan, the scan's
-    // block sums, the rows' offsets and the grand total
+    // block sums, the rows' offsets and the grand total (both read back)
     struct EntryScan {
-        DevBuf<uint32_t> count, eoff, bsums, row, total;
-        // sized for m match entries of nn rows; sa: the arguments of the scan over them
-        int reserve(uint32_t m, size_t nn, ScanArgs& sa) {
+        DevBuf<uint32_t> count, eoff, bsums;
+        Mirror<uint32_t> row, total;
+        uint32_t m = 0;   // the entries reserve() sized it for
+        // sized for m match entries of n rows
+        int reserve(uint32_t m_, uint32_t n) {
             int rc;
-            if ((rc = count.reserve((size_t)m + 1))) return rc;
-            if ((rc = eoff.reserve((size_t)m + 1))) return rc;
-            if ((rc = row.reserve(nn + 1))) return rc;
-            if ((rc = bsums.reserve((size_t)scan_block_count(m) + 1))) return rc;
-            if ((rc = total.reserve(1))) return rc;
-            sa = ScanArgs{};
+            if ((rc = count.reserve((size_t)m_ + 1))) return rc;
+            if ((rc = eoff.reserve((size_t)m_ + 1))) return rc;
+            if ((rc = row.reserve((size_t)n + 1))) return rc;
+            if ((rc = bsums.reserve((size_t)scan_block_count(m_) + 1))) return rc;
+            m = m_;
+            return total.reserve(1);
+        }
+        // the counts scanned into eoff and the total; no entries: the total zeroed
+        hipError_t scan(hipStream_t s) {
+            if (!m) return hipMemsetAsync(total.d.p, 0, 4, s);
+            ScanArgs sa{};
             sa.count = count.p;
             sa.row_off = eoff.p;
             sa.block_sums = bsums.p;
             sa.n = m;
-            return TM_OK;
+            return launch_scan(sa, s, total.d.p);
         }
     };
 
@@ -494,53 +511,48 @@ struct tm_batch {
     // route resolution (tm_batch_routes)
     struct Routes {
         EntryScan es;   // over match entries
-        DevBuf<uint32_t> d_rfid, d_rdest;
-        PinBuf<uint32_t> h_rtotal, h_rrow, h_rfid, h_rdest;
+        Mirror<uint32_t> fid, dest;
     } rt;
 
     // subscriber fan-out (tm_batch_dispatch)
     struct Fanout {
-        DevBuf<uint64_t> d_moff, d_fbsums, d_ftotal, d_drow, d_ftile;
+        DevBuf<uint64_t> d_fbsums, d_ftile;
         DevBuf<uint32_t> d_moff32;
         DevBuf<uint8_t> d_fbig;
         DevBuf<uint32_t> d_dcount;   // TM_DISPATCH_ROWS: deliveries of each row
-        DevBuf<uint64_t> d_fmeta;    // TM_DISPATCH_ROWS: staging regions (vb, rtop)
-        PinBuf<uint64_t> h_fmeta;
-        PinBuf<uint64_t> h_ftotal, h_drow, h_moff;
-        DevBuf<uint32_t> d_fout;
-        PinBuf<uint32_t> h_fout;
+        Mirror<uint64_t> meta;       // TM_DISPATCH_ROWS: staging regions (vb, rtop)
+        Mirror<uint64_t> total, row, moff;
+        Mirror<uint32_t> out;
         Event fev0, fev1;
     } fan;
 
     // shared-subscription dispatch (tm_batch_dispatch_shared)
     struct Shared {
         EntryScan es;
-        DevBuf<uint32_t> d_gkeys, d_gfid, d_ggrp, d_gsub;
-        DevBuf<unsigned long long> d_gtot64;
-        PinBuf<unsigned long long> h_gtot64;
-        PinBuf<uint32_t> h_gkeys, h_grow, h_gfid, h_ggrp, h_gsub;
+        Mirror<uint32_t> keys, fid, grp, sub;
+        Mirror<unsigned long long> tot64;
         Event gev[4];   // around count + scan + rows, around the pick
         DevBuf<uint32_t> d_gent;   // armed inboxes: the match entry of every pick
     } sh;
 
     // per-subscriber inboxes (tm_batch_inboxes): the sort's second key array and
-    // both payload arrays (the first key array is fan.d_fout; d_mkey when armed), the pass table,
-    // the finish's head counts, and the result with its pinned mirror
+    // both payload arrays (the first key array is fan.out; d_mkey when armed), the pass table,
+    // the finish's head counts, and the result
     struct Inbox {
         DevBuf<uint32_t> d_val0, d_key1, d_val1, d_pubof, d_hist, d_hbs, d_hcount, d_hcbs, d_R;
-        DevBuf<uint32_t> d_pub, d_fid, d_sub, d_off;
-        PinBuf<uint32_t> h_R, h_pub, h_fid, h_sub, h_off;
+        PinBuf<uint32_t> h_R;   // [*d_R, *d_merr]: two blocks' words in one, so not a Mirror
+        Mirror<uint32_t> pub, fid, sub, off;
         Event iev0, iev1;   // around the inbox kernels
         // armed batch (tm_batch_shared_mode): the merged list L' as the sort's
         // first input (d_mkey, d_mval), one record per merged position, the
         // groups of the result and the merge's error count
-        DevBuf<uint32_t> d_mkey, d_mval, d_grp, d_merr;
+        DevBuf<uint32_t> d_mkey, d_mval, d_merr;
         DevBuf<uint4> d_mrec;
-        PinBuf<uint32_t> h_grp;
-        const uint32_t* key0 = nullptr;   // the sort's first key array of the last call (fan.d_fout or d_mkey)
+        Mirror<uint32_t> grp;
+        const uint32_t* key0 = nullptr;   // the sort's first key array of the last call (fan.out or d_mkey)
         bool merged = false;         // the last inboxes / deliver / window call ran armed
-        bool grp_host = false;       // h_grp holds the last call's groups
-        const uint32_t* d_groups = nullptr;   // the last call's groups on the device (after deliver's compaction: dlv.d_grp)
+        bool grp_host = false;       // groups' pinned side holds the last call's groups
+        Mirror<uint32_t>* groups = nullptr;   // the last call's groups (grp; after deliver's compaction: dlv.grp)
         uint32_t n_groups = 0;       // their count
     } inbox;
 
@@ -553,34 +565,28 @@ struct tm_batch {
     } shmode;
 
     // what the session sends (tm_batch_deliver): the per-call inputs (from,
-    // msg) and their pinned staging, the per-inbox and per-delivery scratch,
-    // the per-tile counts of what is left, and the result with its pinned mirror
+    // msg_in), the per-inbox and per-delivery scratch, the per-tile counts of
+    // what is left, the totals and the result
     struct Deliver {
-        DevBuf<uint32_t> d_from, d_first, d_esubid, d_kcount, d_kbs, d_ncount, d_nbs, d_tot;
-        DevBuf<uint8_t> d_min, d_own, d_emsg;
+        DevBuf<uint32_t> d_first, d_esubid, d_kcount, d_kbs, d_ncount, d_nbs;
+        DevBuf<uint8_t> d_own, d_emsg;
         DevBuf<uint2> d_rng;
-        DevBuf<uint32_t> d_sub, d_off, d_pub, d_fid, d_subid;
-        DevBuf<uint32_t> d_grp;   // armed batch: the groups after the compaction
-        DevBuf<uint8_t> d_msg;
-        PinBuf<uint32_t> h_from, h_tot, h_sub, h_off, h_pub, h_fid, h_subid;
-        PinBuf<uint8_t> h_min, h_msg;
+        Mirror<uint32_t> from, tot, sub, off, pub, fid, subid;
+        Mirror<uint32_t> grp;   // armed batch: the groups after the compaction
+        Mirror<uint8_t> msg_in, msg;
         Event dev0, dev1;   // around the delivery kernels
     } dlv;
 
-    // the session's send window (tm_batch_window): the uploaded session table
-    // and its pinned staging, the head bits, per-inbox and per-wave scratch, and
-    // the result with its pinned mirror
+    // the session's send window (tm_batch_window): the uploaded session table,
+    // the head bits, per-inbox and per-wave scratch, the totals and the result
     struct Window {
-        DevBuf<uint32_t> d_sess, d_heads, d_hbase, d_wcount, d_wbs, d_tot, d_wdisp;
-        DevBuf<uint4> d_st, d_rec;
-        DevBuf<uint8_t> d_disp;
-        DevBuf<uint16_t> d_pid;
-        DevBuf<unsigned long long> d_totals;
-        PinBuf<uint32_t> h_sess, h_tot;
-        PinBuf<uint4> h_rec;
-        PinBuf<uint8_t> h_disp;
-        PinBuf<uint16_t> h_pid;
-        PinBuf<unsigned long long> h_totals;
+        DevBuf<uint32_t> d_heads, d_hbase, d_wcount, d_wbs, d_wdisp;
+        DevBuf<uint4> d_st;
+        Mirror<uint32_t> sess, tot;
+        Mirror<uint4> rec;
+        Mirror<uint8_t> disp;
+        Mirror<uint16_t> pid;
+        Mirror<unsigned long long> totals;
         Event wev0, wev1;   // around the window kernels
     } win;
 
@@ -2506,3 +2512,16 @@ struct tm_engine {
     int rules_match_split(const uint8_t* names, const uint64_t* noffs, uint32_t n, const uint8_t* rules,
                           const uint64_t* roffs, uint32_t r, bool dollar_rule, uint32_t* bits);
 };
+
+// The tail of a batch's entry point, behind its argument checks: under the
+// engine lock and on the batch's replica, body(); an exception is TM_ENOMEM.
+template <class F>
+int on_batch(tm_engine* e, tm_batch* b, F body) {
+    std::lock_guard<std::recursive_mutex> g(e->mu);
+    if (int rc = e->use(b->rep)) return rc;
+    try {
+        return body();
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}

@@ -82,50 +82,39 @@ int tm_engine::batch_routes(tm_batch* b, tm_routes* out) {
     if ((rc = ensure_dense(b))) return rc;
     if ((rc = sync_routes(R))) return rc;
     const uint32_t n = b->n;
-    const size_t nn = std::max<size_t>(n, 1);
     const uint64_t m64 = b->total;   // match entries (< 2^32: u32 result CSR)
     if (m64 > 0xFFFFFFF0ull) return TM_EOVERFLOW;
     const uint32_t m = (uint32_t)m64;
-    ScanArgs sa{};
-    if ((rc = b->rt.es.reserve(m, nn, sa))) return rc;
-    if ((rc = b->rt.h_rtotal.reserve(1))) return rc;
+    tm_batch::Routes& rt = b->rt;
+    if ((rc = rt.es.reserve(m, n))) return rc;
     RouteArgs r{};
     r.row_off = b->dcsr.d_rowoff.p; r.ids = b->dcsr.d_ids.p; r.n = n; r.m = m;
     r.roff = R.tab.d_roff.p; r.rdest = R.tab.d_rdest.p; r.nnodes = (uint32_t)(h_roff.size() - 1);
-    r.ecount = b->rt.es.count.p; r.eoff = b->rt.es.eoff.p; r.bsums = b->rt.es.bsums.p; r.total = b->rt.es.total.p;
-    r.r_rowoff = b->rt.es.row.p;
+    r.ecount = rt.es.count.p; r.eoff = rt.es.eoff.p; r.bsums = rt.es.bsums.p; r.total = rt.es.total.d.p;
+    r.r_rowoff = rt.es.row.d.p;
     HIP_OK(launch_route_count(r, stream));
-    if (m) {
-        HIP_OK(launch_scan(sa, stream, b->rt.es.total.p));
-    } else {
-        HIP_OK(hipMemsetAsync(b->rt.es.total.p, 0, 4, stream));
-    }
+    HIP_OK(rt.es.scan(stream));
     HIP_OK(launch_route_rows(r, stream));
-    HIP_OK(hipMemcpyAsync(b->rt.h_rtotal.p, b->rt.es.total.p, 4, hipMemcpyDeviceToHost, stream));
+    if ((rc = rt.es.total.fetch(1, stream))) return rc;
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->rt.h_rtotal.p[0];
-    if ((rc = b->rt.d_rfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
-    if ((rc = b->rt.d_rdest.reserve(std::max<uint64_t>(total, 1)))) return rc;
-    r.out_fid = b->rt.d_rfid.p; r.out_dest = b->rt.d_rdest.p; r.cap = total;
+    const uint64_t total = rt.es.total.h.p[0];
+    if ((rc = rt.fid.reserve(total))) return rc;
+    if ((rc = rt.dest.reserve(total))) return rc;
+    r.out_fid = rt.fid.d.p; r.out_dest = rt.dest.d.p; r.cap = total;
     HIP_OK(launch_route_fill(r, stream));
-    if ((rc = b->rt.h_rrow.reserve(nn + 1))) return rc;
-    if ((rc = b->rt.h_rfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
-    if ((rc = b->rt.h_rdest.reserve(std::max<uint64_t>(total, 1)))) return rc;
-    HIP_OK(hipMemcpyAsync(b->rt.h_rrow.p, b->rt.es.row.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
-    if (total) {
-        HIP_OK(hipMemcpyAsync(b->rt.h_rfid.p, b->rt.d_rfid.p, total * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(b->rt.h_rdest.p, b->rt.d_rdest.p, total * 4, hipMemcpyDeviceToHost, stream));
-    }
+    if ((rc = rt.es.row.fetch((size_t)n + 1, stream))) return rc;
+    if ((rc = rt.fid.fetch(total, stream))) return rc;
+    if ((rc = rt.dest.fetch(total, stream))) return rc;
     HIP_OK(hipStreamSynchronize(stream));
-    if (b->rt.h_rrow.p[n] != total) {
-        snprintf(last_error(), 512, "inconsistent route CSR: %u vs %llu", b->rt.h_rrow.p[n], (unsigned long long)total);
+    if (rt.es.row.h.p[n] != total) {
+        snprintf(last_error(), 512, "inconsistent route CSR: %u vs %llu", rt.es.row.h.p[n], (unsigned long long)total);
         return TM_EIO;
     }
     out->n_topics = n;
     out->n_routes = total;
-    out->row_offsets = b->rt.h_rrow.p;
-    out->filter_ids = b->rt.h_rfid.p;
-    out->dests = b->rt.h_rdest.p;
+    out->row_offsets = rt.es.row.h.p;
+    out->filter_ids = rt.fid.h.p;
+    out->dests = rt.dest.h.p;
     return TM_OK;
 }
 
@@ -321,19 +310,17 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out, b
     if (!rows && (rc = ensure_dense(b))) return rc;
     if ((rc = sync_subs(R))) return rc;
     const uint32_t n = b->n;
+    tm_batch::Fanout& fan = b->fan;
     FanArgs fa{};
     uint64_t nm = b->total;
     if (rows) {   // the walk's staging regions as one virtual entry space (FanArgs)
         const uint64_t cap = std::min<uint64_t>(b->walk.d_sfids.cap, MAX_RESULT);
         fa.nreg = b->one_region ? 1u : TICKET_GROUPS;
         fa.rcap = region_cap(cap, b->one_region);
-        // [vb: TICKET_GROUPS + 1 | rtop: TICKET_GROUPS] in pinned memory -> HBM
+        // [vb: TICKET_GROUPS + 1 | rtop: TICKET_GROUPS] -> HBM
         constexpr size_t FM = 2 * TICKET_GROUPS + 1;
-        if ((rc = b->fan.h_fmeta.reserve(FM))) return rc;
-        if ((rc = b->fan.d_fmeta.reserve(FM))) return rc;
-        uint64_t* vb = b->fan.h_fmeta.p;
-        uint64_t* rtop = b->fan.h_fmeta.p + TICKET_GROUPS + 1;
-        std::fill(b->fan.h_fmeta.p, b->fan.h_fmeta.p + FM, 0ull);
+        uint64_t fm[FM] = {};
+        uint64_t *vb = fm, *rtop = fm + TICKET_GROUPS + 1;
         uint64_t v = 0, staged = 0;
         for (uint32_t g = 0; g < fa.nreg; ++g) {
             vb[g] = v;
@@ -342,101 +329,82 @@ int tm_engine::batch_dispatch(tm_batch* b, uint32_t flags, tm_deliveries* out, b
             v += (rtop[g] + 15) & ~15ull;
         }
         for (uint32_t g = fa.nreg; g <= TICKET_GROUPS; ++g) vb[g] = v;
-        HIP_OK(hipMemcpyAsync(b->fan.d_fmeta.p, b->fan.h_fmeta.p, FM * 8, hipMemcpyHostToDevice, stream));
-        fa.vb = b->fan.d_fmeta.p;
-        fa.rtop = b->fan.d_fmeta.p + TICKET_GROUPS + 1;
+        if ((rc = fan.meta.stage(fm, FM, stream))) return rc;
+        fa.vb = fan.meta.d.p;
+        fa.rtop = fan.meta.d.p + TICKET_GROUPS + 1;
         if (staged != b->total) {
             snprintf(last_error(), 512, "staging holds %llu entries, the walk matched %llu",
                      (unsigned long long)staged, (unsigned long long)b->total);
             return TM_EIO;
         }
         nm = v;
-        if ((rc = b->fan.d_dcount.reserve(std::max<size_t>(n, 1)))) return rc;
+        if ((rc = fan.d_dcount.reserve(std::max<size_t>(n, 1)))) return rc;
         fa.rcount = b->walk.d_count;
         fa.rsrc = b->walk.d_src;
-        fa.dcount = b->fan.d_dcount.p;
+        fa.dcount = fan.d_dcount.p;
     }
     const uint32_t nb = (uint32_t)((nm + 1 + fan_scan_tile() - 1) / fan_scan_tile());
-    if ((rc = b->fan.d_moff.reserve(nm + 1))) return rc;
-    if ((rc = b->fan.d_fbsums.reserve(nb))) return rc;
-    if ((rc = b->fan.d_moff32.reserve(nm + 1))) return rc;
-    if ((rc = b->fan.d_fbig.reserve(nb))) return rc;
-    if ((rc = b->fan.d_ftotal.reserve(1))) return rc;
-    if ((rc = b->fan.d_drow.reserve((size_t)n + 1))) return rc;
-    if ((rc = b->fan.h_ftotal.reserve(1))) return rc;
+    if ((rc = fan.moff.reserve(nm + 1))) return rc;
+    if ((rc = fan.d_fbsums.reserve(nb))) return rc;
+    if ((rc = fan.d_moff32.reserve(nm + 1))) return rc;
+    if ((rc = fan.d_fbig.reserve(nb))) return rc;
+    if ((rc = fan.total.reserve(1))) return rc;
+    if ((rc = fan.row.reserve((size_t)n + 1))) return rc;
     const bool counts_only = flags & TM_DISPATCH_COUNT_ONLY;
-    if (!b->fan.fev0.e) {
-        if ((rc = b->fan.fev0.create())) return rc;
-        if ((rc = b->fan.fev1.create())) return rc;
+    if (!fan.fev0.e) {
+        if ((rc = fan.fev0.create())) return rc;
+        if ((rc = fan.fev1.create())) return rc;
     }
     fa.row_off = b->dcsr.d_rowoff.p; fa.ids = rows ? b->walk.d_sfids.p : b->dcsr.d_ids.p; fa.n = n; fa.n_matches = nm;
     fa.soff = R.tab.d_soff.p; fa.scnt = R.tab.d_scnt.p; fa.sone = R.tab.d_sone.p; fa.subs = R.tab.d_subs.p;
     fa.nnodes = subs_nn;
-    fa.moff = b->fan.d_moff.p; fa.moff32 = b->fan.d_moff32.p; fa.bbig = b->fan.d_fbig.p; fa.bsums = b->fan.d_fbsums.p;
-    fa.big_limit = fan_big_limit; fa.d_total = b->fan.d_ftotal.p; fa.drow = b->fan.d_drow.p;
+    fa.moff = fan.moff.d.p; fa.moff32 = fan.d_moff32.p; fa.bbig = fan.d_fbig.p; fa.bsums = fan.d_fbsums.p;
+    fa.big_limit = fan_big_limit; fa.d_total = fan.total.d.p; fa.drow = fan.row.d.p;
     HIP_OK(launch_fan_scan(fa, stream));
-    HIP_OK(hipMemcpyAsync(b->fan.h_ftotal.p, b->fan.d_ftotal.p, 8, hipMemcpyDeviceToHost, stream));
+    if ((rc = fan.total.fetch(1, stream))) return rc;
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->fan.h_ftotal.p[0];
+    const uint64_t total = fan.total.h.p[0];
     float fill_ms = 0.f;
     if (!counts_only) {
-        if ((rc = b->fan.d_fout.reserve(std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = b->fan.d_ftile.reserve((size_t)(total / fan_fill_tile()) + 2))) return rc;
-        fa.out = b->fan.d_fout.p; fa.total = total; fa.tile_j = b->fan.d_ftile.p;
+        if ((rc = fan.out.reserve(total))) return rc;
+        if ((rc = fan.d_ftile.reserve((size_t)(total / fan_fill_tile()) + 2))) return rc;
+        fa.out = fan.out.d.p; fa.total = total; fa.tile_j = fan.d_ftile.p;
         if (entries) {
             if (total > MAX_RESULT) return TM_EOVERFLOW;   // the sort's payload and the inbox offsets are u32
             if ((rc = b->inbox.d_val0.reserve(std::max<uint64_t>(total, 1)))) return rc;
             fa.out_j = b->inbox.d_val0.p;
         }
-        HIP_OK(hipEventRecord(b->fan.fev0.e, stream));
+        HIP_OK(hipEventRecord(fan.fev0.e, stream));
         HIP_OK(launch_fan_fill(fa, stream));
-        HIP_OK(hipEventRecord(b->fan.fev1.e, stream));
+        HIP_OK(hipEventRecord(fan.fev1.e, stream));
     }
     const bool want_moff = flags & TM_DISPATCH_MATCH_OFFSETS;
     if (want_moff) HIP_OK(launch_fan_globalize(fa, stream));   // moff is block-relative until now
-    out->n_topics = n;
-    out->n_matches = b->total;
-    out->n_deliveries = total;
-    out->row_counts = nullptr;
-    if (flags & TM_DISPATCH_DEVICE) {
-        HIP_OK(hipStreamSynchronize(stream));
-        if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fan.fev0.e, b->fan.fev1.e));
-        out->row_offsets = b->fan.d_drow.p;
-        out->match_offsets = want_moff ? b->fan.d_moff.p : nullptr;
-        out->subscribers = counts_only ? nullptr : b->fan.d_fout.p;
-        out->fill_ms = fill_ms;
-        out->row_counts = rows ? b->fan.d_dcount.p : nullptr;
-        return TM_OK;
-    }
-    if ((rc = b->fan.h_drow.reserve((size_t)n + 1))) return rc;
-    HIP_OK(hipMemcpyAsync(b->fan.h_drow.p, b->fan.d_drow.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
-    if (want_moff) {
-        if ((rc = b->fan.h_moff.reserve(nm + 1))) return rc;
-        HIP_OK(hipMemcpyAsync(b->fan.h_moff.p, b->fan.d_moff.p, (nm + 1) * 8, hipMemcpyDeviceToHost, stream));
-    }
-    if (!counts_only) {
-        if ((rc = b->fan.h_fout.reserve(std::max<uint64_t>(total, 1)))) return rc;
-        if (total) HIP_OK(hipMemcpyAsync(b->fan.h_fout.p, b->fan.d_fout.p, total * 4, hipMemcpyDeviceToHost, stream));
+    const bool device = flags & TM_DISPATCH_DEVICE;
+    if (!device) {
+        if ((rc = fan.row.fetch((size_t)n + 1, stream))) return rc;
+        if (want_moff && (rc = fan.moff.fetch(nm + 1, stream))) return rc;
+        if (!counts_only && (rc = fan.out.fetch(total, stream))) return rc;
     }
     HIP_OK(hipStreamSynchronize(stream));
-    if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, b->fan.fev0.e, b->fan.fev1.e));
-    if (b->fan.h_drow.p[n] != total) {
-        snprintf(last_error(), 512, "inconsistent delivery CSR: %llu vs %llu", (unsigned long long)b->fan.h_drow.p[n],
+    if (!counts_only) HIP_OK(hipEventElapsedTime(&fill_ms, fan.fev0.e, fan.fev1.e));
+    if (!device && fan.row.h.p[n] != total) {
+        snprintf(last_error(), 512, "inconsistent delivery CSR: %llu vs %llu", (unsigned long long)fan.row.h.p[n],
                  (unsigned long long)total);
         return TM_EIO;
     }
-    out->row_offsets = b->fan.h_drow.p;
-    out->match_offsets = want_moff ? b->fan.h_moff.p : nullptr;
-    out->subscribers = counts_only ? nullptr : b->fan.h_fout.p;
+    out->n_topics = n;
+    out->n_matches = b->total;
+    out->n_deliveries = total;
+    out->row_offsets = fan.row.view(device);
+    out->match_offsets = want_moff ? fan.moff.view(device) : nullptr;
+    out->subscribers = counts_only ? nullptr : fan.out.view(device);
     out->fill_ms = fill_ms;
+    out->row_counts = rows ? fan.d_dcount.p : nullptr;
     return TM_OK;
 }
 
 int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
-    auto einval = [](const char* msg) {
-        snprintf(last_error(), 512, "%s", msg);
-        return TM_EINVAL;
-    };
     if (!b->done) return einval("tm_batch_inboxes: the batch has not been waited for");
     if (b->dedup) return einval("tm_batch_inboxes: a TM_BATCH_DEDUP batch (an inbox entry names a publish)");
     if (b->total > MAX_RESULT) return TM_EOVERFLOW;
@@ -454,9 +422,9 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     tm_batch::Inbox& ib = b->inbox;
     ib.merged = false;
     ib.grp_host = false;
-    ib.d_groups = nullptr;
+    ib.groups = nullptr;
     ib.n_groups = 0;
-    ib.key0 = b->fan.d_fout.p;
+    ib.key0 = b->fan.out.d.p;
     const uint32_t n = b->n, m = (uint32_t)b->total;
     const uint32_t D0 = (uint32_t)dl.n_deliveries;   // <= MAX_RESULT (batch_dispatch checked)
     uint32_t DS = 0;                                  // shared deliveries
@@ -485,37 +453,37 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     if ((rc = ib.d_R.reserve(1))) return rc;
     if ((rc = ib.h_R.reserve(2))) return rc;
     ib.h_R.p[1] = 0;
-    if ((rc = ib.d_pub.reserve(dd))) return rc;
-    if ((rc = ib.d_fid.reserve(dd))) return rc;
-    if ((rc = ib.d_sub.reserve(rcap))) return rc;
-    if ((rc = ib.d_off.reserve((size_t)rcap + 1))) return rc;
+    if ((rc = ib.pub.reserve(D))) return rc;
+    if ((rc = ib.fid.reserve(D))) return rc;
+    if ((rc = ib.sub.reserve(rcap))) return rc;
+    if ((rc = ib.off.reserve((size_t)rcap + 1))) return rc;
     if ((rc = ib.iev0.create())) return rc;
     if ((rc = ib.iev1.create())) return rc;
     InboxArgs a{};
     a.row_off = b->dcsr.d_rowoff.p; a.ids = b->dcsr.d_ids.p; a.n = n; a.m = m; a.D = D; a.ntiles = ntiles;
     a.passes = passes; a.pub_of = ib.d_pubof.p;
-    a.key0 = b->fan.d_fout.p; a.val0 = ib.d_val0.p; a.key1 = ib.d_key1.p; a.val1 = ib.d_val1.p;
+    a.key0 = b->fan.out.d.p; a.val0 = ib.d_val0.p; a.key1 = ib.d_key1.p; a.val1 = ib.d_val1.p;
     a.hist = ib.d_hist.p; a.hbs = ib.d_hbs.p; a.rcap = rcap; a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
-    a.d_R = ib.d_R.p; a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
-    a.inbox_offsets = ib.d_off.p;
+    a.d_R = ib.d_R.p; a.publishes = ib.pub.d.p; a.filter_ids = ib.fid.d.p; a.subscribers = ib.sub.d.p;
+    a.inbox_offsets = ib.off.d.p;
     MergeArgs ma{};
     if (armed) {
         if ((rc = ib.d_mkey.reserve(dd))) return rc;
         if ((rc = ib.d_mval.reserve(dd))) return rc;
         if ((rc = ib.d_mrec.reserve(dd))) return rc;
-        if ((rc = ib.d_grp.reserve(dd))) return rc;
+        if ((rc = ib.grp.reserve(D))) return rc;
         if ((rc = ib.d_merr.reserve(1))) return rc;
-        ma.fsub = b->fan.d_fout.p; ma.fent = ib.d_val0.p; ma.nd = D0;
-        ma.gsub = b->sh.d_gsub.p; ma.ggrp = b->sh.d_ggrp.p; ma.gent = b->sh.d_gent.p; ma.ns = DS;
-        ma.m = m; ma.moff = b->fan.d_moff.p; ma.eoff = b->sh.es.eoff.p; ma.bsums = b->sh.es.bsums.p;
+        ma.fsub = b->fan.out.d.p; ma.fent = ib.d_val0.p; ma.nd = D0;
+        ma.gsub = b->sh.sub.d.p; ma.ggrp = b->sh.grp.d.p; ma.gent = b->sh.d_gent.p; ma.ns = DS;
+        ma.m = m; ma.moff = b->fan.moff.d.p; ma.eoff = b->sh.es.eoff.p; ma.bsums = b->sh.es.bsums.p;
         ma.pub_of = ib.d_pubof.p; ma.ids = b->dcsr.d_ids.p;
         ma.cap = D; ma.key = ib.d_mkey.p; ma.val = ib.d_mval.p; ma.rec = ib.d_mrec.p;
         ma.err = ib.d_merr.p;
         a.key0 = ib.d_mkey.p; a.val0 = ib.d_mval.p;
-        a.mrec = ib.d_mrec.p; a.groups = ib.d_grp.p;
+        a.mrec = ib.d_mrec.p; a.groups = ib.grp.d.p;
         ib.key0 = ib.d_mkey.p;
         ib.merged = true;
-        ib.d_groups = ib.d_grp.p;
+        ib.groups = &ib.grp;
         ib.n_groups = D;
     }
     uint32_t nsub = 0;
@@ -545,7 +513,7 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
             return TM_EIO;
         }
     } else {
-        HIP_OK(hipMemsetAsync(ib.d_off.p, 0, 4, stream));   // inbox_offsets = {0}
+        HIP_OK(hipMemsetAsync(ib.off.d.p, 0, 4, stream));   // inbox_offsets = {0}
         HIP_OK(hipStreamSynchronize(stream));
     }
     out->n_topics = n;
@@ -553,28 +521,20 @@ int tm_engine::batch_inboxes(tm_batch* b, uint32_t flags, tm_inboxes* out) {
     out->n_deliveries = D;
     out->kernel_ms = ms;
     out->passes = D ? passes : 0;
-    if (flags & TM_INBOX_DEVICE) {
-        out->subscribers = ib.d_sub.p; out->inbox_offsets = ib.d_off.p;
-        out->publishes = ib.d_pub.p; out->filter_ids = ib.d_fid.p;
-        return TM_OK;
+    const bool device = flags & TM_INBOX_DEVICE;
+    if (!device) {
+        if ((rc = ib.off.fetch((size_t)nsub + 1, stream))) return rc;
+        if ((rc = ib.sub.fetch(nsub, stream))) return rc;
+        if ((rc = ib.pub.fetch(D, stream))) return rc;
+        if ((rc = ib.fid.fetch(D, stream))) return rc;
+        HIP_OK(hipStreamSynchronize(stream));
+        if (ib.off.h.p[nsub] != D) {
+            snprintf(last_error(), 512, "inconsistent inbox offsets: %u vs %u", ib.off.h.p[nsub], D);
+            return TM_EIO;
+        }
     }
-    if ((rc = ib.h_sub.reserve(std::max<size_t>(nsub, 1)))) return rc;
-    if ((rc = ib.h_off.reserve((size_t)nsub + 1))) return rc;
-    if ((rc = ib.h_pub.reserve(dd))) return rc;
-    if ((rc = ib.h_fid.reserve(dd))) return rc;
-    HIP_OK(hipMemcpyAsync(ib.h_off.p, ib.d_off.p, ((size_t)nsub + 1) * 4, hipMemcpyDeviceToHost, stream));
-    if (nsub) HIP_OK(hipMemcpyAsync(ib.h_sub.p, ib.d_sub.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, stream));
-    if (D) {
-        HIP_OK(hipMemcpyAsync(ib.h_pub.p, ib.d_pub.p, (size_t)D * 4, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(ib.h_fid.p, ib.d_fid.p, (size_t)D * 4, hipMemcpyDeviceToHost, stream));
-    }
-    HIP_OK(hipStreamSynchronize(stream));
-    if (ib.h_off.p[nsub] != D) {
-        snprintf(last_error(), 512, "inconsistent inbox offsets: %u vs %u", ib.h_off.p[nsub], D);
-        return TM_EIO;
-    }
-    out->subscribers = ib.h_sub.p; out->inbox_offsets = ib.h_off.p;
-    out->publishes = ib.h_pub.p; out->filter_ids = ib.h_fid.p;
+    out->subscribers = ib.sub.view(device); out->inbox_offsets = ib.off.view(device);
+    out->publishes = ib.pub.view(device); out->filter_ids = ib.fid.view(device);
     return TM_OK;
 }
 
@@ -650,19 +610,13 @@ int tm_engine::sync_subopts(Replica& R) {
 }
 
 int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_inboxes* out) {
-    auto einval = [](const char* msg) {
-        snprintf(last_error(), 512, "%s", msg);
-        return TM_EINVAL;
-    };
     if (!b->done) return einval("tm_batch_deliver: the batch has not been waited for");
     if (b->dedup) return einval("tm_batch_deliver: a TM_BATCH_DEDUP batch (a delivery names a publish)");
     const uint32_t n = b->n;
     if (o->msg)
         for (uint32_t i = 0; i < n; ++i)
-            if ((o->msg[i] & ~0xFu) || (o->msg[i] & 3u) == 3u) {
-                snprintf(last_error(), 512, "tm_batch_deliver: msg[%u] = 0x%02x (QoS 3 or bits above 3)", i, o->msg[i]);
-                return TM_EINVAL;
-            }
+            if ((o->msg[i] & ~0xFu) || (o->msg[i] & 3u) == 3u)
+                return einval("tm_batch_deliver: msg[%u] = 0x%02x (QoS 3 or bits above 3)", i, o->msg[i]);
     const bool device = o->flags & TM_DELIVER_DEVICE, want_subids = o->flags & TM_DELIVER_SUBIDS;
     // nothing can drop without a publisher or without a No-Local subscription
     const bool can_drop = o->from && nl_entries > 0;
@@ -677,59 +631,50 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
     const size_t dd = std::max<size_t>(D, 1);
     *out = tm_session_inboxes{};
     out->n_topics = n;
-    if ((rc = dv.d_msg.reserve(dd))) return rc;
-    if ((rc = dv.h_msg.reserve(dd))) return rc;
-    if (want_subids) {
-        if ((rc = dv.d_subid.reserve(dd))) return rc;
-        if ((rc = dv.h_subid.reserve(dd))) return rc;
-    }
+    if ((rc = dv.msg.reserve(D))) return rc;
+    if (want_subids && (rc = dv.subid.reserve(D))) return rc;
     if (!D) {   // no delivery: n_subscribers = 0, inbox_offsets = {0}
         if (device) {
-            out->inbox_offsets = ib.d_off.p;
-            out->subscribers = ib.d_sub.p; out->publishes = ib.d_pub.p; out->filter_ids = ib.d_fid.p;
-            out->msg = dv.d_msg.p; out->subids = want_subids ? dv.d_subid.p : nullptr;
-            return TM_OK;
+            out->inbox_offsets = ib.off.d.p;
+            out->subscribers = ib.sub.d.p; out->publishes = ib.pub.d.p; out->filter_ids = ib.fid.d.p;
+        } else {   // nothing to copy: the pinned sides alone, the offset written here
+            if ((rc = dv.off.fetch(0, stream))) return rc;
+            if ((rc = dv.sub.fetch(0, stream))) return rc;
+            if ((rc = dv.msg.fetch(0, stream))) return rc;
+            if (want_subids && (rc = dv.subid.fetch(0, stream))) return rc;
+            dv.off.h.p[0] = 0;
+            out->inbox_offsets = dv.off.h.p;
+            out->subscribers = out->publishes = out->filter_ids = dv.sub.h.p;
         }
-        if ((rc = dv.h_off.reserve(1))) return rc;
-        if ((rc = dv.h_sub.reserve(1))) return rc;
-        dv.h_off.p[0] = 0;
-        out->inbox_offsets = dv.h_off.p;
-        out->subscribers = out->publishes = out->filter_ids = dv.h_sub.p;
-        out->msg = dv.h_msg.p; out->subids = want_subids ? dv.h_subid.p : nullptr;
+        out->msg = dv.msg.view(device);
+        out->subids = want_subids ? dv.subid.view(device) : nullptr;
         return TM_OK;
     }
     if ((rc = sync_subopts(R))) return rc;
     const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
     if ((rc = dv.d_rng.reserve(nsub))) return rc;
     if ((rc = dv.d_first.reserve(nsub))) return rc;
-    if ((rc = dv.d_tot.reserve(4))) return rc;
-    if ((rc = dv.h_tot.reserve(4))) return rc;
+    if ((rc = dv.tot.reserve(4))) return rc;
     if ((rc = dv.dev0.create())) return rc;
     if ((rc = dv.dev1.create())) return rc;
     DeliverArgs a{};
     a.keys = ibx.passes & 1 ? ib.d_key1.p : ib.key0;   // where the sort left the pairs
-    a.groups = ib.merged ? ib.d_grp.p : nullptr;
-    a.publishes = ib.d_pub.p; a.filter_ids = ib.d_fid.p; a.subscribers = ib.d_sub.p;
+    a.groups = ib.merged ? ib.grp.d.p : nullptr;
+    a.publishes = ib.pub.d.p; a.filter_ids = ib.fid.d.p; a.subscribers = ib.sub.d.p;
     a.hcount = ib.d_hcount.p; a.hcbs = ib.d_hcbs.p;
     a.D = D; a.R = nsub; a.n = n; a.ntiles = ntiles;
     a.tsub = R.tab.d_tsub.p; a.tstart = R.tab.d_tstart.p; a.tnode = R.tab.d_tnode.p; a.tval = R.tab.d_tval.p;
     a.T = (uint32_t)h_tnode.size(); a.NS = (uint32_t)h_tsub.size();
     a.flags = o->flags;
     a.rng = dv.d_rng.p; a.first = dv.d_first.p;
-    a.err = dv.d_tot.p + 2; a.d_tot = dv.d_tot.p;
+    a.err = dv.tot.d.p + 2; a.d_tot = dv.tot.d.p;
     if (o->msg) {
-        if ((rc = dv.d_min.reserve(n))) return rc;
-        if ((rc = dv.h_min.reserve(n))) return rc;
-        memcpy(dv.h_min.p, o->msg, n);
-        HIP_OK(hipMemcpyAsync(dv.d_min.p, dv.h_min.p, n, hipMemcpyHostToDevice, stream));
-        a.msg = dv.d_min.p;
+        if ((rc = dv.msg_in.stage(o->msg, n, stream))) return rc;
+        a.msg = dv.msg_in.d.p;
     }
     if (can_drop) {
-        if ((rc = dv.d_from.reserve(n))) return rc;
-        if ((rc = dv.h_from.reserve(n))) return rc;
-        memcpy(dv.h_from.p, o->from, (size_t)n * 4);
-        HIP_OK(hipMemcpyAsync(dv.d_from.p, dv.h_from.p, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-        a.from = dv.d_from.p;
+        if ((rc = dv.from.stage(o->from, n, stream))) return rc;
+        a.from = dv.from.d.p;
         if ((rc = dv.d_own.reserve(dd))) return rc;
         if ((rc = dv.d_emsg.reserve(dd))) return rc;
         if (want_subids && (rc = dv.d_esubid.reserve(dd))) return rc;
@@ -737,90 +682,75 @@ int tm_engine::batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_i
         if ((rc = dv.d_kbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
         if ((rc = dv.d_ncount.reserve((size_t)ntiles + 1))) return rc;
         if ((rc = dv.d_nbs.reserve((size_t)scan_block_count(ntiles) + 1))) return rc;
-        if ((rc = dv.d_sub.reserve(nsub))) return rc;
-        if ((rc = dv.d_off.reserve((size_t)nsub + 1))) return rc;
-        if ((rc = dv.d_pub.reserve(dd))) return rc;
-        if ((rc = dv.d_fid.reserve(dd))) return rc;
+        if ((rc = dv.sub.reserve(nsub))) return rc;
+        if ((rc = dv.off.reserve((size_t)nsub + 1))) return rc;
+        if ((rc = dv.pub.reserve(D))) return rc;
+        if ((rc = dv.fid.reserve(D))) return rc;
         if (ib.merged) {
-            if ((rc = dv.d_grp.reserve(dd))) return rc;
-            a.o_grp = dv.d_grp.p;
+            if ((rc = dv.grp.reserve(D))) return rc;
+            a.o_grp = dv.grp.d.p;
         }
         a.own = dv.d_own.p; a.emsg = dv.d_emsg.p; a.esubid = want_subids ? dv.d_esubid.p : nullptr;
         a.kcount = dv.d_kcount.p; a.kbs = dv.d_kbs.p; a.ncount = dv.d_ncount.p; a.nbs = dv.d_nbs.p;
-        a.o_sub = dv.d_sub.p; a.o_off = dv.d_off.p; a.o_pub = dv.d_pub.p; a.o_fid = dv.d_fid.p;
-        a.o_msg = dv.d_msg.p; a.o_subid = want_subids ? dv.d_subid.p : nullptr;
+        a.o_sub = dv.sub.d.p; a.o_off = dv.off.d.p; a.o_pub = dv.pub.d.p; a.o_fid = dv.fid.d.p;
+        a.o_msg = dv.msg.d.p; a.o_subid = want_subids ? dv.subid.d.p : nullptr;
     } else {   // the enriched bytes are the result; the other four arrays are the inboxes'
-        a.emsg = dv.d_msg.p; a.esubid = want_subids ? dv.d_subid.p : nullptr;
+        a.emsg = dv.msg.d.p; a.esubid = want_subids ? dv.subid.d.p : nullptr;
     }
-    HIP_OK(hipMemsetAsync(dv.d_tot.p, 0, 16, stream));
+    HIP_OK(hipMemsetAsync(dv.tot.d.p, 0, 16, stream));
     HIP_OK(hipEventRecord(dv.dev0.e, stream));
     HIP_OK(launch_deliver_flags(a, can_drop, stream));
     if (can_drop) HIP_OK(launch_deliver_compact(a, stream));
     HIP_OK(hipEventRecord(dv.dev1.e, stream));
-    HIP_OK(hipMemcpyAsync(dv.h_tot.p, dv.d_tot.p, 16, hipMemcpyDeviceToHost, stream));
+    if ((rc = dv.tot.fetch(4, stream))) return rc;
     HIP_OK(hipStreamSynchronize(stream));
     HIP_OK(hipEventElapsedTime(&out->kernel_ms, dv.dev0.e, dv.dev1.e));
-    if (dv.h_tot.p[2]) {
-        snprintf(last_error(), 512, "tm_batch_deliver: %u of %u deliveries without subscription options", dv.h_tot.p[2], D);
+    const uint32_t* tot = dv.tot.h.p;   // [deliveries left, inboxes left, errors]
+    if (tot[2]) {
+        snprintf(last_error(), 512, "tm_batch_deliver: %u of %u deliveries without subscription options", tot[2], D);
         return TM_EIO;
     }
-    uint32_t left = D, rleft = nsub;
-    if (can_drop) {
-        left = dv.h_tot.p[0];
-        rleft = dv.h_tot.p[1];
-        if (left > D || rleft > nsub || (left == 0) != (rleft == 0)) {
-            snprintf(last_error(), 512, "inconsistent session inboxes: %u of %u deliveries, %u of %u subscribers", left, D,
-                     rleft, nsub);
-            return TM_EIO;
-        }
+    const uint32_t left = can_drop ? tot[0] : D, rleft = can_drop ? tot[1] : nsub;
+    if (left > D || rleft > nsub || (left == 0) != (rleft == 0)) {
+        snprintf(last_error(), 512, "inconsistent session inboxes: %u of %u deliveries, %u of %u subscribers", left, D,
+                 rleft, nsub);
+        return TM_EIO;
     }
     out->n_subscribers = rleft;
     out->n_deliveries = left;
     out->n_dropped_no_local = D - left;
     if (ib.merged && can_drop) {   // tm_batch_inbox_groups: compacted alike
-        ib.d_groups = dv.d_grp.p;
+        ib.groups = &dv.grp;
         ib.n_groups = left;
         ib.grp_host = false;
     }
-    if (device) {
-        out->subscribers = can_drop ? dv.d_sub.p : ib.d_sub.p;
-        out->inbox_offsets = can_drop ? dv.d_off.p : ib.d_off.p;
-        out->publishes = can_drop ? dv.d_pub.p : ib.d_pub.p;
-        out->filter_ids = can_drop ? dv.d_fid.p : ib.d_fid.p;
-        out->msg = dv.d_msg.p;
-        out->subids = want_subids ? dv.d_subid.p : nullptr;
-        return TM_OK;
-    }
-    if (left) {
-        HIP_OK(hipMemcpyAsync(dv.h_msg.p, dv.d_msg.p, left, hipMemcpyDeviceToHost, stream));
-        if (want_subids) HIP_OK(hipMemcpyAsync(dv.h_subid.p, dv.d_subid.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
+    if (!device) {
+        if ((rc = dv.msg.fetch(left, stream))) return rc;
+        if (want_subids && (rc = dv.subid.fetch(left, stream))) return rc;
+        if (can_drop) {
+            if ((rc = dv.off.fetch(rleft ? (size_t)rleft + 1 : 0, stream))) return rc;
+            if ((rc = dv.sub.fetch(rleft, stream))) return rc;
+            if ((rc = dv.pub.fetch(left, stream))) return rc;
+            if ((rc = dv.fid.fetch(left, stream))) return rc;
+        }
+        HIP_OK(hipStreamSynchronize(stream));
+        if (can_drop) {
+            if (!rleft) dv.off.h.p[0] = 0;
+            if (dv.off.h.p[rleft] != left) {
+                snprintf(last_error(), 512, "inconsistent session inbox offsets: %u vs %u", dv.off.h.p[rleft], left);
+                return TM_EIO;
+            }
+        }
     }
     if (can_drop) {
-        if ((rc = dv.h_sub.reserve(std::max<size_t>(rleft, 1)))) return rc;
-        if ((rc = dv.h_off.reserve((size_t)rleft + 1))) return rc;
-        if ((rc = dv.h_pub.reserve(dd))) return rc;
-        if ((rc = dv.h_fid.reserve(dd))) return rc;
-        if (rleft) {
-            HIP_OK(hipMemcpyAsync(dv.h_off.p, dv.d_off.p, ((size_t)rleft + 1) * 4, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipMemcpyAsync(dv.h_sub.p, dv.d_sub.p, (size_t)rleft * 4, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipMemcpyAsync(dv.h_pub.p, dv.d_pub.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
-            HIP_OK(hipMemcpyAsync(dv.h_fid.p, dv.d_fid.p, (size_t)left * 4, hipMemcpyDeviceToHost, stream));
-        }
-        HIP_OK(hipStreamSynchronize(stream));
-        if (!rleft) dv.h_off.p[0] = 0;
-        if (dv.h_off.p[rleft] != left) {
-            snprintf(last_error(), 512, "inconsistent session inbox offsets: %u vs %u", dv.h_off.p[rleft], left);
-            return TM_EIO;
-        }
-        out->subscribers = dv.h_sub.p; out->inbox_offsets = dv.h_off.p;
-        out->publishes = dv.h_pub.p; out->filter_ids = dv.h_fid.p;
-    } else {
-        HIP_OK(hipStreamSynchronize(stream));
+        out->subscribers = dv.sub.view(device); out->inbox_offsets = dv.off.view(device);
+        out->publishes = dv.pub.view(device); out->filter_ids = dv.fid.view(device);
+    } else {   // nothing dropped: the inboxes' own arrays
         out->subscribers = ibx.subscribers; out->inbox_offsets = ibx.inbox_offsets;
         out->publishes = ibx.publishes; out->filter_ids = ibx.filter_ids;
     }
-    out->msg = dv.h_msg.p;
-    out->subids = want_subids ? dv.h_subid.p : nullptr;
+    out->msg = dv.msg.view(device);
+    out->subids = want_subids ? dv.subid.view(device) : nullptr;
     return TM_OK;
 }
 
@@ -850,72 +780,65 @@ int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_wind
     tm_batch::Window& wn = b->win;
     // where batch_deliver left the result on the device, whichever copy it returned
     const bool can_drop = o->from && nl_entries > 0;
-    const uint32_t* d_sub = can_drop ? b->dlv.d_sub.p : b->inbox.d_sub.p;
-    const uint32_t* d_off = can_drop ? b->dlv.d_off.p : b->inbox.d_off.p;
+    const uint32_t* d_sub = can_drop ? b->dlv.sub.d.p : b->inbox.sub.d.p;
+    const uint32_t* d_off = can_drop ? b->dlv.off.d.p : b->inbox.off.d.p;
     const uint32_t D = (uint32_t)out->inboxes.n_deliveries, nsub = out->inboxes.n_subscribers, ns = w->n_sessions;
-    const size_t dd = std::max<size_t>(D, 1), rr = std::max<size_t>(nsub, 1);
-    if ((rc = wn.d_disp.reserve(dd))) return rc;
-    if ((rc = wn.d_pid.reserve(dd))) return rc;
-    if ((rc = wn.d_rec.reserve(rr))) return rc;
+    const size_t rr = std::max<size_t>(nsub, 1);
+    const bool live = D && nsub;   // else nothing left to send: every total 0
+    if ((rc = wn.disp.reserve(D))) return rc;
+    if ((rc = wn.pid.reserve(D))) return rc;
+    if ((rc = wn.rec.reserve(nsub))) return rc;
+    if (live) {
+        const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
+        const size_t nheads = (size_t)2 * (((size_t)D + 63) / 64);
+        WindowArgs a{};
+        a.nwaves = ntiles * (INBOX_TILE / 1024);
+        if ((rc = wn.d_heads.reserve(nheads))) return rc;
+        if ((rc = wn.d_st.reserve(rr))) return rc;
+        if ((rc = wn.d_hbase.reserve(rr))) return rc;
+        if ((rc = wn.d_wcount.reserve((size_t)a.nwaves + 1))) return rc;
+        if ((rc = wn.d_wbs.reserve((size_t)scan_block_count(a.nwaves) + 1))) return rc;
+        if ((rc = wn.d_wdisp.reserve((size_t)a.nwaves * 8))) return rc;
+        if ((rc = wn.tot.reserve(2))) return rc;
+        if ((rc = wn.totals.reserve(WIN_NDISP))) return rc;
+        if ((rc = wn.wev0.create())) return rc;
+        if ((rc = wn.wev1.create())) return rc;
+        // uploaded per call: acks change the sessions on the host between any two calls
+        if ((rc = wn.sess.stage(reinterpret_cast<const uint32_t*>(w->sessions), (size_t)ns * WIN_SESSION_WORDS, stream)))
+            return rc;
+        a.subscribers = d_sub; a.off = d_off; a.msg = b->dlv.msg.d.p; a.sess = wn.sess.d.p;
+        a.D = D; a.R = nsub; a.NS = ns;
+        memcpy(a.dflt, &w->defaults, sizeof a.dflt);
+        a.heads = wn.d_heads.p; a.st = wn.d_st.p; a.hbase = wn.d_hbase.p;
+        a.wcount = wn.d_wcount.p; a.wbs = wn.d_wbs.p; a.d_tot = wn.tot.d.p;
+        a.disp = wn.disp.d.p; a.pid = wn.pid.d.p; a.rec = wn.rec.d.p;
+        a.wdisp = wn.d_wdisp.p; a.totals = wn.totals.d.p;
+        HIP_OK(hipMemsetAsync(wn.d_heads.p, 0, nheads * 4, stream));
+        HIP_OK(hipMemsetAsync(wn.tot.d.p, 0, 8, stream));
+        HIP_OK(hipEventRecord(wn.wev0.e, stream));
+        HIP_OK(launch_window(a, stream));
+        HIP_OK(hipEventRecord(wn.wev1.e, stream));
+        if ((rc = wn.tot.fetch(2, stream))) return rc;
+        if ((rc = wn.totals.fetch(WIN_NDISP, stream))) return rc;
+    }
     if (!device) {
-        if ((rc = wn.h_disp.reserve(dd))) return rc;
-        if ((rc = wn.h_pid.reserve(dd))) return rc;
-        if ((rc = wn.h_rec.reserve(rr))) return rc;
+        if ((rc = wn.disp.fetch(live ? D : 0, stream))) return rc;
+        if ((rc = wn.pid.fetch(live ? D : 0, stream))) return rc;
+        if ((rc = wn.rec.fetch(live ? nsub : 0, stream))) return rc;
     }
-    out->disp = device ? wn.d_disp.p : wn.h_disp.p;
-    out->packet_ids = device ? wn.d_pid.p : wn.h_pid.p;
-    out->records = (const tm_window_record*)(device ? wn.d_rec.p : wn.h_rec.p);
-    if (!D || !nsub) return TM_OK;   // nothing left to send: every total 0
-    const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
-    const size_t nheads = (size_t)2 * (((size_t)D + 63) / 64);
-    WindowArgs a{};
-    a.nwaves = ntiles * (INBOX_TILE / 1024);
-    if ((rc = wn.d_sess.reserve(std::max<size_t>((size_t)ns * WIN_SESSION_WORDS, 1)))) return rc;
-    if ((rc = wn.h_sess.reserve(std::max<size_t>((size_t)ns * WIN_SESSION_WORDS, 1)))) return rc;
-    if ((rc = wn.d_heads.reserve(nheads))) return rc;
-    if ((rc = wn.d_st.reserve(rr))) return rc;
-    if ((rc = wn.d_hbase.reserve(rr))) return rc;
-    if ((rc = wn.d_wcount.reserve((size_t)a.nwaves + 1))) return rc;
-    if ((rc = wn.d_wbs.reserve((size_t)scan_block_count(a.nwaves) + 1))) return rc;
-    if ((rc = wn.d_wdisp.reserve((size_t)a.nwaves * 8))) return rc;
-    if ((rc = wn.d_tot.reserve(2))) return rc;
-    if ((rc = wn.h_tot.reserve(2))) return rc;
-    if ((rc = wn.d_totals.reserve(WIN_NDISP))) return rc;
-    if ((rc = wn.h_totals.reserve(WIN_NDISP))) return rc;
-    if ((rc = wn.wev0.create())) return rc;
-    if ((rc = wn.wev1.create())) return rc;
-    a.subscribers = d_sub; a.off = d_off; a.msg = b->dlv.d_msg.p; a.sess = wn.d_sess.p;
-    a.D = D; a.R = nsub; a.NS = ns;
-    memcpy(a.dflt, &w->defaults, sizeof a.dflt);
-    a.heads = wn.d_heads.p; a.st = wn.d_st.p; a.hbase = wn.d_hbase.p;
-    a.wcount = wn.d_wcount.p; a.wbs = wn.d_wbs.p; a.d_tot = wn.d_tot.p;
-    a.disp = wn.d_disp.p; a.pid = wn.d_pid.p; a.rec = wn.d_rec.p;
-    a.wdisp = wn.d_wdisp.p; a.totals = wn.d_totals.p;
-    if (ns) {   // uploaded per call: acks change the sessions on the host between any two calls
-        memcpy(wn.h_sess.p, w->sessions, (size_t)ns * sizeof(tm_session_state));
-        HIP_OK(hipMemcpyAsync(wn.d_sess.p, wn.h_sess.p, (size_t)ns * sizeof(tm_session_state), hipMemcpyHostToDevice, stream));
-    }
-    HIP_OK(hipMemsetAsync(wn.d_heads.p, 0, nheads * 4, stream));
-    HIP_OK(hipMemsetAsync(wn.d_tot.p, 0, 8, stream));
-    HIP_OK(hipEventRecord(wn.wev0.e, stream));
-    HIP_OK(launch_window(a, stream));
-    HIP_OK(hipEventRecord(wn.wev1.e, stream));
-    HIP_OK(hipMemcpyAsync(wn.h_tot.p, wn.d_tot.p, 8, hipMemcpyDeviceToHost, stream));
-    HIP_OK(hipMemcpyAsync(wn.h_totals.p, wn.d_totals.p, WIN_NDISP * 8, hipMemcpyDeviceToHost, stream));
-    if (!device) {
-        HIP_OK(hipMemcpyAsync(wn.h_disp.p, wn.d_disp.p, D, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(wn.h_pid.p, wn.d_pid.p, (size_t)D * 2, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(wn.h_rec.p, wn.d_rec.p, (size_t)nsub * 16, hipMemcpyDeviceToHost, stream));
-    }
+    out->disp = wn.disp.view(device);
+    out->packet_ids = wn.pid.view(device);
+    out->records = (const tm_window_record*)wn.rec.view(device);
+    if (!live) return TM_OK;
     HIP_OK(hipStreamSynchronize(stream));
     HIP_OK(hipEventElapsedTime(&out->kernel_ms, wn.wev0.e, wn.wev1.e));
-    if (wn.h_tot.p[1]) {
-        snprintf(last_error(), 512, "tm_batch_window: %u indices past %u deliveries, %u inboxes or %u sessions", wn.h_tot.p[1],
+    if (wn.tot.h.p[1]) {
+        snprintf(last_error(), 512, "tm_batch_window: %u indices past %u deliveries, %u inboxes or %u sessions", wn.tot.h.p[1],
                  D, nsub, ns);
         return TM_EIO;
     }
     uint64_t sum = 0;
-    for (uint32_t k = 0; k < WIN_NDISP; ++k) sum += out->totals[k] = wn.h_totals.p[k];
+    for (uint32_t k = 0; k < WIN_NDISP; ++k) sum += out->totals[k] = wn.totals.h.p[k];
     if (sum != D) {
         snprintf(last_error(), 512, "tm_batch_window: dispositions of %llu of %u deliveries", (unsigned long long)sum, D);
         return TM_EIO;

@@ -6,15 +6,6 @@
 static_assert(SH_RANDOM == TM_SHARED_RANDOM && SH_ROUND_ROBIN == TM_SHARED_ROUND_ROBIN && SH_HASH == TM_SHARED_HASH,
               "the kernels' strategy codes are the ABI's");
 
-namespace {
-
-int einval(const char* msg) {
-    snprintf(last_error(), 512, "%s", msg);
-    return TM_EINVAL;
-}
-
-}  // namespace
-
 int tm_engine::shared_subscribe(const uint8_t* t, size_t len, uint32_t group, uint32_t sub) {
     std::string k((const char*)t, len);
     auto it = shared_of.find(k);
@@ -225,93 +216,76 @@ int tm_engine::batch_dispatch_shared(tm_batch* b, const tm_shared_opts* o, tm_sh
     int rc;
     if ((rc = ensure_dense(b))) return rc;
     if ((rc = sync_shared(R))) return rc;
-    const size_t nn = std::max<size_t>(n, 1);
     const uint64_t m64 = b->total;   // match entries (< 2^32: u32 result CSR)
     if (m64 > 0xFFFFFFF0ull) return TM_EOVERFLOW;
     const uint32_t m = (uint32_t)m64;
-    ScanArgs sa{};
-    if ((rc = b->sh.es.reserve(m, nn, sa))) return rc;
-    if ((rc = b->sh.d_gtot64.reserve(1))) return rc;
-    if ((rc = b->sh.h_gtot64.reserve(1))) return rc;
-    for (Event& ev : b->sh.gev)
+    tm_batch::Shared& sh = b->sh;
+    if ((rc = sh.es.reserve(m, n))) return rc;
+    if ((rc = sh.tot64.reserve(1))) return rc;
+    for (Event& ev : sh.gev)
         if ((rc = ev.create())) return rc;
     SharedArgs a{};
     a.row_off = b->dcsr.d_rowoff.p; a.ids = b->dcsr.d_ids.p; a.n = n; a.m = m;
     a.gcnt = R.tab.d_gcnt.p; a.goff = R.tab.d_goff.p; a.runs = R.tab.d_gruns.p; a.mem = R.tab.d_gmem.p;
     a.nnodes = shared_nn; a.nruns = (uint32_t)h_gruns.size(); a.nmem = (uint32_t)h_gmem.size();
     a.nslots = (uint32_t)h_gupd.size(); a.slots = R.tab.d_gslots.p;
-    a.ecount = b->sh.es.count.p; a.eoff = b->sh.es.eoff.p; a.bsums = b->sh.es.bsums.p; a.total = b->sh.es.total.p;
-    a.total64 = b->sh.d_gtot64.p; a.g_rowoff = b->sh.es.row.p;
+    a.ecount = sh.es.count.p; a.eoff = sh.es.eoff.p; a.bsums = sh.es.bsums.p; a.total = sh.es.total.d.p;
+    a.total64 = sh.tot64.d.p; a.g_rowoff = sh.es.row.d.p;
     a.strategy = o->strategy; a.seed = o->seed;
-    HIP_OK(hipEventRecord(b->sh.gev[0].e, stream));
-    HIP_OK(hipMemsetAsync(b->sh.d_gtot64.p, 0, 8, stream));
+    HIP_OK(hipEventRecord(sh.gev[0].e, stream));
+    HIP_OK(hipMemsetAsync(sh.tot64.d.p, 0, 8, stream));
     HIP_OK(launch_shared_count(a, stream));
-    if (m) {
-        HIP_OK(launch_scan(sa, stream, b->sh.es.total.p));
-    } else {
-        HIP_OK(hipMemsetAsync(b->sh.es.total.p, 0, 4, stream));
-    }
+    HIP_OK(sh.es.scan(stream));
     HIP_OK(launch_shared_rows(a, stream));
-    HIP_OK(hipEventRecord(b->sh.gev[1].e, stream));
-    HIP_OK(hipMemcpyAsync(b->sh.h_gtot64.p, b->sh.d_gtot64.p, 8, hipMemcpyDeviceToHost, stream));
+    HIP_OK(hipEventRecord(sh.gev[1].e, stream));
+    if ((rc = sh.tot64.fetch(1, stream))) return rc;
     HIP_OK(hipStreamSynchronize(stream));
-    const uint64_t total = b->sh.h_gtot64.p[0];
+    const uint64_t total = sh.tot64.h.p[0];
     if (total > 0xFFFFFFF0ull) return TM_EOVERFLOW;   // the u32 scan wrapped: nothing of it is used
     float ms = 0.f, ms2 = 0.f;
     if (!counts_only) {
-        if ((rc = b->sh.d_gfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = b->sh.d_ggrp.reserve(std::max<uint64_t>(total, 1)))) return rc;
-        if ((rc = b->sh.d_gsub.reserve(std::max<uint64_t>(total, 1)))) return rc;
+        if ((rc = sh.fid.reserve(total))) return rc;
+        if ((rc = sh.grp.reserve(total))) return rc;
+        if ((rc = sh.sub.reserve(total))) return rc;
         if (o->strategy == TM_SHARED_HASH && n) {
-            if ((rc = b->sh.d_gkeys.reserve(nn))) return rc;
-            if ((rc = b->sh.h_gkeys.reserve(nn))) return rc;
-            memcpy(b->sh.h_gkeys.p, o->keys, (size_t)n * 4);
-            HIP_OK(hipMemcpyAsync(b->sh.d_gkeys.p, b->sh.h_gkeys.p, (size_t)n * 4, hipMemcpyHostToDevice, stream));
-            a.keys = b->sh.d_gkeys.p;
+            if ((rc = sh.keys.stage(o->keys, n, stream))) return rc;
+            a.keys = sh.keys.d.p;
         }
-        a.out_fid = b->sh.d_gfid.p; a.out_grp = b->sh.d_ggrp.p; a.out_sub = b->sh.d_gsub.p; a.cap = total;
+        a.out_fid = sh.fid.d.p; a.out_grp = sh.grp.d.p; a.out_sub = sh.sub.d.p; a.cap = total;
         if (entries) {
-            if ((rc = b->sh.d_gent.reserve(std::max<uint64_t>(total, 1)))) return rc;
-            a.out_ent = b->sh.d_gent.p;
+            if ((rc = sh.d_gent.reserve(std::max<uint64_t>(total, 1)))) return rc;
+            a.out_ent = sh.d_gent.p;
             // a slot the pick leaves unwritten reads as a pick without a member: the merge counts it
-            if (total) HIP_OK(hipMemsetAsync(b->sh.d_gsub.p, 0xFF, total * 4, stream));
+            if (total) HIP_OK(hipMemsetAsync(sh.sub.d.p, 0xFF, total * 4, stream));
         }
-        HIP_OK(hipEventRecord(b->sh.gev[2].e, stream));
+        HIP_OK(hipEventRecord(sh.gev[2].e, stream));
         if (total) HIP_OK(launch_shared_pick(a, stream));
-        HIP_OK(hipEventRecord(b->sh.gev[3].e, stream));
+        HIP_OK(hipEventRecord(sh.gev[3].e, stream));
     }
+    const bool device = o->flags & TM_SHARED_DEVICE;
+    if (!device) {
+        if ((rc = sh.es.row.fetch((size_t)n + 1, stream))) return rc;
+        if (!counts_only) {
+            if ((rc = sh.fid.fetch(total, stream))) return rc;
+            if ((rc = sh.grp.fetch(total, stream))) return rc;
+            if ((rc = sh.sub.fetch(total, stream))) return rc;
+        }
+    }
+    HIP_OK(hipStreamSynchronize(stream));
+    if (!device && sh.es.row.h.p[n] != total) {
+        snprintf(last_error(), 512, "inconsistent shared delivery CSR: %u vs %llu", sh.es.row.h.p[n],
+                 (unsigned long long)total);
+        return TM_EIO;
+    }
+    HIP_OK(hipEventElapsedTime(&ms, sh.gev[0].e, sh.gev[1].e));
+    if (!counts_only) HIP_OK(hipEventElapsedTime(&ms2, sh.gev[2].e, sh.gev[3].e));
     out->n_topics = n;
     out->n_deliveries = total;
-    if (o->flags & TM_SHARED_DEVICE) {
-        HIP_OK(hipStreamSynchronize(stream));
-    } else {
-        if ((rc = b->sh.h_grow.reserve(nn + 1))) return rc;
-        HIP_OK(hipMemcpyAsync(b->sh.h_grow.p, b->sh.es.row.p, ((size_t)n + 1) * 4, hipMemcpyDeviceToHost, stream));
-        if (!counts_only) {
-            if ((rc = b->sh.h_gfid.reserve(std::max<uint64_t>(total, 1)))) return rc;
-            if ((rc = b->sh.h_ggrp.reserve(std::max<uint64_t>(total, 1)))) return rc;
-            if ((rc = b->sh.h_gsub.reserve(std::max<uint64_t>(total, 1)))) return rc;
-            if (total) {
-                HIP_OK(hipMemcpyAsync(b->sh.h_gfid.p, b->sh.d_gfid.p, total * 4, hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipMemcpyAsync(b->sh.h_ggrp.p, b->sh.d_ggrp.p, total * 4, hipMemcpyDeviceToHost, stream));
-                HIP_OK(hipMemcpyAsync(b->sh.h_gsub.p, b->sh.d_gsub.p, total * 4, hipMemcpyDeviceToHost, stream));
-            }
-        }
-        HIP_OK(hipStreamSynchronize(stream));
-        if (b->sh.h_grow.p[n] != total) {
-            snprintf(last_error(), 512, "inconsistent shared delivery CSR: %u vs %llu", b->sh.h_grow.p[n],
-                     (unsigned long long)total);
-            return TM_EIO;
-        }
-    }
-    HIP_OK(hipEventElapsedTime(&ms, b->sh.gev[0].e, b->sh.gev[1].e));
-    if (!counts_only) HIP_OK(hipEventElapsedTime(&ms2, b->sh.gev[2].e, b->sh.gev[3].e));
     out->kernel_ms = ms + ms2;
-    const bool dev = o->flags & TM_SHARED_DEVICE;
-    out->row_offsets = dev ? b->sh.es.row.p : b->sh.h_grow.p;
-    out->filter_ids = counts_only ? nullptr : dev ? b->sh.d_gfid.p : b->sh.h_gfid.p;
-    out->groups = counts_only ? nullptr : dev ? b->sh.d_ggrp.p : b->sh.h_ggrp.p;
-    out->subscribers = counts_only ? nullptr : dev ? b->sh.d_gsub.p : b->sh.h_gsub.p;
+    out->row_offsets = sh.es.row.view(device);
+    out->filter_ids = counts_only ? nullptr : sh.fid.view(device);
+    out->groups = counts_only ? nullptr : sh.grp.view(device);
+    out->subscribers = counts_only ? nullptr : sh.sub.view(device);
     return TM_OK;
 }
 
@@ -362,20 +336,14 @@ int tm_engine::batch_inbox_groups(tm_batch* b, uint32_t flags, const uint32_t** 
     tm_batch::Inbox& ib = b->inbox;
     if (!b->shmode.armed || !ib.merged)
         return einval("tm_batch_inbox_groups: the batch is not armed, or no inboxes / deliver / window call ran armed");
-    if (flags & TM_INBOX_DEVICE) {
-        *groups = ib.d_groups;
-        return TM_OK;
-    }
-    if (!ib.grp_host) {
+    const bool device = flags & TM_INBOX_DEVICE;
+    if (!device && !ib.grp_host) {
         const hipStream_t stream = b->rep->stream;
-        int rc;
-        if ((rc = ib.h_grp.reserve(std::max<size_t>(ib.n_groups, 1)))) return rc;
-        if (ib.n_groups)
-            HIP_OK(hipMemcpyAsync(ib.h_grp.p, ib.d_groups, (size_t)ib.n_groups * 4, hipMemcpyDeviceToHost, stream));
+        if (int rc = ib.groups->fetch(ib.n_groups, stream)) return rc;
         HIP_OK(hipStreamSynchronize(stream));
         ib.grp_host = true;
     }
-    *groups = ib.h_grp.p;
+    *groups = ib.groups->view(device);
     return TM_OK;
 }
 
@@ -418,14 +386,7 @@ int tm_batch_inbox_groups(tm_engine* e, tm_batch* b, uint32_t flags, const uint3
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_inbox_groups(b, flags, groups);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_inbox_groups(b, flags, groups); });
 }
 
 int tm_batch_dispatch_shared(tm_engine* e, tm_batch* b, const tm_shared_opts* opts, tm_shared_deliveries* out) {
@@ -438,12 +399,5 @@ int tm_batch_dispatch_shared(tm_engine* e, tm_batch* b, const tm_shared_opts* op
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
-    std::lock_guard<std::recursive_mutex> g(e->mu);
-    int rc = e->use(b->rep);
-    if (rc) return rc;
-    try {
-        return e->batch_dispatch_shared(b, opts, out);
-    } catch (...) {
-        return TM_ENOMEM;
-    }
+    return on_batch(e, b, [&] { return e->batch_dispatch_shared(b, opts, out); });
 }
