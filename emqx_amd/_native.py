@@ -162,6 +162,27 @@ class SessionWindow(C.Structure):
                 ("kernel_ms", C.c_float), ("pad0", C.c_uint32)]
 
 
+TM_PRIO_INFINITY, TM_PRIO_MAX_CLASSES, TM_PRIO_MAX_TABLES, TM_PRIO_NOCLASS = 0xFFFF, 8, 16, 0xFF
+
+
+class SessionPrio(C.Structure):
+    _fields_ = [("subscriber", C.c_uint32), ("table", C.c_uint32), ("plen", C.c_uint32 * TM_PRIO_MAX_CLASSES)]
+
+
+class WindowPrioOpts(C.Structure):
+    _fields_ = [("tables", C.POINTER(C.c_void_p)), ("n_tables", C.c_uint32), ("n_prio", C.c_uint32),
+                ("prio", C.POINTER(SessionPrio)), ("default_table", C.c_uint32), ("pad0", C.c_uint32)]
+
+
+class PrioRecord(C.Structure):
+    _fields_ = [("n_queued", C.c_uint32), ("n_dropped_old", C.c_uint32)]
+
+
+class WindowPrio(C.Structure):
+    _fields_ = [("pclass", C.POINTER(C.c_uint8)), ("precords", C.POINTER(PrioRecord)),
+                ("lookup_kernel_ms", C.c_float), ("pad0", C.c_uint32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -286,6 +307,11 @@ SIGNATURES = {
     "tm_get_subopts": (C.c_int, [P, U8P, SZ, C.c_uint32, C.POINTER(SubOpts)]),
     "tm_batch_deliver": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(SessionInboxes)]),
     "tm_batch_window": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(WindowOpts), C.POINTER(SessionWindow)]),
+    "tm_ptable_create": (C.c_int, [P, P, P, P, C.c_uint32, C.c_uint32, C.POINTER(P)]),
+    "tm_ptable_free": (None, [P, P]),
+    "tm_ptable_classes": (C.c_uint32, [P, C.POINTER(C.c_uint16)]),
+    "tm_batch_window_prio": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(WindowOpts), C.POINTER(WindowPrioOpts),
+                                       C.POINTER(SessionWindow), C.POINTER(WindowPrio)]),
     "tm_match_routes_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Routes)]),
     "tm_trie_insert_many": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_trie_delete_many": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(C.c_uint64)]),

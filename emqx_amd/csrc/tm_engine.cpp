@@ -801,38 +801,135 @@ int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* opts, tm_
 }
 
 // one tm_session_state of tm_window_opts; which = its index, -1 for defaults
-static int session_check(const tm_session_state* s, long which) {
+// (sum: mqueue_len is checked against mqueue_max -- not for a session with a
+// priority table, whose classes are bounded one by one)
+static int session_check(const char* fn, const tm_session_state* s, long which, bool sum = true) {
     const char* bad = nullptr;
     if (s->next_pkt_id < 1 || s->next_pkt_id > 65535) bad = "next_pkt_id outside 1..65535";
     else if (s->flags & ~(TM_SESS_DISCONNECTED | TM_SESS_STORE_QOS0 | TM_SESS_HOST)) bad = "unknown session flag";
-    else if (s->mqueue_max && s->mqueue_len > s->mqueue_max) bad = "mqueue_len above mqueue_max";
+    else if (sum && s->mqueue_max && s->mqueue_len > s->mqueue_max) bad = "mqueue_len above mqueue_max";
     if (!bad) return TM_OK;
-    if (which < 0) return einval("tm_batch_window: defaults: %s", bad);
-    return einval("tm_batch_window: sessions[%ld] (subscriber %u): %s", which, s->subscriber, bad);
+    if (which < 0) return einval("%s: defaults: %s", fn, bad);
+    return einval("%s: sessions[%ld] (subscriber %u): %s", fn, which, s->subscriber, bad);
+}
+
+// tm_batch_window's checks of its arguments; tabled(i) (i = -1: the defaults):
+// that session has a priority table
+static int window_check(const char* fn, const tm_deliver_opts* dopts, const tm_window_opts* wopts, tm_session_window* out,
+                        const std::function<bool(long)>& tabled) {
+    if (!out || !dopts || !wopts) return einval("%s: %s is NULL", fn, !out ? "out" : !dopts ? "dopts" : "wopts");
+    if (dopts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS))
+        return einval("%s: unknown deliver flag", fn);
+    if (wopts->flags & ~TM_WINDOW_DEVICE) return einval("%s: unknown window flag", fn);
+    if (wopts->n_sessions && !wopts->sessions)
+        return einval("%s: sessions is NULL with n_sessions = %u", fn, wopts->n_sessions);
+    if (int rc = session_check(fn, &wopts->defaults, -1, !tabled(-1L))) return rc;
+    for (uint32_t i = 0; i < wopts->n_sessions; ++i) {
+        if (int rc = session_check(fn, &wopts->sessions[i], (long)i, !tabled((long)i))) return rc;
+        if (i && wopts->sessions[i].subscriber <= wopts->sessions[i - 1].subscriber)
+            return einval("%s: sessions[%u] (subscriber %u) not above sessions[%u] (%u)", fn, i,
+                          wopts->sessions[i].subscriber, i - 1, wopts->sessions[i - 1].subscriber);
+    }
+    return TM_OK;
 }
 
 int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
                     tm_session_window* out) {
     // the arguments are checked first, so a host-only engine reports them too
     if (!e) return TM_EINVAL;
-    if (!out || !dopts || !wopts)
-        return einval("tm_batch_window: %s is NULL", !out ? "out" : !dopts ? "dopts" : "wopts");
-    if (dopts->flags & ~(TM_DELIVER_DEVICE | TM_DELIVER_UPGRADE_QOS | TM_DELIVER_NL_ALL | TM_DELIVER_SUBIDS))
-        return einval("tm_batch_window: unknown deliver flag");
-    if (wopts->flags & ~TM_WINDOW_DEVICE) return einval("tm_batch_window: unknown window flag");
-    if (wopts->n_sessions && !wopts->sessions)
-        return einval("tm_batch_window: sessions is NULL with n_sessions = %u", wopts->n_sessions);
-    if (int rc = session_check(&wopts->defaults, -1)) return rc;
-    for (uint32_t i = 0; i < wopts->n_sessions; ++i) {
-        if (int rc = session_check(&wopts->sessions[i], (long)i)) return rc;
-        if (i && wopts->sessions[i].subscriber <= wopts->sessions[i - 1].subscriber)
-            return einval("tm_batch_window: sessions[%u] (subscriber %u) not above sessions[%u] (%u)", i,
-                          wopts->sessions[i].subscriber, i - 1, wopts->sessions[i - 1].subscriber);
-    }
+    if (int rc = window_check("tm_batch_window", dopts, wopts, out, [](long) { return false; })) return rc;
     if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
     if (!b) return TM_EINVAL;
     if (!b->rep) return TM_ENODEV;
     return on_batch(e, b, [&] { return e->batch_window(b, dopts, wopts, out); });
+}
+
+// one session of tm_batch_window_prio against its table (nullptr: none) and
+// its prio entry (nullptr: not listed); who names it in the message
+static int prio_session_check(const tm_session_state* s, const tm_ptable* t, const tm_session_prio* pe, const char* who,
+                              uint32_t subscriber) {
+    static const char* fn = "tm_batch_window_prio";
+    if (!t || (s->flags & TM_SESS_HOST)) return TM_OK;   // no table, or left to the host whole
+    if (!pe) {
+        if (s->mqueue_len)
+            return einval("%s: %s (subscriber %u) has a priority table and mqueue_len = %u but no prio entry", fn, who,
+                          subscriber, s->mqueue_len);
+        return TM_OK;
+    }
+    uint64_t sum = 0;
+    for (uint32_t c = 0; c < TM_PRIO_MAX_CLASSES; ++c) {
+        sum += pe->plen[c];
+        if (c >= t->ncls && pe->plen[c])
+            return einval("%s: %s (subscriber %u): plen[%u] = %u for a class its table lacks (%u classes)", fn, who,
+                          subscriber, c, pe->plen[c], t->ncls);
+        if (s->mqueue_max && pe->plen[c] > s->mqueue_max)
+            return einval("%s: %s (subscriber %u): plen[%u] = %u above mqueue_max %u", fn, who, subscriber, c,
+                          pe->plen[c], s->mqueue_max);
+    }
+    if (sum != s->mqueue_len)
+        return einval("%s: %s (subscriber %u): sum of plen %llu is not mqueue_len %u", fn, who, subscriber,
+                      (unsigned long long)sum, s->mqueue_len);
+    return TM_OK;
+}
+
+int tm_batch_window_prio(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
+                         const tm_window_prio_opts* popts, tm_session_window* out, tm_window_prio* pout) {
+    static const char* fn = "tm_batch_window_prio";
+    if (!e) return TM_EINVAL;
+    if (!popts || !pout) return einval("%s: %s is NULL", fn, !popts ? "popts" : "pout");
+    const uint32_t nt = popts->n_tables, np = popts->n_prio;
+    if (nt > TM_PRIO_MAX_TABLES) return einval("%s: n_tables = %u above %u", fn, nt, (unsigned)TM_PRIO_MAX_TABLES);
+    if ((nt && !popts->tables) || (np && !popts->prio))
+        return einval("%s: %s is NULL with a count above 0", fn, nt && !popts->tables ? "tables" : "prio");
+    if (popts->pad0) return einval("%s: pad0 is not 0", fn);
+    for (uint32_t t = 0; t < nt; ++t)
+        if (!popts->tables[t] || popts->tables[t]->e != e)
+            return einval("%s: tables[%u] is %s", fn, t, popts->tables[t] ? "a table of another engine" : "NULL");
+    if (popts->default_table != TM_NONE && popts->default_table >= nt)
+        return einval("%s: default_table = %u with n_tables = %u", fn, popts->default_table, nt);
+    for (uint32_t i = 0; i < np; ++i) {
+        const tm_session_prio& pe = popts->prio[i];
+        if (i && pe.subscriber <= popts->prio[i - 1].subscriber)
+            return einval("%s: prio[%u] (subscriber %u) not above prio[%u] (%u)", fn, i, pe.subscriber, i - 1,
+                          popts->prio[i - 1].subscriber);
+        if (pe.table != TM_NONE && pe.table >= nt)
+            return einval("%s: prio[%u] (subscriber %u): table = %u with n_tables = %u", fn, i, pe.subscriber, pe.table, nt);
+    }
+    auto table_at = [&](uint32_t idx) -> const tm_ptable* { return idx == TM_NONE ? nullptr : popts->tables[idx]; };
+    // the prio entry of a subscriber (both lists ascend: one search each)
+    auto entry_of = [&](uint32_t sub) -> const tm_session_prio* {
+        const tm_session_prio* end = popts->prio + np;
+        const tm_session_prio* it = std::lower_bound(popts->prio, end, sub,
+                                                     [](const tm_session_prio& x, uint32_t s) { return x.subscriber < s; });
+        return it != end && it->subscriber == sub ? it : nullptr;
+    };
+    auto table_of = [&](const tm_session_prio* pe) { return table_at(pe ? pe->table : popts->default_table); };
+    const bool args = out && dopts && wopts && !(wopts->n_sessions && !wopts->sessions);
+    auto tabled = [&](long i) {
+        if (!args || !nt) return false;
+        return table_of(i < 0 ? nullptr : entry_of(wopts->sessions[i].subscriber)) != nullptr;
+    };
+    if (int rc = window_check(fn, dopts, wopts, out, tabled)) return rc;
+    for (uint32_t i = 0; i < np; ++i) {   // (sessions ascend as well: window_check)
+        const uint32_t sub = popts->prio[i].subscriber;
+        const tm_session_state* end = wopts->sessions + wopts->n_sessions;
+        const tm_session_state* it = wopts->n_sessions ? std::lower_bound(wopts->sessions, end, sub,
+                                         [](const tm_session_state& x, uint32_t s) { return x.subscriber < s; }) : end;
+        if (it == end || it->subscriber != sub)
+            return einval("%s: prio[%u] (subscriber %u) is not in wopts->sessions", fn, i, sub);
+    }
+    if (nt) {
+        if (int rc = prio_session_check(&wopts->defaults, table_at(popts->default_table), nullptr, "defaults", 0)) return rc;
+        for (uint32_t i = 0; i < wopts->n_sessions; ++i) {
+            const tm_session_state& s = wopts->sessions[i];
+            const tm_session_prio* pe = entry_of(s.subscriber);
+            if (int rc = prio_session_check(&s, table_of(pe), pe, "a session", s.subscriber)) return rc;
+        }
+    }
+    if (e->reps.empty()) return TM_ENODEV;   // host-only engine: no CPU fallback
+    if (!b) return TM_EINVAL;
+    if (!b->rep) return TM_ENODEV;
+    return on_batch(e, b, [&] { return e->batch_window_prio(b, dopts, wopts, popts, out, pout); });
 }
 
 int tm_batch_routes(tm_engine* e, tm_batch* b, tm_routes* out) {

@@ -387,6 +387,19 @@ struct GraphCache {
     }
 };
 
+// A priority table (tm_ptable_create): its classes and the host image of the
+// open-addressed table tm_prio_lookup probes (layout in tm_internal.hpp).  A
+// call packs the images of its tables into one block, so the table itself
+// holds no device memory.
+struct tm_ptable {
+    tm_engine* e = nullptr;
+    uint64_t serial = 0;             // unique per create: what a batch's packed block is keyed by
+    uint32_t ncls = 0, dcls = 0;     // classes; the class of the default priority
+    uint16_t classes[TM_PRIO_MAX_CLASSES] = {};   // descending, TM_PRIO_INFINITY first
+    std::vector<uint32_t> slots;     // 2 words per slot, a power of two of them
+    std::vector<uint8_t> keys;       // the keys back to back + 32 B of padding
+};
+
 struct tm_batch {
     uint32_t n = 0;
     uint64_t nwords = 0;
@@ -589,6 +602,25 @@ struct tm_batch {
         Mirror<unsigned long long> totals;
         Event wev0, wev1;   // around the window kernels
     } win;
+
+    // the window over priority tables (tm_batch_window_prio): the call's
+    // tables as one block and which tables it was packed from (serials: the
+    // block is uploaded again only when they change), the uploaded prio
+    // entries, the class of every (table, publish), per-inbox and per-wave
+    // class scratch, and the result.  d_tbytes / d_toffs: the topic bytes of a
+    // host-tokenised batch, uploaded per call
+    struct Prio {
+        Mirror<uint32_t> blk, prio;
+        std::vector<uint64_t> blk_serials;
+        DevBuf<uint8_t> d_pcp, d_tbytes;
+        DevBuf<uint64_t> d_toffs;
+        DevBuf<uint4> d_ptab;
+        DevBuf<uint32_t> d_chbase, d_cw, d_cbs, d_ctot;
+        DevBuf<uint2> d_cthr;
+        Mirror<uint2> prec;
+        Mirror<uint8_t> pclass;
+        Event lev0, lev1;   // around the lookup kernel
+    } prio;
 
     static constexpr size_t HDR_FIXED = ((size_t)XG_WORD + TICKET_GROUPS * TICKET_STRIDE) * 4;
     static size_t hdr_bytes(size_t n) { return HDR_FIXED + n * 12; }
@@ -2013,6 +2045,9 @@ struct tm_engine {
     int batch_deliver(tm_batch* b, const tm_deliver_opts* o, tm_session_inboxes* out);
     // tm_batch_window: batch_deliver, then every delivery's disposition and packet id
     int batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w, tm_session_window* out);
+    // tm_batch_window_prio: batch_window over mqueues with priority tables
+    int batch_window_prio(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w, const tm_window_prio_opts* p,
+                          tm_session_window* out, tm_window_prio* pout);
 
     // do_unsubscribe/4 (:179-191) + handle_cast({unsubscribed, Topic}) (:463-469):
     // the last subscriber of a topic deletes the node's route.

@@ -2,6 +2,8 @@
 // (emqx_broker:publish -> subscribers), rule predicates.
 #include "tm_engine_impl.hpp"
 
+#include <memory>
+
 int tm_engine::route_add(const uint8_t* t, size_t len, uint32_t dest) {
     uint32_t n = node_of(t, len);
     if (n == NONE || n >= n_nroutes.size() || n_nroutes[n] == 0) {
@@ -768,8 +770,204 @@ static_assert(sizeof(tm_window_record) == sizeof(uint4) && std::has_unique_objec
 static_assert(sizeof(tm_session_window) == sizeof(tm_session_inboxes) + 3 * sizeof(void*) + 8 * TM_DISP_COUNT + 8,
               "tm_session_window has implicit padding");
 
+// ---- priority tables (tm_ptable_create, tm_batch_window_prio)
+static_assert(PRIO_CLASSES == TM_PRIO_MAX_CLASSES && PRIO_NOCLASS == TM_PRIO_NOCLASS && PRIO_MAX_KEY == TM_MAX_TOPIC_LEN,
+              "TM_PRIO_* as the kernels use them");
+static_assert(sizeof(tm_session_prio) == PRIO_SESSION_WORDS * 4 && std::has_unique_object_representations_v<tm_session_prio>,
+              "tm_session_prio is uploaded as ten words");
+static_assert(sizeof(tm_window_prio_opts) == 32 && std::has_unique_object_representations_v<tm_window_prio_opts>,
+              "tm_window_prio_opts has implicit padding");
+static_assert(sizeof(tm_prio_record) == sizeof(uint2) && std::has_unique_object_representations_v<tm_prio_record>,
+              "tm_prio_record is the kernels' uint2");
+static_assert(sizeof(tm_window_prio) == 2 * sizeof(void*) + 8, "tm_window_prio has implicit padding");
+
+// dd_hash (tm_kernels.hip) on the host, bit for bit: NH over the first 64
+// bytes as little-endian words, the bytes past them chained 8 at a time, the
+// length, the finaliser.
+static uint64_t prio_hash(const uint8_t* p, uint32_t len) {
+    static const uint32_t K[16] = {0x9E3779B1u, 0x85EBCA77u, 0xC2B2AE3Du, 0x27D4EB2Fu, 0x165667B1u, 0xD3A2646Du,
+                                   0xFD7046C5u, 0xB55A4F09u, 0x6C8E9CF5u, 0x7FEB352Du, 0x846CA68Bu, 0x94D049BBu,
+                                   0xBF58476Du, 0x1CE4E5B9u, 0x2545F491u, 0x9FB21C65u};
+    uint32_t c[16] = {};
+    if (len) memcpy(c, p, std::min<uint32_t>(len, 64u));
+    uint64_t h = 0;
+    for (uint32_t j = 0; j < 8; ++j) h += (uint64_t)(uint32_t)(c[2 * j] + K[2 * j]) * (uint64_t)(uint32_t)(c[2 * j + 1] + K[2 * j + 1]);
+    for (uint32_t k = 64; k < len; k += 8) {
+        uint64_t v = 0;
+        memcpy(&v, p + k, std::min<uint32_t>(len - k, 8u));
+        v *= 0x87C37B91114253D5ull;
+        v = (v << 31) | (v >> 33);
+        v *= 0x4CF5AD432745937Full;
+        h ^= v;
+        h = (h << 27) | (h >> 37);
+        h = h * 5u + 0x52DCE729ull;
+    }
+    h ^= (uint64_t)len * 0xC2B2AE3D27D4EB4Full;
+    h ^= h >> 33;
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 33;
+    h *= 0xC4CEB9FE1A85EC53ull;
+    return h ^ (h >> 33);
+}
+
+int tm_ptable_create(tm_engine* e, const uint8_t* topics, const uint64_t* offsets, const uint16_t* priorities, uint32_t n,
+                     uint32_t default_priority, tm_ptable** table) {
+    if (!e || !table || (n && (!offsets || !priorities))) return TM_EINVAL;
+    auto bad_prio = [](uint32_t p) { return p > 255u && p != TM_PRIO_INFINITY; };
+    if (bad_prio(default_priority))
+        return einval("tm_ptable_create: default priority %u (0..255 or TM_PRIO_INFINITY)", default_priority);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i]) return einval("tm_ptable_create: key %u: offsets not monotone", i);
+        if (offsets[i + 1] - offsets[i] > TM_MAX_TOPIC_LEN)
+            return einval("tm_ptable_create: key %u of %llu bytes (over %u)", i, (unsigned long long)(offsets[i + 1] - offsets[i]),
+                          (unsigned)TM_MAX_TOPIC_LEN);
+        if (bad_prio(priorities[i])) return einval("tm_ptable_create: key %u: priority %u (0..255 or TM_PRIO_INFINITY)", i, priorities[i]);
+    }
+    if (n && offsets[n] > offsets[0] && !topics) return TM_EINVAL;
+    static std::atomic<uint64_t> serials{0};
+    try {
+        // maps:put: a repeated key keeps its last priority
+        std::unordered_map<std::string, uint16_t> map;
+        std::vector<std::string> order;
+        for (uint32_t i = 0; i < n; ++i) {
+            std::string k(reinterpret_cast<const char*>(topics) + offsets[i], offsets[i + 1] - offsets[i]);
+            auto it = map.find(k);
+            if (it == map.end()) {
+                order.push_back(k);
+                map.emplace(std::move(k), priorities[i]);
+            } else {
+                it->second = priorities[i];
+            }
+        }
+        std::vector<uint16_t> cls{(uint16_t)default_priority};
+        for (const auto& kv : map) cls.push_back(kv.second);
+        std::sort(cls.begin(), cls.end(), std::greater<uint16_t>());   // TM_PRIO_INFINITY = 0xFFFF sorts first
+        cls.erase(std::unique(cls.begin(), cls.end()), cls.end());
+        if (cls.size() > TM_PRIO_MAX_CLASSES)
+            return einval("tm_ptable_create: %zu classes (distinct priorities and the default), at most %u", cls.size(),
+                          (unsigned)TM_PRIO_MAX_CLASSES);
+        auto class_of = [&](uint16_t p) { return (uint32_t)(std::find(cls.begin(), cls.end(), p) - cls.begin()); };
+        std::unique_ptr<tm_ptable> t(new tm_ptable);
+        t->e = e;
+        t->serial = ++serials;
+        t->ncls = (uint32_t)cls.size();
+        t->dcls = class_of((uint16_t)default_priority);
+        std::copy(cls.begin(), cls.end(), t->classes);
+        size_t cap = 8;
+        while (cap < 2 * order.size()) cap <<= 1;   // load <= 1/2
+        t->slots.assign(2 * cap, 0u);
+        for (const std::string& k : order) {
+            const uint64_t h = prio_hash(reinterpret_cast<const uint8_t*>(k.data()), (uint32_t)k.size());
+            size_t s = (uint32_t)h & (cap - 1);
+            while (t->slots[2 * s + 1]) s = (s + 1) & (cap - 1);
+            t->slots[2 * s] = (uint32_t)t->keys.size();
+            t->slots[2 * s + 1] = PRIO_META_USED | (uint32_t)(h >> 54) << PRIO_META_HASH_SHIFT |
+                                  class_of(map[k]) << PRIO_META_CLS_SHIFT | (uint32_t)k.size();
+            t->keys.insert(t->keys.end(), k.begin(), k.end());
+        }
+        t->keys.resize(((t->keys.size() + 15) & ~(size_t)15) + 32, 0);   // the kernel's 16-B loads stay inside
+        *table = t.release();
+        return TM_OK;
+    } catch (...) {
+        return TM_ENOMEM;
+    }
+}
+
+void tm_ptable_free(tm_engine* e, tm_ptable* table) {
+    (void)e;
+    delete table;
+}
+
+uint32_t tm_ptable_classes(const tm_ptable* table, uint16_t out[TM_PRIO_MAX_CLASSES]) {
+    if (!table) return 0;
+    if (out) std::copy(table->classes, table->classes + table->ncls, out);
+    return table->ncls;
+}
+
+// The call's tables as one block on the device (packed again only when the
+// list of tables changed), its prio entries, the batch's topic bytes, and the
+// lookup kernel between lev0 and lev1.  Fills pa's inputs.
+static int prio_lookup(tm_batch* b, const tm_window_prio_opts* p, PrioArgs& pa) {
+    tm_batch::Prio& pr = b->prio;
+    const hipStream_t stream = b->rep->stream;
+    const uint32_t ntab = p->n_tables, n = b->n;
+    int rc;
+    std::vector<uint64_t> serials(ntab);
+    uint32_t ncls = 0;
+    for (uint32_t t = 0; t < ntab; ++t) {
+        serials[t] = p->tables[t]->serial;
+        ncls = std::max(ncls, p->tables[t]->ncls);
+    }
+    if (serials != pr.blk_serials || !pr.blk.d.p) {
+        size_t w = (PRIO_HDR_W * (size_t)ntab + 3) & ~(size_t)3;
+        std::vector<uint32_t> blk(w, 0u);
+        for (uint32_t t = 0; t < ntab; ++t) {
+            blk[PRIO_HDR_W * t] = (uint32_t)w;
+            w += p->tables[t]->slots.size();
+        }
+        size_t bytes = (w * 4 + 15) & ~(size_t)15;
+        for (uint32_t t = 0; t < ntab; ++t) {
+            const tm_ptable& T = *p->tables[t];
+            blk[PRIO_HDR_W * t + 1] = (uint32_t)bytes;
+            blk[PRIO_HDR_W * t + 2] = (uint32_t)(T.slots.size() / 2 - 1);
+            blk[PRIO_HDR_W * t + 3] = T.dcls;
+            bytes += T.keys.size();   // (a multiple of 16)
+        }
+        if (bytes > 0xFFFFFFF0ull) return TM_EOVERFLOW;
+        blk.resize(bytes / 4, 0u);
+        for (uint32_t t = 0; t < ntab; ++t) {
+            const tm_ptable& T = *p->tables[t];
+            std::copy(T.slots.begin(), T.slots.end(), blk.begin() + blk[PRIO_HDR_W * t]);
+            memcpy(reinterpret_cast<uint8_t*>(blk.data()) + blk[PRIO_HDR_W * t + 1], T.keys.data(), T.keys.size());
+        }
+        pr.blk_serials.clear();
+        if ((rc = pr.blk.stage(blk.data(), blk.size(), stream))) return rc;
+        pr.blk_serials = serials;
+    }
+    // uploaded per call, as the sessions are: acks change the queues between any two calls
+    if ((rc = pr.prio.stage(reinterpret_cast<const uint32_t*>(p->prio), (size_t)p->n_prio * PRIO_SESSION_WORDS, stream)))
+        return rc;
+    if ((rc = pr.d_pcp.reserve(std::max<size_t>((size_t)ntab * n, 1)))) return rc;
+    if ((rc = pr.lev0.create())) return rc;
+    if ((rc = pr.lev1.create())) return rc;
+    PrioLookupArgs la{};
+    if (b->dev_tok) {
+        la.bytes = b->tok.in_bytes; la.offs = b->tok.in_offs; la.base = b->tok_base;
+    } else {   // tokenised on the host: the bytes go up for this call
+        const size_t nbytes = b->bytes.size();
+        if ((rc = pr.d_tbytes.reserve(nbytes + 32))) return rc;
+        if ((rc = pr.d_toffs.reserve((size_t)n + 1))) return rc;
+        if (nbytes) HIP_OK(hipMemcpyAsync(pr.d_tbytes.p, b->bytes.data(), nbytes, hipMemcpyHostToDevice, stream));
+        HIP_OK(hipMemcpyAsync(pr.d_toffs.p, b->offs.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, stream));
+        la.bytes = pr.d_tbytes.p; la.offs = pr.d_toffs.p; la.base = 0;
+    }
+    la.blk = pr.blk.d.p; la.n = n; la.ntab = ntab; la.out = pr.d_pcp.p;
+    HIP_OK(hipEventRecord(pr.lev0.e, stream));
+    HIP_OK(launch_prio_lookup(la, stream));
+    HIP_OK(hipEventRecord(pr.lev1.e, stream));
+    pa.pcp = pr.d_pcp.p; pa.prio = pr.prio.d.p;
+    pa.n = n; pa.ntab = ntab; pa.NP = p->n_prio; pa.dtab = p->default_table; pa.ncls = ncls;
+    return TM_OK;
+}
+
 int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w, tm_session_window* out) {
+    return batch_window_prio(b, o, w, nullptr, out, nullptr);
+}
+
+// p = nullptr: tm_batch_window, the old kernels alone.  With p but no table
+// (n_tables = 0) the same kernels run and pclass / precords are filled by two
+// memsets: no session has a table.
+int tm_engine::batch_window_prio(tm_batch* b, const tm_deliver_opts* o, const tm_window_opts* w,
+                                 const tm_window_prio_opts* p, tm_session_window* out, tm_window_prio* pout) {
     const bool device = w->flags & TM_WINDOW_DEVICE;
+    if (p) *pout = tm_window_prio{};
+    const uint32_t ntab = p ? p->n_tables : 0u;
+    if (ntab) {   // checked before anything runs: the lookup reads the batch's topic bytes on the device
+        if (!b->done) return einval("tm_batch_window_prio: the batch has not been waited for");
+        if (b->tokens_only || b->bounded || (b->dev_tok ? !b->tok.in_bytes || !b->tok.in_offs : b->offs.size() != (size_t)b->n + 1))
+            return einval("tm_batch_window_prio: the batch has no device copy of its topic bytes "
+                          "(tm_batch_prepare_tokens): the class lookup reads them");
+    }
     tm_deliver_opts dopt = *o;
     dopt.flags = (o->flags & ~TM_DELIVER_DEVICE) | (device ? TM_DELIVER_DEVICE : 0u);
     *out = tm_session_window{};
@@ -788,6 +986,13 @@ int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_wind
     if ((rc = wn.disp.reserve(D))) return rc;
     if ((rc = wn.pid.reserve(D))) return rc;
     if ((rc = wn.rec.reserve(nsub))) return rc;
+    tm_batch::Prio& pr = b->prio;
+    if (p) {
+        if ((rc = pr.pclass.reserve(D))) return rc;
+        if ((rc = pr.prec.reserve((size_t)nsub * PRIO_CLASSES))) return rc;
+    }
+    PrioArgs pa{};
+    if (live && ntab && (rc = prio_lookup(b, p, pa))) return rc;   // enqueued ahead of the window's kernels
     if (live) {
         const uint32_t ntiles = (uint32_t)(((uint64_t)D + INBOX_TILE - 1) / INBOX_TILE);
         const size_t nheads = (size_t)2 * (((size_t)D + 63) / 64);
@@ -816,7 +1021,25 @@ int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_wind
         HIP_OK(hipMemsetAsync(wn.d_heads.p, 0, nheads * 4, stream));
         HIP_OK(hipMemsetAsync(wn.tot.d.p, 0, 8, stream));
         HIP_OK(hipEventRecord(wn.wev0.e, stream));
-        HIP_OK(launch_window(a, stream));
+        if (ntab) {
+            const size_t nsb = (a.nwaves + PRIO_SCAN_TILE - 1) / PRIO_SCAN_TILE;
+            if ((rc = pr.d_ptab.reserve(rr))) return rc;
+            if ((rc = pr.d_chbase.reserve(rr * PRIO_CLASSES))) return rc;
+            if ((rc = pr.d_cw.reserve(((size_t)a.nwaves + 1) * PRIO_CLASSES))) return rc;
+            if ((rc = pr.d_cbs.reserve((nsb + 1) * PRIO_CLASSES))) return rc;
+            if ((rc = pr.d_ctot.reserve(PRIO_CLASSES))) return rc;
+            if ((rc = pr.d_cthr.reserve(rr * PRIO_CLASSES))) return rc;
+            pa.publishes = can_drop ? b->dlv.pub.d.p : b->inbox.pub.d.p;
+            pa.ptab = pr.d_ptab.p; pa.chbase = pr.d_chbase.p; pa.cw = pr.d_cw.p; pa.cbs = pr.d_cbs.p;
+            pa.ctot = pr.d_ctot.p; pa.cthr = pr.d_cthr.p; pa.prec = pr.prec.d.p; pa.pclass = pr.pclass.d.p;
+            HIP_OK(launch_window_prio(a, pa, stream));
+        } else {
+            HIP_OK(launch_window(a, stream));
+            if (p) {   // no table: no class anywhere
+                HIP_OK(hipMemsetAsync(pr.pclass.d.p, 0xFF, D, stream));
+                HIP_OK(hipMemsetAsync(pr.prec.d.p, 0, (size_t)nsub * PRIO_CLASSES * sizeof(uint2), stream));
+            }
+        }
         HIP_OK(hipEventRecord(wn.wev1.e, stream));
         if ((rc = wn.tot.fetch(2, stream))) return rc;
         if ((rc = wn.totals.fetch(WIN_NDISP, stream))) return rc;
@@ -825,6 +1048,14 @@ int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_wind
         if ((rc = wn.disp.fetch(live ? D : 0, stream))) return rc;
         if ((rc = wn.pid.fetch(live ? D : 0, stream))) return rc;
         if ((rc = wn.rec.fetch(live ? nsub : 0, stream))) return rc;
+        if (p) {
+            if ((rc = pr.pclass.fetch(live ? D : 0, stream))) return rc;
+            if ((rc = pr.prec.fetch(live ? (size_t)nsub * PRIO_CLASSES : 0, stream))) return rc;
+        }
+    }
+    if (p) {
+        pout->pclass = pr.pclass.view(device);
+        pout->precords = (const tm_prio_record*)pr.prec.view(device);
     }
     out->disp = wn.disp.view(device);
     out->packet_ids = wn.pid.view(device);
@@ -832,15 +1063,17 @@ int tm_engine::batch_window(tm_batch* b, const tm_deliver_opts* o, const tm_wind
     if (!live) return TM_OK;
     HIP_OK(hipStreamSynchronize(stream));
     HIP_OK(hipEventElapsedTime(&out->kernel_ms, wn.wev0.e, wn.wev1.e));
+    if (ntab) HIP_OK(hipEventElapsedTime(&pout->lookup_kernel_ms, pr.lev0.e, pr.lev1.e));
+    const char* fn = p ? "tm_batch_window_prio" : "tm_batch_window";
     if (wn.tot.h.p[1]) {
-        snprintf(last_error(), 512, "tm_batch_window: %u indices past %u deliveries, %u inboxes or %u sessions", wn.tot.h.p[1],
+        snprintf(last_error(), 512, "%s: %u indices past %u deliveries, %u inboxes or %u sessions", fn, wn.tot.h.p[1],
                  D, nsub, ns);
         return TM_EIO;
     }
     uint64_t sum = 0;
     for (uint32_t k = 0; k < WIN_NDISP; ++k) sum += out->totals[k] = wn.totals.h.p[k];
     if (sum != D) {
-        snprintf(last_error(), 512, "tm_batch_window: dispositions of %llu of %u deliveries", (unsigned long long)sum, D);
+        snprintf(last_error(), 512, "%s: dispositions of %llu of %u deliveries", fn, (unsigned long long)sum, D);
         return TM_EIO;
     }
     return TM_OK;

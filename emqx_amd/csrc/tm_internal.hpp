@@ -535,6 +535,52 @@ struct WindowArgs {
 };
 static_assert(std::has_unique_object_representations_v<WindowArgs>, "WindowArgs has implicit padding");
 
+// The send window over mqueues with priority tables (tm_batch_window_prio).
+// The tables of one call travel as ONE block of u32 words (tm_engine::
+// batch_window_prio packs it from the tables' host images, the kernel reads
+// it through a single kernel-argument pointer):
+//   table t   blk[PRIO_HDR_W * t ..]: word index of its slots, byte offset of
+//             its key bytes, slot mask (slots - 1, a power of two), the class
+//             of its default priority
+//   slot      two words {byte offset of the key within the table's bytes,
+//             meta}; meta = 0: empty, else 1 << 31 | 10 hash bits << 21 |
+//             class << 13 | key length (<= 4096).  Linear probing from
+//             hash & mask, load <= 1/2.
+//   bytes     the keys back to back, 16-B aligned start, 32 B of padding
+// The hash is dd_hash (tm_kernels.hip); prio_hash (tm_fanout.cpp) is its host
+// twin, and a key is accepted only after its bytes compared equal.
+constexpr uint32_t PRIO_HDR_W = 4;
+constexpr uint32_t PRIO_CLASSES = 8;        // TM_PRIO_MAX_CLASSES
+constexpr uint32_t PRIO_NOCLASS = 0xFF;     // TM_PRIO_NOCLASS
+constexpr uint32_t PRIO_MAX_KEY = 4096;     // TM_MAX_TOPIC_LEN
+constexpr uint32_t PRIO_META_USED = 1u << 31, PRIO_META_CLS_SHIFT = 13, PRIO_META_HASH_SHIFT = 21;
+constexpr uint32_t PRIO_SESSION_WORDS = 2 + PRIO_CLASSES;   // tm_session_prio as u32 words
+constexpr uint32_t PRIO_SCAN_TILE = 1024;   // waves per block of the class-count scan
+struct PrioLookupArgs {
+    const uint8_t* bytes;     // the batch's topic bytes (the tokeniser's input), 16-B aligned and padded
+    const uint64_t* offs;     // n + 1
+    uint64_t base;            // topic i = bytes[offs[i] - base .. offs[i + 1] - base)
+    const uint32_t* blk;      // the call's tables
+    uint32_t n, ntab;
+    uint8_t* out;             // ntab x n: the class of publish i in table t
+};
+struct PrioArgs {
+    const uint32_t* publishes;   // D
+    const uint8_t* pcp;          // ntab x n (PrioLookupArgs::out)
+    const uint32_t* prio;        // NP x {subscriber, table, plen[8]}
+    uint32_t n, ntab, NP, dtab;  // dtab: the table of a subscriber not in prio, or NONE
+    uint32_t ncls, pad0;         // the most classes any of the call's tables has
+    uint4* ptab;                 // R: {table or NONE, index into prio or NONE, mqueue_max, 0}
+    uint32_t* chbase;            // R x 8: entering deliveries per class of the head's wave before the head
+    uint32_t* cw;                // (nwaves + 1) x 8: entering deliveries per wave and class, scanned in place (+ cbs)
+    uint32_t* cbs;               // scan blocks x 8
+    uint32_t* ctot;              // 8: entering deliveries per class of the batch
+    uint2* cthr;                 // R x 8: {scanned base of the inbox in class c, dnew_c}
+    uint2* prec;                 // R x 8: tm_prio_record
+    uint8_t* pclass;             // D
+};
+static_assert(std::has_unique_object_representations_v<PrioArgs>, "PrioArgs has implicit padding");
+
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
 struct RulesArgs {
     const uint32_t* nwords;   // name word ids (rule dictionary; unknown = W_UNKNOWN)
@@ -632,6 +678,10 @@ hipError_t launch_deliver_compact(const DeliverArgs& a, hipStream_t s);
 // window: state per inbox, counts per wave, the scan, the plan per inbox
 // (writes rec), the disposition and packet id of every delivery, the totals
 hipError_t launch_window(const WindowArgs& a, hipStream_t s);
+// window with priority tables: the class of every (table, publish); then the
+// window's own kernels with the per-class counts, scan, plan and classify
+hipError_t launch_prio_lookup(const PrioLookupArgs& a, hipStream_t s);
+hipError_t launch_window_prio(const WindowArgs& a, const PrioArgs& p, hipStream_t s);
 hipError_t launch_fan_globalize(const FanArgs& a, hipStream_t s);   // block-relative moff -> global
 uint32_t fan_scan_tile();   // match entries per scan block
 uint32_t fan_fill_tile();   // deliveries per fill block

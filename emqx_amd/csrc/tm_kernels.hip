@@ -3234,6 +3234,303 @@ __device__ __forceinline__ bool dd_equal(const uint8_t* bytes, const uint32_t (&
     return diff == 0;
 }
 
+// ------------------- the send window over priority tables (tm_batch_window_prio)
+//
+// emqx_mqueue:in/2 with a p_table (src/emqx_mqueue.erl:151-168): Priority =
+// get_priority(Topic, PTab, Dp) picks one of the table's classes, and every
+// class is a bounded queue of its own.  Which deliveries are sent is the old
+// plan's business (the counted rank against nsend); the ENTERING deliveries
+// (counted rank >= nsend) of a tabled inbox then need their rank within
+// (inbox, class), found the way the window finds the counted rank, per class:
+//   lookup    per (table, publish): the class of the publish's topic bytes
+//   session   per inbox: its table and its entry of `prio` (one search)
+//   count     per wave: its entering deliveries per class, one ballot per
+//             class and round; the lane on an inbox head stores the wave's
+//             counts before it
+//   scan      the waves' counts per class, two levels (tiles of
+//             PRIO_SCAN_TILE waves, then the tiles' sums)
+//   plan      per inbox: per class base, total, the closed form in 64 bits ->
+//             {base, dnew} and the class record; the inbox's record holds
+//             the sums
+//   classify  per delivery: the old classify, with DROP_FULL / QUEUED of a
+//             tabled inbox decided by the class rank; pclass
+// An inbox without a table goes through the same kernels and keeps what the
+// old plan gave it.  No kernel waits for another workgroup, no thread loops
+// over an inbox, no atomics on the deliveries.
+
+// the len bytes at b of `bytes` (first 64 in c) equal to the len bytes at ob of `other`?
+__device__ __forceinline__ bool prio_equal(const uint8_t* bytes, const uint32_t (&c)[16], uint64_t b,
+                                           const uint8_t* other, uint64_t ob, uint32_t len) {
+    uint32_t o[16];
+    dd_load64(other, ob, len, o);
+    uint32_t diff = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 16; ++j) diff |= c[j] ^ o[j];
+    for (uint32_t k = 64; diff == 0 && k < len; k += 8)   // (keys over 64 bytes: rare, kept narrow)
+        diff |= low_bytes(dd_u64(bytes, b + k) ^ dd_u64(other, ob + k), len - k < 8u ? len - k : 8u) != 0;
+    return diff == 0;
+}
+
+// One thread per publish, one grid row per table.  A hash collision costs a
+// probe: a slot is accepted only when hash bits, length and bytes all agree.
+__global__ __launch_bounds__(256) void tm_prio_lookup(PrioLookupArgs a) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x, t = blockIdx.y;
+    if (i >= a.n) return;
+    const uint32_t* hd = a.blk + PRIO_HDR_W * t;
+    const uint2* slots = reinterpret_cast<const uint2*>(a.blk + hd[0]);
+    const uint8_t* keys = reinterpret_cast<const uint8_t*>(a.blk) + hd[1];
+    const uint32_t mask = hd[2];
+    uint32_t cls = hd[3];
+    const uint64_t b = a.offs[i] - a.base, l64 = a.offs[i + 1] - a.offs[i];
+    if (l64 <= PRIO_MAX_KEY) {   // a longer topic equals no key
+        const uint32_t len = (uint32_t)l64;
+        uint32_t c[16];
+        dd_load64(a.bytes, b, len, c);
+        const uint64_t h = dd_hash(a.bytes, b, len, c);
+        const uint32_t want = PRIO_META_USED | (uint32_t)(h >> 54) << PRIO_META_HASH_SHIFT | len;
+        uint32_t s = (uint32_t)h & mask;
+        for (uint32_t k = 0; k <= mask; ++k, s = (s + 1) & mask) {
+            const uint2 e = slots[s];
+            if (!e.y) break;
+            if ((e.y & ~(0xFFu << PRIO_META_CLS_SHIFT)) == want && prio_equal(a.bytes, c, b, keys, e.x, len)) {
+                cls = (e.y >> PRIO_META_CLS_SHIFT) & 0xFFu;
+                break;
+            }
+        }
+    }
+    a.out[(uint64_t)t * a.n + i] = (uint8_t)cls;
+}
+
+__global__ __launch_bounds__(256) void tm_winp_session(WindowArgs a, PrioArgs p) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint32_t S = a.subscribers[r];
+    uint32_t lo = 0, hi = p.NP;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (p.prio[(uint64_t)mid * PRIO_SESSION_WORDS] < S) lo = mid + 1; else hi = mid;
+    }
+    const uint4 s = a.st[r];   // tm_window_state's {P | flags << 16, F, L, M}
+    uint4 g = make_uint4(p.dtab, NONE, s.w, 0u);
+    if (lo < p.NP && p.prio[(uint64_t)lo * PRIO_SESSION_WORDS] == S) {
+        g.x = p.prio[(uint64_t)lo * PRIO_SESSION_WORDS + 1];
+        g.y = lo;
+    }
+    if (g.x >= p.ntab || ((s.x >> 16) & WIN_HOST)) g.x = g.y = NONE;   // TM_SESS_HOST wins over a table
+    p.ptab[r] = g;
+}
+
+// the scanned per-class counts before wave gw (after the scan)
+__device__ __forceinline__ uint32_t winp_scanned(const PrioArgs& p, uint32_t gw, uint32_t c) {
+    return p.cw[(uint64_t)gw * PRIO_CLASSES + c] + p.cbs[(uint64_t)(gw / PRIO_SCAN_TILE) * PRIO_CLASSES + c];
+}
+
+// after tm_window_plan: st[r] = {P | flags << 16, base, nsend, .}
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_winp_count(WindowArgs a, PrioArgs p) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    uint32_t crun[PRIO_CLASSES] = {};
+    if (wbase < a.D) {
+        uint32_t hb = win_heads_before(a, (uint32_t)wbase);
+        uint32_t run = win_scanned(a, gw), bad = 0;
+#pragma unroll 1
+        for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+            const uint64_t q = wbase + r * 64 + lane;
+            const bool on = q < a.D;
+            const uint64_t hm = win_head_mask(a, wbase + r * 64);
+            const bool head = (hm >> lane) & 1ull;
+            const uint32_t ri = hb + inbox_mbcnt(hm) + (head ? 1u : 0u) - 1u;
+            hb += (uint32_t)__popcll(hm);
+            const bool ok = on && ri < a.R;
+            const uint4 pl = ok ? a.st[ri] : make_uint4(WIN_HOST << 16, 0u, 0u, 0u);
+            const uint32_t flags = pl.x >> 16;
+            const uint32_t qos = ok ? a.msg[q] & MSG_QOS : 0u;
+            const bool counted = ok && win_counted(flags, qos);
+            const uint64_t cm = __ballot(counted);
+            const uint32_t rank = run + inbox_mbcnt(cm) - pl.y;
+            run += (uint32_t)__popcll(cm);
+            const uint32_t tb = ok ? p.ptab[ri].x : NONE;
+            bool ent = counted && rank >= pl.z && tb < p.ntab;
+            uint32_t cls = PRIO_NOCLASS;
+            if (ent) {
+                const uint32_t pub = p.publishes[q];
+                if (pub < p.n) cls = p.pcp[(uint64_t)tb * p.n + pub];
+                else { ent = false; ++bad; }
+            }
+            uint32_t hv[PRIO_CLASSES];
+#pragma unroll
+            for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+                hv[c] = crun[c];
+                if (c < p.ncls) {   // (wave-uniform)
+                    const uint64_t m = __ballot(ent && cls == c);
+                    hv[c] += inbox_mbcnt(m);
+                    crun[c] += (uint32_t)__popcll(m);
+                }
+            }
+            if (ok && head) {
+                uint4* hbp = reinterpret_cast<uint4*>(p.chbase + (uint64_t)ri * PRIO_CLASSES);
+                hbp[0] = make_uint4(hv[0], hv[1], hv[2], hv[3]);
+                hbp[1] = make_uint4(hv[4], hv[5], hv[6], hv[7]);
+            }
+        }
+        if (bad) atomicAdd(a.d_tot + 1, bad);
+    }
+    if (lane == 0) {
+        uint4* wp = reinterpret_cast<uint4*>(p.cw + (uint64_t)gw * PRIO_CLASSES);
+        wp[0] = make_uint4(crun[0], crun[1], crun[2], crun[3]);
+        wp[1] = make_uint4(crun[4], crun[5], crun[6], crun[7]);
+    }
+}
+static_assert(PRIO_CLASSES == 8, "two uint4 per class vector");
+
+// Level one of the class-count scan: a block owns PRIO_SCAN_TILE waves, thread
+// (segment sg, class c) 32 of them; exclusive in place, the tile's sums to cbs.
+__global__ __launch_bounds__(256) void tm_winp_scan_tiles(PrioArgs p, uint32_t nwaves) {
+    __shared__ uint32_t seg[32][PRIO_CLASSES];
+    const uint32_t c = threadIdx.x & 7u, sg = threadIdx.x >> 3;
+    const uint32_t w0 = blockIdx.x * PRIO_SCAN_TILE + sg * 32u;
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < 32u; ++i)
+        if (w0 + i < nwaves) sum += p.cw[(uint64_t)(w0 + i) * PRIO_CLASSES + c];
+    seg[sg][c] = sum;
+    __syncthreads();
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < sg; ++k) run += seg[k][c];
+    if (sg == 31u) p.cbs[(uint64_t)blockIdx.x * PRIO_CLASSES + c] = run + sum;
+    for (uint32_t i = 0; i < 32u; ++i)
+        if (w0 + i < nwaves) {
+            const uint64_t at = (uint64_t)(w0 + i) * PRIO_CLASSES + c;
+            const uint32_t v = p.cw[at];
+            p.cw[at] = run;
+            run += v;
+        }
+}
+static_assert(PRIO_SCAN_TILE == 32 * 32, "32 segments of 32 waves");
+
+// Level two: the tiles' sums, exclusive in place, and the batch's totals (one
+// thread per class; at most 2^32 / (1024 * PRIO_SCAN_TILE) = 4096 tiles).
+__global__ __launch_bounds__(64) void tm_winp_scan_sums(PrioArgs p, uint32_t nblocks) {
+    const uint32_t c = threadIdx.x;
+    if (c >= PRIO_CLASSES) return;
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < nblocks; ++k) {
+        const uint32_t v = p.cbs[(uint64_t)k * PRIO_CLASSES + c];
+        p.cbs[(uint64_t)k * PRIO_CLASSES + c] = run;
+        run += v;
+    }
+    p.ctot[c] = run;
+}
+
+__global__ __launch_bounds__(256) void tm_winp_plan(WindowArgs a, PrioArgs p) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint4 s = a.st[r];   // tm_window_plan's: an inbox it refused is WIN_HOST
+    const uint4 g = p.ptab[r];
+    uint2* thr = p.cthr + (uint64_t)r * PRIO_CLASSES;
+    uint2* rec = p.prec + (uint64_t)r * PRIO_CLASSES;
+    if (((s.x >> 16) & WIN_HOST) || g.x >= p.ntab) {
+#pragma unroll
+        for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+            thr[c] = make_uint2(0u, 0u);
+            rec[c] = make_uint2(0u, 0u);
+        }
+        return;
+    }
+    const uint32_t o = a.off[r], on = r + 1 < a.R ? a.off[r + 1] : a.D;   // (tm_window_plan checked them)
+    const uint32_t wo = o / INBOX_WAVE_PAIRS, wn = on / INBOX_WAVE_PAIRS;
+    const bool last = r + 1 >= a.R;
+    const uint32_t M = g.z;
+    const uint32_t* plen = g.y < p.NP ? p.prio + (uint64_t)g.y * PRIO_SESSION_WORDS + 2 : nullptr;
+    uint32_t nq = 0, nold = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+        const uint32_t base = winp_scanned(p, wo, c) + p.chbase[(uint64_t)r * PRIO_CLASSES + c];
+        const uint32_t next = last ? p.ctot[c] : winp_scanned(p, wn, c) + p.chbase[(uint64_t)(r + 1) * PRIO_CLASSES + c];
+        const uint32_t E = next - base;   // entering deliveries of the inbox in class c
+        const uint32_t L = plen ? plen[c] : 0u;
+        const uint64_t over = (uint64_t)L + E;
+        const uint64_t drops = (M && over > M) ? over - M : 0ull;
+        const uint32_t dold = (uint32_t)min<uint64_t>(drops, L);
+        const uint32_t dnew = (uint32_t)min<uint64_t>(drops - dold, E);
+        thr[c] = make_uint2(base, dnew);
+        rec[c] = make_uint2(E - dnew, dold);
+        nq += E - dnew;
+        nold += dold;
+    }
+    const uint4 old = a.rec[r];   // next_pkt_id and n_inflight do not depend on the queue
+    a.rec[r] = make_uint4(old.x, old.y, nq, nold);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_winp_classify(WindowArgs a, PrioArgs p) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    uint32_t tot[WIN_NDISP] = {};
+    if (wbase < a.D) {
+        uint32_t crun[PRIO_CLASSES];
+#pragma unroll
+        for (uint32_t c = 0; c < PRIO_CLASSES; ++c) crun[c] = winp_scanned(p, gw, c);
+        uint32_t hb = win_heads_before(a, (uint32_t)wbase);
+        uint32_t run = win_scanned(a, gw), bad = 0;
+#pragma unroll 1
+        for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+            const uint64_t q = wbase + r * 64 + lane;
+            const bool on = q < a.D;
+            const uint64_t hm = win_head_mask(a, wbase + r * 64);
+            const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
+            hb += (uint32_t)__popcll(hm);
+            const bool ok = on && ri < a.R;
+            if (on && !ok) ++bad;
+            const uint4 pl = ok ? a.st[ri] : make_uint4(WIN_HOST << 16, 0u, 0u, 0u);
+            const uint32_t P = pl.x & 0xFFFFu, flags = pl.x >> 16;
+            const uint32_t qos = ok ? a.msg[q] & MSG_QOS : 0u;
+            const bool counted = ok && win_counted(flags, qos);
+            const uint64_t cm = __ballot(counted);
+            const uint32_t rank = run + inbox_mbcnt(cm) - pl.y;
+            run += (uint32_t)__popcll(cm);
+            const uint32_t tb = ok ? p.ptab[ri].x : NONE;
+            const bool tabled = tb < p.ntab && !(flags & WIN_HOST);
+            uint32_t cls = PRIO_NOCLASS;
+            if (tabled) {
+                const uint32_t pub = p.publishes[q];
+                if (pub < p.n) cls = p.pcp[(uint64_t)tb * p.n + pub];
+                else ++bad;
+            }
+            const bool ent = counted && rank >= pl.z && cls < PRIO_CLASSES;
+            uint32_t crank = 0;
+#pragma unroll
+            for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+                if (c < p.ncls) {   // (wave-uniform)
+                    const uint64_t m = __ballot(ent && cls == c);
+                    if (cls == c) crank = crun[c] + inbox_mbcnt(m);
+                    crun[c] += (uint32_t)__popcll(m);
+                }
+            }
+            uint32_t d, id = 0;
+            if (flags & WIN_HOST) d = 5u;                                   // TM_DISP_HOST
+            else if (!counted) d = (flags & WIN_DISCONNECTED) ? 3u : 0u;    // TM_DISP_DROP_QOS0 : TM_DISP_SEND0
+            else if (rank < pl.z) { d = 1u; id = (P - 1u + rank % 65535u) % 65535u + 1u; }   // TM_DISP_SEND
+            else if (ent) {                                                 // the class's own queue
+                const uint2 th = p.cthr[(uint64_t)ri * PRIO_CLASSES + cls];
+                d = crank - th.x < th.y ? 4u : 2u;
+            } else d = rank < pl.w ? 4u : 2u;                               // TM_DISP_DROP_FULL : TM_DISP_QUEUED
+            if (on) {
+                a.disp[q] = (uint8_t)d;
+                a.pid[q] = (uint16_t)id;
+                p.pclass[q] = (uint8_t)cls;
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < WIN_NDISP; ++k) tot[k] += (uint32_t)__popcll(__ballot(on && d == k));
+        }
+        if (bad) atomicAdd(a.d_tot + 1, bad);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < WIN_NDISP; ++k) a.wdisp[(uint64_t)gw * 8 + k] = tot[k];
+    }
+}
+
 // The global table: a slot holds ONE topic, {1 | 10 hash bits | length (13
 // bits) | byte offset (40 bits)}.  A claim probes from the hash's home; an
 // occupant with the same hash bits and length has its bytes compared, and
@@ -4630,6 +4927,34 @@ hipError_t launch_window(const WindowArgs& a, hipStream_t s) {
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(tm_window_plan, dim3((a.R + 255) / 256), dim3(256), 0, s, a);
     hipLaunchKernelGGL(tm_window_classify, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tm_window_totals, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_prio_lookup(const PrioLookupArgs& a, hipStream_t s) {
+    if (a.n && a.ntab) hipLaunchKernelGGL(tm_prio_lookup, dim3((a.n + 255) / 256, a.ntab), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// launch_window's sequence with the class kernels in it: the session's table
+// needs tm_window_state's flags and M, the class counts need the old plan's nsend
+hipError_t launch_window_prio(const WindowArgs& a, const PrioArgs& p, hipStream_t s) {
+    if (!a.D || !a.R || !a.nwaves) return hipGetLastError();
+    const uint32_t ntiles = a.nwaves / (INBOX_BLOCK / 64), rblocks = (a.R + 255) / 256;
+    const uint32_t nsb = (a.nwaves + PRIO_SCAN_TILE - 1) / PRIO_SCAN_TILE;
+    hipLaunchKernelGGL(tm_window_state, dim3(rblocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_winp_session, dim3(rblocks), dim3(256), 0, s, a, p);
+    hipLaunchKernelGGL(tm_window_count, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    ScanArgs sc{};
+    sc.count = a.wcount; sc.row_off = a.wcount; sc.block_sums = a.wbs; sc.n = a.nwaves;   // in place
+    const hipError_t e = launch_scan(sc, s, a.d_tot);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(tm_window_plan, dim3(rblocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_winp_count, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a, p);
+    hipLaunchKernelGGL(tm_winp_scan_tiles, dim3(nsb), dim3(256), 0, s, p, a.nwaves);
+    hipLaunchKernelGGL(tm_winp_scan_sums, dim3(1), dim3(64), 0, s, p, nsb);
+    hipLaunchKernelGGL(tm_winp_plan, dim3(rblocks), dim3(256), 0, s, a, p);
+    hipLaunchKernelGGL(tm_winp_classify, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a, p);
     hipLaunchKernelGGL(tm_window_totals, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }

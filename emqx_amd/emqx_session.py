@@ -116,8 +116,9 @@ def session_inboxes(mailboxes, subopts, from_=None, msg=None, upgrade_qos: bool 
 # inflight (the window's keys: a list of packet ids); mqueue, a dict
 # {store_qos0, max_len (0 = ?MAX_LEN_INFINITY), len, dropped, q: deque}.  A
 # message is any object with m["qos"]; the queue holds the objects themselves.
-# Not restated: priority tables (get_priority/3 is always the default
-# priority: one queue), maybe_ack / maybe_nack (shared deliveries), expiry.
+# Here get_priority/3 is always the default priority, one queue: priority
+# tables are restated in emqx_mqueue.py (window_one_prio) over emqx_pqueue.py.
+# Not restated: maybe_ack / maybe_nack (shared deliveries), expiry.
 
 from collections import deque  # noqa: E402
 

@@ -343,8 +343,85 @@ class Batch:
                 raise ValueError(f"session field {k} = {v} out of range")
         return N.SessionState(**vals)
 
+    def window_prio(self, sessions=None, defaults=None, tables=(), prio=None, default_table=None, from_=None, msg=None,
+                    upgrade_qos: bool = False, nl_all: bool = False, subids: bool = False):
+        """window() over mqueues with priority tables (tm_batch_window_prio).
+        tables: PTable handles (Engine.ptable); prio: iterable of dicts
+        {subscriber, table (index into tables, None = no table), plen (messages
+        per class in the queue now, at most 8)} ascending by subscriber, each
+        also listed in sessions; default_table: the table index of subscribers
+        not in prio (None = no table) -> window()'s tuple plus pclass u8[D']
+        (TM_PRIO_NOCLASS without a table) and precords u32[R', 8, 2] =
+        n_queued / n_dropped_old per class; window_info also holds
+        lookup_kernel_ms."""
+        w, pw, _keep = self._window_prio(sessions, defaults, tables, prio, default_table, from_, msg,
+                                         self._deliver_flags(upgrade_qos, nl_all, subids), 0)
+        d = w.inboxes
+        r, t = int(d.n_subscribers), int(d.n_deliveries)
+        cp = lambda p, k, ty=np.uint32: (np.ctypeslib.as_array(p, shape=(k,)).copy() if k  # noqa: E731
+                                         else np.zeros(0, ty))
+        rec = (np.ctypeslib.as_array(C.cast(w.records, C.POINTER(C.c_uint32)), shape=(r, 4)).copy() if r
+               else np.zeros((0, 4), np.uint32))
+        prec = (np.ctypeslib.as_array(C.cast(pw.precords, C.POINTER(C.c_uint32)),
+                                      shape=(r, N.TM_PRIO_MAX_CLASSES, 2)).copy() if r
+                else np.zeros((0, N.TM_PRIO_MAX_CLASSES, 2), np.uint32))
+        return ((cp(d.subscribers, r), cp(d.inbox_offsets, r + 1), cp(d.publishes, t), cp(d.filter_ids, t),
+                 cp(d.msg, t, np.uint8), cp(d.subids, t) if subids else None),
+                cp(w.disp, t, np.uint8), cp(w.packet_ids, t, np.uint16), rec, cp(pw.pclass, t, np.uint8), prec)
+
+    def window_prio_device(self, sessions=None, defaults=None, tables=(), prio=None, default_table=None, from_=None,
+                           msg=None, upgrade_qos: bool = False, nl_all: bool = False, subids: bool = False):
+        """TM_WINDOW_DEVICE: window_device()'s tuple plus the device pointers
+        of pclass and precords; window_info as window_prio()."""
+        w, pw, _keep = self._window_prio(sessions, defaults, tables, prio, default_table, from_, msg,
+                                         self._deliver_flags(upgrade_qos, nl_all, subids), N.TM_WINDOW_DEVICE)
+        d = w.inboxes
+        ptr = lambda p: C.cast(p, C.c_void_p).value  # noqa: E731
+        return (int(d.n_subscribers), int(d.n_deliveries), ptr(d.subscribers), ptr(d.inbox_offsets),
+                ptr(d.publishes), ptr(d.filter_ids), ptr(d.msg), ptr(d.subids) if subids else None,
+                ptr(w.disp), ptr(w.packet_ids), ptr(w.records), ptr(pw.pclass), ptr(pw.precords))
+
+    def _window_prio(self, sessions, defaults, tables, prio, default_table, from_, msg, dflags: int, wflags: int):
+        o, keep = self._deliver_opts(from_, msg, dflags)
+        wo = self._window_opts(sessions, defaults, wflags, keep)
+        po = N.WindowPrioOpts()
+        tables = list(tables or ())
+        po.n_tables = len(tables)
+        if tables:
+            arr = (C.c_void_p * len(tables))(*[t.h.value for t in tables])
+            keep.append(arr)
+            po.tables = C.cast(arr, C.POINTER(C.c_void_p))
+        idx = lambda t: N.TM_NONE if t is None else int(t)  # noqa: E731
+        po.default_table = idx(default_table)
+        ents = []
+        for e in (prio or []):
+            plen = [int(x) for x in e.get("plen", ())]
+            if len(plen) > N.TM_PRIO_MAX_CLASSES or any(not 0 <= x <= 0xFFFFFFFF for x in plen):
+                raise ValueError(f"plen of subscriber {e['subscriber']}: at most {N.TM_PRIO_MAX_CLASSES} u32 counts")
+            plen += [0] * (N.TM_PRIO_MAX_CLASSES - len(plen))
+            ents.append(N.SessionPrio(int(e["subscriber"]), idx(e.get("table")), (C.c_uint32 * N.TM_PRIO_MAX_CLASSES)(*plen)))
+        po.n_prio = len(ents)
+        if ents:
+            arr = (N.SessionPrio * len(ents))(*ents)
+            keep.append(arr)
+            po.prio = C.cast(arr, C.POINTER(N.SessionPrio))
+        w, pw = N.SessionWindow(), N.WindowPrio()
+        N.check(self.eng.L.tm_batch_window_prio(self.eng.h, self.h, C.byref(o), C.byref(wo), C.byref(po), C.byref(w),
+                                                C.byref(pw)), "tm_batch_window_prio")
+        self._last_deliveries = int(w.inboxes.n_deliveries)
+        self._window_info(w)
+        self.window_info["lookup_kernel_ms"] = float(pw.lookup_kernel_ms)
+        return w, pw, keep
+
     def _window(self, sessions, defaults, from_, msg, dflags: int, wflags: int):
         o, keep = self._deliver_opts(from_, msg, dflags)
+        wo = self._window_opts(sessions, defaults, wflags, keep)
+        w = N.SessionWindow()
+        N.check(self.eng.L.tm_batch_window(self.eng.h, self.h, C.byref(o), C.byref(wo), C.byref(w)), "tm_batch_window")
+        self._last_deliveries = int(w.inboxes.n_deliveries)
+        return w, keep
+
+    def _window_opts(self, sessions, defaults, wflags: int, keep):
         wo = N.WindowOpts()
         wo.flags = wflags
         wo.defaults = self._session(defaults, self.SESSION_DEFAULTS)
@@ -362,10 +439,7 @@ class Batch:
                 arr = (N.SessionState * len(ss))(*ss)
                 keep.append(arr)
                 wo.sessions = C.cast(arr, C.POINTER(N.SessionState))
-        w = N.SessionWindow()
-        N.check(self.eng.L.tm_batch_window(self.eng.h, self.h, C.byref(o), C.byref(wo), C.byref(w)), "tm_batch_window")
-        self._last_deliveries = int(w.inboxes.n_deliveries)
-        return w, keep
+        return wo
 
     def _deliver(self, from_, msg, flags: int):
         o, keep = self._deliver_opts(from_, msg, flags)
@@ -699,6 +773,35 @@ class Acl:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+class PTable:
+    """A priority table of an mqueue (tm_ptable)."""
+
+    def __init__(self, engine: "Engine", h):
+        self.engine, self._h = engine, h
+        out = (C.c_uint16 * N.TM_PRIO_MAX_CLASSES)()
+        k = engine.L.tm_ptable_classes(h, out)
+        self.classes = ["infinity" if out[i] == N.TM_PRIO_INFINITY else int(out[i]) for i in range(k)]
+
+    @property
+    def h(self):
+        if self._h is None:
+            raise RuntimeError("priority table is freed (or its engine was closed)")
+        return self._h
+
+    def free(self):
+        if self._h is not None:
+            self.engine.L.tm_ptable_free(self.engine.h, self._h)
+            self._h = None
+
+    close = free
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 
@@ -1040,6 +1143,30 @@ class Engine:
                                       int(dollar_rule), bits.ctypes.data), "tm_rules_match")
         b = np.unpackbits(bits.view(np.uint8).reshape(n, wpr * 4), axis=1, bitorder="little")
         return b[:, :r].astype(bool)
+
+    # ---- mqueue priority tables ------------------------------------------------
+    def ptable(self, entries, default="lowest") -> "PTable":
+        """A priority table (tm_ptable_create; #mqueue.p_table and default_p,
+        src/emqx_mqueue.erl:94-116): entries {topic bytes: 0..255 or
+        "infinity"}, default "lowest" | "highest" | int -> a handle with
+        .classes (the priorities highest first, "infinity" for infinity) and
+        .free().  Works on a host-only engine."""
+        enc = lambda p: N.TM_PRIO_INFINITY if p == "infinity" else int(p)  # noqa: E731
+        dflt = 0 if default == "lowest" else N.TM_PRIO_INFINITY if default in ("highest", "infinity") else int(default)
+        keys = list(entries)
+        pr = [enc(entries[k]) for k in keys]
+        if not (0 <= dflt <= 0xFFFFFFFF) or any(not 0 <= p <= 0xFFFF for p in pr):   # (ctypes would wrap them)
+            raise ValueError("priority out of range")
+        s = _pack(keys)
+        buf = np.ascontiguousarray(s.buf if s.buf.size else np.zeros(1, np.uint8))
+        offs = np.ascontiguousarray(s.offs, dtype=np.uint64)
+        prio = np.ascontiguousarray(np.asarray(pr if pr else [0], dtype=np.uint16))
+        h = C.c_void_p()
+        _acl_check(self.L, self.L.tm_ptable_create(self.h, buf.ctypes.data, offs.ctypes.data, prio.ctypes.data, len(keys),
+                                                   dflt, C.byref(h)), "tm_ptable_create")
+        t = PTable(self, h)
+        self.__dict__.setdefault("_acls", weakref.WeakSet()).add(t)   # freed with the engine, as the rule sets
+        return t
 
     # ---- batched emqx_access_control:check_acl/3 -----------------------------
     def acl_create(self, rules) -> "Acl":

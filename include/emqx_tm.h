@@ -613,7 +613,7 @@ TM_API int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* op
  * M = 0 (?MAX_LEN_INFINITY): nothing drops.
  * TM_SESS_HOST: every delivery of the inbox is TM_DISP_HOST; the record keeps
  * P and holds zeros otherwise.
- * Not here: priority tables (use TM_SESS_HOST), maybe_ack / maybe_nack of
+ * Not here: priority tables (tm_batch_window_prio, or TM_SESS_HOST), maybe_ack / maybe_nack of
  * shared deliveries (they enter the inboxes of an armed batch as plain
  * delivers, tm_batch_shared_mode), message expiry.
  * The call counts as a dispatch of the batch (pointer lifetime as
@@ -669,6 +669,110 @@ typedef struct {
 } tm_session_window;
 TM_API int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
                            tm_session_window* out);
+
+/* The send window of sessions whose mqueue has a priority table
+ * (#mqueue.p_table, src/emqx_mqueue.erl:151-168, 195-196; the zone settings
+ * mqueue_priorities / mqueue_default_priority, src/emqx_session.erl:179-180).
+ * A table (tm_ptable) maps topics to priorities 0..255 or TM_PRIO_INFINITY;
+ * Priority = get_priority(Topic, PTab, Dp) compares the publish's topic BYTES
+ * with the keys (maps:get/3, no wildcard) and gives default_priority (0 for
+ * `lowest`, TM_PRIO_INFINITY for `highest`, or an integer) to a topic the
+ * table lacks -- an empty table included (:196).  A session without a table
+ * (?NO_PRIORITY_TABLE) always uses priority 0 (:195) and is what
+ * tm_batch_window computes.
+ * tm_ptable_create: n keys, key i = topics[offsets[i] .. offsets[i + 1]); a
+ * repeated key keeps its last priority (maps:put).  The table's CLASSES are
+ * its distinct priorities together with its default, descending, infinity
+ * first: class 0 is the highest.  tm_ptable_classes writes them (as given:
+ * 0..255 or TM_PRIO_INFINITY) and returns their number.  The table belongs to
+ * the engine it was made for and is freed with tm_ptable_free before that
+ * engine is closed, as a tm_acl; both calls work on a host-only engine.  The
+ * host builds the open-addressed image the lookup kernel probes here, once.
+ * TM_EINVAL + tm_last_error(): a priority above 255 that is not
+ * TM_PRIO_INFINITY (the default included), more than TM_PRIO_MAX_CLASSES
+ * classes, a key over TM_MAX_TOPIC_LEN bytes, offsets not monotone.
+ * The two caps are design limits, not measurements: eight classes keep the
+ * per-inbox class record at 64 B and the per-round work at one ballot per
+ * class (the reference's own tables hold three priorities); sixteen tables
+ * bound the per-publish class bytes of one call.
+ *
+ * tm_batch_window_prio is tm_batch_window with tables.  The table of inbox S
+ * is tables[prio entry of S .table] when `prio` lists S, else
+ * tables[default_table] (TM_NONE: no table); a prio entry may name TM_NONE
+ * itself (that session has no table, its plen is ignored).  TM_SESS_HOST wins
+ * over a table.  Every priority class of a session is a bounded queue of its
+ * own: max_len bounds each priority separately (PLen =:= MaxLen with PLen =
+ * emqx_pqueue:plen(Priority, Q), :159-165), the message pushed out is the
+ * oldest of that priority (emqx_pqueue:out/2), and len is the sum.  Which
+ * deliveries are TM_DISP_SEND0 / SEND / DROP_QOS0 is decided exactly as in
+ * tm_batch_window, whatever the priority (the QoS-0 clause :149-150 comes
+ * first).  Of the entering deliveries class c has E_c; with L_c = plen[c]
+ * (0 for a session not in `prio`) and M = mqueue_max, in 64 bits:
+ *   drops_c = max(0, L_c + E_c - M) when M > 0, else 0
+ *   n_dropped_old_c = min(drops_c, L_c);  dnew_c = drops_c - n_dropped_old_c
+ * and an entering delivery whose 0-based rank among the entering deliveries
+ * of its inbox and class is below dnew_c is TM_DISP_DROP_FULL, the others
+ * TM_DISP_QUEUED.  out is filled exactly as tm_batch_window fills it; a tabled
+ * session's record holds the sums over its classes.  pout->pclass[q] is the
+ * class of delivery q in its session's table, for every delivery of a tabled
+ * session, sent or not; TM_PRIO_NOCLASS for a session without a table or with
+ * TM_SESS_HOST.  pout->precords[r * TM_PRIO_MAX_CLASSES + c] are class c's
+ * {n_queued, n_dropped_old} of inbox r: zeros for classes the table lacks and
+ * for sessions without a table.  A session without a table gets bit for bit
+ * what tm_batch_window gives it (n_tables = 0: every session).
+ * The classes come from a lookup kernel over the batch's device-resident topic
+ * bytes (lookup_kernel_ms; out->kernel_ms is the window kernels' time), so a
+ * batch made by tm_batch_prepare_tokens, which has none, is refused.  An
+ * armed batch (tm_batch_shared_mode) needs nothing extra: a shared delivery's
+ * topic is its publish's.  Memory mode and pointer lifetime follow
+ * TM_WINDOW_DEVICE in wopts, as for tm_batch_window; pclass and precords are
+ * device pointers exactly when the other results are.
+ * Errors as tm_batch_window (mqueue_len > mqueue_max is legal for a tabled
+ * session: each class is bounded, not the sum), and TM_EINVAL +
+ * tm_last_error() for NULL popts or pout, n_tables > TM_PRIO_MAX_TABLES, a
+ * NULL table or one of another engine, a table index >= n_tables that is not
+ * TM_NONE, prio not strictly ascending by subscriber, a prio subscriber
+ * missing from wopts->sessions, sum of plen != mqueue_len, plen[c] >
+ * mqueue_max when mqueue_max > 0, plen[c] != 0 for a class the table lacks, a
+ * tabled session (or tabled defaults) with mqueue_len > 0 and no prio entry
+ * (TM_SESS_HOST sessions are exempt from these four), a batch without a
+ * device copy of its topic bytes.  TM_ENODEV on a host-only engine.
+ * Not here: more than TM_PRIO_MAX_CLASSES classes, the group / sharded /
+ * multi-process forms, message expiry, maybe_ack / maybe_nack. */
+#define TM_PRIO_INFINITY    0xFFFFu  /* the priority `infinity` */
+#define TM_PRIO_MAX_CLASSES 8u       /* classes of one table (distinct priorities + default) */
+#define TM_PRIO_MAX_TABLES  16u      /* tables of one tm_batch_window_prio call */
+#define TM_PRIO_NOCLASS     0xFFu    /* pclass of a delivery whose session has no table */
+typedef struct tm_ptable tm_ptable;
+TM_API int tm_ptable_create(tm_engine* e, const uint8_t* topics, const uint64_t* offsets, const uint16_t* priorities,
+                            uint32_t n, uint32_t default_priority, tm_ptable** table);
+TM_API void tm_ptable_free(tm_engine* e, tm_ptable* table);
+TM_API uint32_t tm_ptable_classes(const tm_ptable* table, uint16_t out[TM_PRIO_MAX_CLASSES]);
+typedef struct {
+    uint32_t subscriber;                  /* the caller's id, as in tm_session_state */
+    uint32_t table;                       /* index into tables[], or TM_NONE: no table */
+    uint32_t plen[TM_PRIO_MAX_CLASSES];   /* messages of class c in the queue now; their sum is mqueue_len */
+} tm_session_prio;
+typedef struct {
+    tm_ptable* const*      tables;        /* n_tables; NULL when 0 */
+    uint32_t               n_tables;
+    uint32_t               n_prio;
+    const tm_session_prio* prio;          /* n_prio, strictly ascending by subscriber; NULL when 0 */
+    uint32_t               default_table; /* index into tables[] or TM_NONE: subscribers not listed in prio */
+    uint32_t               pad0;          /* 0 */
+} tm_window_prio_opts;
+typedef struct {
+    uint32_t n_queued;       /* deliveries of this batch and class in the queue at the end */
+    uint32_t n_dropped_old;  /* messages to pop from the front of that class's queue */
+} tm_prio_record;
+typedef struct {
+    const uint8_t*        pclass;           /* D' */
+    const tm_prio_record* precords;         /* R' x TM_PRIO_MAX_CLASSES */
+    float                 lookup_kernel_ms; /* device time of the class lookup */
+    uint32_t              pad0;
+} tm_window_prio;
+TM_API int tm_batch_window_prio(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
+                                const tm_window_prio_opts* popts, tm_session_window* out, tm_window_prio* pout);
 
 /* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
 /* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
