@@ -2926,9 +2926,9 @@ __global__ __launch_bounds__(256) void tm_rules_match(RulesArgs a) {
                 for (;;) {
                     if (i == nl && k == rl) { m = true; break; }
                     const uint32_t fw = k < rl ? a.rwords[rb + k] : 0u;
-                    if (k + 1 == rl && fw == W_HASH) { m = true; break; }
-                    if (i == nl || k == rl) break;
-                    if (fw == W_PLUS || fw == a.nwords[nb + i]) { ++i; ++k; continue; }
+                    // [H|T1] against [H|T2] is tried before (_, ['#']): a name's own '#' is consumed
+                    if (i < nl && k < rl && (fw == W_PLUS || fw == a.nwords[nb + i])) { ++i; ++k; continue; }
+                    m = k + 1 == rl && fw == W_HASH;
                     break;
                 }
             }

@@ -353,3 +353,325 @@ def nif_clients(clients):
     def und(x):
         return "undefined" if x is None else x
     return [(und(c.get("clientid")), und(c.get("username")), und(R.peer_tuple(c.get("peerhost")))) for c in clients]
+
+
+# ---- edge builders (test_gpu_acl_edges.py on the device, their conditions in test_acl.py) ----
+STAGE = 16384        # ACL_STAGE (tm_internal.hpp): a block whose names span more is read from global memory
+BLOCK = 256          # requests per block of tm_acl_check
+
+
+def block_spans(requests, base=0):
+    """[(b0, b1, a0)] per 256-request block, from the names' lengths alone: the
+    block's byte range and the 16-byte boundary before it, as the kernel derives them."""
+    offs = [base]
+    for _c, _a, t in requests:
+        offs.append(offs[-1] + len(t))
+    out = []
+    for t0 in range(0, len(requests), BLOCK):
+        b0, b1 = offs[t0] - base, offs[min(t0 + BLOCK, len(requests))] - base
+        out.append((b0, b1, b0 & ~15))
+    return out
+
+
+def _fit(names, total):
+    """Lengthens the names' last levels (round robin) until they hold `total` bytes."""
+    names = list(names)
+    need = total - sum(len(x) for x in names)
+    assert need >= 0, need
+    q, r = divmod(need, len(names))
+    return [x + b"p" * (q + (1 if i < r else 0)) for i, x in enumerate(names)]
+
+
+def _flip(b, at):
+    at %= len(b)
+    return b[:at] + bytes([b[at] ^ 1]) + b[at + 1:]
+
+
+def stage_case(lead, width, form, tag=b""):
+    """3 blocks (256, 256, 188 requests).  Block 0's names hold 4096 + lead
+    bytes, so block 1 starts `lead` bytes past a 16-byte boundary; block 1's
+    hold width - lead, so its b1 - a0 is `width`.  The first and last name of
+    block 1 and the last name of blocks 0 and 2 (the edge names) are each
+    allowed by one filter (form "eq": {eq, Name}; "pattern": the name with its
+    client level as %c) that follows two deny filters differing from it in the
+    first and in the last byte only.  One name of block 1 ends in an empty
+    level and is decided by a filter whose last level is '+'.
+    -> (rule terms, clients, requests, indices of the edge requests)."""
+    assert form in ("eq", "pattern") and 0 <= lead < 16
+    clients = [{"clientid": b"k0", "username": None, "peerhost": None},
+               {"clientid": b"k1", "username": None, "peerhost": None}]
+
+    def short(i, blk):
+        return b"s/k%d/%s%d%03d" % (i % 2, tag, blk, i)
+
+    def edge(what, c):
+        return b"E%s/k%d/%s/x/zQ" % (what, c, tag)
+
+    b0 = [short(i, 0) for i in range(BLOCK - 1)] + [edge(b"a", 1)]
+    b0 = _fit(b0[:-1], 4096 + lead - len(b0[-1])) + b0[-1:]
+    mid = [b"w/k%d/%s%03d/" % (i % 2, tag, i) + b"q" * 40 for i in range(BLOCK - 4)]
+    b1 = [edge(b"b", 0)] + mid[:100] + [b"m/k1/x/", b"m/k1/x"] + mid[100:] + [edge(b"c", 1)]
+    fixed = [0, 101, 102, BLOCK - 1]
+    room = width - lead - sum(len(b1[i]) for i in fixed)
+    fitted = iter(_fit([x for i, x in enumerate(b1) if i not in fixed], room))
+    b1 = [x if i in fixed else next(fitted) for i, x in enumerate(b1)]
+    b2 = [short(i, 2) for i in range(187)] + [edge(b"d", 0)]
+    names = b0 + b1 + b2
+    edges = [BLOCK - 1, BLOCK, 2 * BLOCK - 1, len(names) - 1]
+
+    def flt(name):
+        if form == "eq":
+            return ("eq", name.decode())
+        ws = name.split(b"/")
+        return b"/".join([ws[0], b"%c"] + ws[2:]).decode()
+
+    rules = []
+    for i in edges:
+        e = names[i]
+        rules.append(("deny", R.ALL, "pubsub", [flt(_flip(e, 0)), flt(_flip(e, -1))]))
+        rules.append(("allow", R.ALL, "pubsub", [flt(e)]))
+    rules += [("allow", R.ALL, "publish", ["m/%c/x/+"]),
+              ("allow", ("client", "k0"), "publish", ["s/%c/+"]),
+              ("deny", ("client", "k1"), "publish", ["s/%c/+", "w/%c/#"]),
+              ("deny", R.ALL)]
+    requests = [(int(x.split(b"/")[1][1:]), "publish", x) for x in names]
+    return rules, clients, requests, edges
+
+
+# who programs: trees over the two leaves TRUE_LEAF / FALSE_LEAF of client "k1"
+WHO_CLIENTS = [{"clientid": b"k1", "username": None, "peerhost": None},
+               {"clientid": b"k0", "username": None, "peerhost": None}]
+TRUE_LEAF, FALSE_LEAF = ("client", "k1"), ("client", "zz")
+
+
+def who_chain(depth, leaf, outer="and"):
+    """`leaf` at depth `depth` (the root is depth 1) under depth - 1
+    single-child nodes that alternate 'and' / 'or', the outermost being `outer`."""
+    ops = [outer, "or" if outer == "and" else "and"]
+    t = leaf
+    for d in range(depth - 2, -1, -1):
+        t = (ops[d % 2], [t])
+    return t
+
+
+def who_plain(tree, cid):
+    """match_who/2 restated with all / any for the trees built here."""
+    if tree[0] == "and":
+        return all([who_plain(c, cid) for c in tree[1]])
+    if tree[0] == "or":
+        return any([who_plain(c, cid) for c in tree[1]])
+    assert tree[0] == "client"
+    return cid == tree[1].encode()
+
+
+def who_depth(tree):
+    return 1 + max((who_depth(c) for c in tree[1]), default=0) if tree[0] in ("and", "or") else 1
+
+
+def who_trees(max_depth=N.TM_ACL_MAX_WHO_DEPTH):
+    """{label: who term}, all within the depth limit."""
+    out = {}
+    for outer in ("and", "or"):
+        dual = "or" if outer == "and" else "and"
+        for leaf, lname in ((TRUE_LEAF, "true"), (FALSE_LEAF, "false")):
+            out["deep %s %s" % (outer, lname)] = who_chain(max_depth, leaf, outer)
+        # a sibling at the outermost node: the oldest stack bit decides
+        first, deep = (TRUE_LEAF, FALSE_LEAF) if outer == "or" else (FALSE_LEAF, TRUE_LEAF)
+        out["deep %s sibling first" % outer] = (outer, [first, who_chain(max_depth - 1, deep, dual)])
+        out["deep %s sibling last" % outer] = (outer, [who_chain(max_depth - 1, deep, dual), first])
+        out["deep %s neutral sibling" % outer] = (outer, [deep, who_chain(max_depth - 1, first, dual)])
+    wide_or = ("or", [("client", "x%d" % i) for i in range(39)] + [TRUE_LEAF])
+    wide_and = ("and", [TRUE_LEAF] * 39 + [FALSE_LEAF])
+    wide_or0 = ("or", [("client", "x%d" % i) for i in range(40)])
+    wide_and1 = ("and", [TRUE_LEAF] * 40)
+    for name, w in (("wide or", wide_or), ("wide and", wide_and), ("wide or none", wide_or0),
+                    ("wide and every", wide_and1)):
+        out[name] = w
+        for outer in ("and", "or"):
+            out["%s under %s at depth 10" % (name, outer)] = who_chain(10, w, outer)
+    return out
+
+
+def who_case():
+    """One rule per tree of who_trees() on its own topic, both clients asking
+    -> (rule terms, clients, requests, labels, plain expectations [(verdict, rule)])."""
+    trees = who_trees()
+    labels = list(trees)
+    rules = [("allow", trees[k], "pubsub", ["w/%d" % j]) for j, k in enumerate(labels)]
+    requests, plain = [], []
+    for j, k in enumerate(labels):
+        for ci, c in enumerate(WHO_CLIENTS):
+            requests.append((ci, "publish" if ci else "subscribe", b"w/%d" % j))
+            ok = who_plain(trees[k], c["clientid"])
+            plain.append((N.TM_ACL_ALLOW, j) if ok else (N.TM_ACL_NOMATCH, N.TM_NONE))
+    return rules, WHO_CLIENTS, requests, labels, plain
+
+
+# address ranges
+IP_WORDS = [0x00000000, 0x00000001, 0x01000000, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF]
+IP_REST = [0x20010DB8, 0x80000001, 0x01000000, 0x7FFFFF00]      # the words a v6 range does not vary
+
+
+def ip_tuple(x, fam):
+    import ipaddress
+    return R._inet_tuple(ipaddress.IPv4Address(x) if fam == 4 else ipaddress.IPv6Address(x))
+
+
+def ip_text(x, fam):
+    import ipaddress
+    return str(ipaddress.IPv4Address(x) if fam == 4 else ipaddress.IPv6Address(x))
+
+
+def ip_case():
+    """Ranges whose ends differ in one 32-bit word only (each word of a v6
+    address, and v4), the word's values drawn from IP_WORDS, probed at
+    lo-1, lo, lo+1, hi-1, hi, hi+1 and at the varied word's own neighbours;
+    lo == hi; lo > hi; the other family with the same leading bytes; no peerhost.
+    -> (rule terms, clients, requests, plain expectations, [(lo, hi, fam)] per rule)."""
+    import ipaddress
+    ranges = []
+    pairs = [(a, b) for a in IP_WORDS for b in IP_WORDS if a < b]
+    for q in range(4):
+        sh = 32 * (3 - q)
+        rest = sum(w << (32 * (3 - i)) for i, w in enumerate(IP_REST) if i != q)
+        for a, b in pairs:
+            ranges.append((rest | a << sh, rest | b << sh, 6, sh))
+    for a, b in pairs:
+        ranges.append((a, b, 4, 0))
+    for w in IP_WORDS:                                   # lo == hi
+        ranges.append((w, w, 4, 0))
+        ranges.append((w << 64 | w, w << 64 | w, 6, 0))
+    ranges.append((0x80000000, 0x7FFFFFFF, 4, 0))        # lo > hi: nobody
+    ranges.append((0x01000000, 0x00000001, 4, 0))
+    ranges.append((IP_REST[0] << 96 | 1 << 32, IP_REST[0] << 96 | 1, 6, 0))
+    ranges.append((1 << 127, (1 << 127) - 1, 6, 0))
+    # the other family with the same leading bytes
+    ranges.append((IP_REST[0] << 96, IP_REST[0] << 96 | 0xFFFF, 6, 0))
+    ranges.append((IP_REST[0], IP_REST[0], 4, 0))
+    clients, index = [{"clientid": b"c", "username": None, "peerhost": None}], {}
+
+    def client(x, fam):
+        if (x, fam) not in index:
+            index[(x, fam)] = len(clients)
+            clients.append({"clientid": b"c", "username": None, "peerhost": ip_text(x, fam)})
+        return index[(x, fam)]
+
+    rules, requests, plain = [], [], []
+    for j, (lo, hi, fam, sh) in enumerate(ranges):
+        top = (1 << (32 if fam == 4 else 128)) - 1
+        rules.append(("allow", ("ipaddr", (ip_tuple(lo, fam), ip_tuple(hi, fam), 0)), "pubsub", ["r/%d" % j]))
+        probes = {lo - 1, lo, lo + 1, hi - 1, hi, hi + 1, (lo + hi) // 2,
+                  lo - (1 << sh), lo + (1 << sh), hi - (1 << sh), hi + (1 << sh),
+                  lo >> sh << sh, hi | ((1 << sh) - 1)}
+        asks = [(p, fam) for p in sorted(probes) if 0 <= p <= top]
+        if fam == 6:
+            asks += [(lo >> 96, 4), (hi >> 96, 4)]
+        else:
+            asks += [(lo << 96, 6), (hi << 96, 6)]
+        for p, pf in asks:
+            requests.append((client(p, pf), "publish", b"r/%d" % j))
+            host = ipaddress.ip_address(clients[requests[-1][0]]["peerhost"])
+            ok = host.version == fam and lo <= int(host) <= hi
+            plain.append((N.TM_ACL_ALLOW, j) if ok else (N.TM_ACL_NOMATCH, N.TM_NONE))
+        requests.append((0, "publish", b"r/%d" % j))     # no peerhost
+        plain.append((N.TM_ACL_NOMATCH, N.TM_NONE))
+    return rules, clients, requests, plain, [r[:3] for r in ranges]
+
+
+# levels and variables
+def _level_strings(alphabet):
+    import itertools
+    return [b"/".join(ws) for k in (1, 2, 3) for ws in itertools.product(alphabet, repeat=k)]
+
+
+LEVEL_FILTERS = _level_strings([b"a", b"", b"+", b"#", b"%c", b"%u"])
+LEVEL_NAMES = _level_strings([b"a", b"", b"+", b"#", b"cid", b"b"])
+LEVEL_EXTRA_NAMES = [b"%c", b"%u", b"a/%c", b"%u/a", b"%c/%u", b"a/%u/"]    # what an unfed %c / %u level equals
+LEVEL_CLIENTS = [{"clientid": b"cid", "username": b"b", "peerhost": None},
+                 {"clientid": None, "username": b"b", "peerhost": None},
+                 {"clientid": b"cid", "username": None, "peerhost": None}]
+
+
+def level_case(f):
+    """One filter as a pattern (publish) and as {eq, _} (subscribe) against
+    every name, for each of LEVEL_CLIENTS -> (rule terms, clients, requests)."""
+    rules = [("allow", R.ALL, "publish", [f.decode()]), ("deny", R.ALL, "subscribe", [("eq", f.decode())])]
+    requests = [(c, acc, x) for c in range(len(LEVEL_CLIENTS)) for acc in ("publish", "subscribe")
+                for x in LEVEL_NAMES + LEVEL_EXTRA_NAMES]
+    return rules, LEVEL_CLIENTS, requests
+
+
+def max_shape_case():
+    """Names of 2,048 one-byte levels (4,095 bytes), and with one more byte
+    (a longer last level; an empty 2,049th level), against 2,048-level filters:
+    '+' at every level, '#' after 2,047 levels, %c last, {eq, _} of the full
+    4,096 bytes and of its copy differing in the last byte.
+    -> (rule terms, clients, requests)."""
+    n4095 = b"/".join([b"a"] * 2048)
+    assert len(n4095) == 4095
+    long_a, long_s = n4095 + b"a", n4095 + b"/"
+    assert len(long_a) == len(long_s) == N.TM_MAX_TOPIC_LEN
+    other = long_a[:-1] + b"b"
+    head = "a/" * 2047
+    varc, hsh, plus = head + "%c", head + "#", "/".join(["+"] * 2048)
+    assert (len(varc), len(hsh), len(plus)) == (4096, 4095, 4095)
+    rules = [("deny", ("client", "e"), "pubsub", [("eq", other.decode())]),
+             ("allow", ("client", "e"), "pubsub", [("eq", long_a.decode())]),
+             ("allow", R.ALL, "pubsub", [varc]),
+             ("deny", R.ALL, "publish", [hsh]),
+             ("allow", R.ALL, "subscribe", [plus])]
+    ids = [b"e", b"a", b"aa", b"aaa", b"a" * 4097, b"", None, b"ab"]
+    clients = [{"clientid": i, "username": None, "peerhost": None} for i in ids]
+    requests = [(c, acc, x) for c in range(len(ids)) for x in (n4095, long_a, long_s, other)
+                for acc in ("publish", "subscribe")]
+    return rules, clients, requests
+
+
+# waves and tails
+WAVE_RULES = 48
+
+
+def wave_case(n, final=True):
+    """48 rules, rule j allowing client k<j> alone on t/#, then {deny, all}
+    (left out with final=False).  The requests walk the 49 clients (the 49th
+    passes no who) with stride 5, so neighbouring lanes decide at different
+    rules; the last request's name is under no rule's filter.
+    -> (rule terms, clients, requests)."""
+    rules = [("allow", ("client", "k%d" % j), "pubsub", ["t/#"]) for j in range(WAVE_RULES)]
+    if final:
+        rules.append(("deny", R.ALL))
+    clients = [{"clientid": b"k%d" % j, "username": None, "peerhost": None} for j in range(WAVE_RULES)]
+    clients.append({"clientid": b"nobody", "username": None, "peerhost": None})
+    requests = [((i * 5) % 49, "publish" if i % 3 else "subscribe", b"t/%d" % i) for i in range(n)]
+    requests[-1] = (requests[-1][0], "publish", b"u/%d" % n)
+    return rules, clients, requests
+
+
+def slice_case(total=70000):
+    """The wave pattern (513 requests) and the stage pattern (700) repeated to
+    `total` requests under one rule list -> (rule terms, clients, requests, period)."""
+    wr, wc, wq = wave_case(513, final=False)
+    sr, _sc, sq, _e = stage_case(1, STAGE, "pattern")
+    period = wq + sq                     # the stage pattern's clients k0 / k1 are the wave's first two
+    reps = -(-total // len(period))
+    return wr + sr, wc, (period * reps)[:total], len(period)
+
+
+# tm_rules_match
+RULES_SPECIAL = [b"", b"/", b"#", b"+", b"a/#", b"#/a"]
+
+
+def rules_match_case():
+    """257 names and 65 rules from the generator of test_gpu_rules.py plus
+    RULES_SPECIAL; the tests take prefixes of both."""
+    rng = random.Random(8)
+    alpha = [b"a", b"b", b"", b"$a", b"%", b"!", b"c", b"x"]
+    names = [b"/".join(rng.choice(alpha) for _ in range(rng.randint(1, 4))) for _ in range(257)]
+    rules = [b"/".join(rng.choice(alpha[:3] + [b"+", b"+", b"#"]) for _ in range(rng.randint(1, 3))) for _ in range(65)]
+    for i, s in enumerate(RULES_SPECIAL):
+        names[3 + 40 * i] = s
+        rules[2 + 9 * i] = s
+    # the rules a tested r ends on each match some names and not others
+    for at, f in ((0, b"a/#"), (30, b"b/#"), (31, b"+/a"), (32, b"+/+"), (63, b"a/+/#"), (64, b"+/b/#")):
+        rules[at] = f
+    return names, rules

@@ -116,6 +116,141 @@ def test_random_generator_meets_the_floors():
     K.assert_floors(v, r, k)
 
 
+# ---- the edge builders' conditions (test_gpu_acl_edges.py runs them on the device) -------------
+@pytest.mark.parametrize("form", ["eq", "pattern"])
+@pytest.mark.parametrize("width", [K.STAGE, K.STAGE + 1])
+@pytest.mark.parametrize("lead", [0, 1, 15])
+def test_stage_case_arithmetic(lead, width, form):
+    """Block 1 starts `lead` bytes past a 16-byte boundary and spans `width`
+    from it; the last block is partial and ends inside a 16-byte line; the edge
+    names are decided by their own rule, which a changed first or last byte
+    turns into the deny before it."""
+    terms, clients, requests, edges = K.stage_case(lead, width, form, tag=b"%d%d" % (lead, width & 1))
+    assert len(requests) == 2 * K.BLOCK + 188 and edges == [255, 256, 511, 699]
+    (a0, a1, aa), (b0, b1, ba), (c0, c1, ca) = K.block_spans(requests)
+    assert (a0, aa, a1) == (0, 0, 4096 + lead) and a1 - aa <= K.STAGE
+    assert b0 % 16 == lead and ba == b0 - lead and b1 - ba == width
+    assert c1 - ca <= K.STAGE and (c1 - ca) % 16 != 0
+    assert all(len(q[2]) < 256 for q in requests)
+    compiled = [R.compile(t) for t in terms]
+    kinds = set()
+    for k, i in enumerate(edges):
+        c, access, name = requests[i]
+        client = K.full_client(clients[c])
+        v, j, kind = K.decide(compiled, client, access, name)
+        assert (v, j) == (N.TM_ACL_ALLOW, 2 * k + 1)
+        kinds.add(kind)
+        for at in (0, -1):
+            assert K.decide(compiled, client, access, K._flip(name, at))[:2] == (N.TM_ACL_DENY, 2 * k)
+        for cut in (name[1:], name[:-1]):               # a dropped edge byte: neither
+            assert K.decide(compiled, client, access, cut)[1] not in (2 * k, 2 * k + 1)
+    assert kinds == {form}
+    at = [q[2] for q in requests].index(b"m/k1/x/")
+    assert K.BLOCK < at < 2 * K.BLOCK - 1
+    assert K.decide(compiled, K.full_client(clients[1]), "publish", b"m/k1/x/")[:2] == (N.TM_ACL_ALLOW, 8)
+    assert terms[8][3] == ["m/%c/x/+"]
+    assert K.decide(compiled, K.full_client(clients[1]), "publish", b"m/k1/x")[:2] == (N.TM_ACL_DENY, 11)
+    _v, r, _k = K.mirror_batch(terms, clients, requests)
+    assert set(r) == {1, 3, 5, 7, 8, 9, 10, 11}
+
+
+def test_who_trees_plain_evaluation_equals_the_mirror():
+    terms, clients, requests, labels, plain = K.who_case()
+    trees = K.who_trees()
+    assert sum(K.who_depth(t) == N.TM_ACL_MAX_WHO_DEPTH for t in trees.values()) >= 8
+    assert max(K.who_depth(t) for t in trees.values()) == N.TM_ACL_MAX_WHO_DEPTH
+    assert K.who_depth(K.who_chain(33, K.TRUE_LEAF)) == 33
+    assert K.who_depth(trees["wide or under and at depth 10"]) == 11
+    for k in ("wide or", "wide and"):
+        assert len(trees[k][1]) == 40
+    # only the last child decides the wide nodes
+    assert [K.who_plain(c, b"k1") for c in trees["wide or"][1]] == [False] * 39 + [True]
+    assert [K.who_plain(c, b"k1") for c in trees["wide and"][1]] == [True] * 39 + [False]
+    v, r, _ = K.mirror_batch(terms, clients, requests)
+    assert list(zip(v, r)) == plain
+    k1 = {labels[i // 2]: p[0] == N.TM_ACL_ALLOW for i, p in enumerate(plain) if i % 2 == 0}
+    assert k1["deep and true"] and k1["deep or true"] and not k1["deep and false"] and not k1["deep or false"]
+    assert k1["deep or sibling first"] and not k1["deep and sibling first"]
+    assert k1["wide or"] and not k1["wide and"] and k1["wide and every"] and not k1["wide or none"]
+    assert all(p == (N.TM_ACL_NOMATCH, N.TM_NONE) for p in plain[1::2])       # client k0 passes none of them
+
+
+def test_address_table_integer_compare_equals_the_mirror():
+    import ipaddress
+    terms, clients, requests, plain, ranges = K.ip_case()
+    v, r, _ = K.mirror_batch(terms, clients, requests)
+    assert list(zip(v, r)) == plain
+    # each word of a v6 address, and v4, varies alone in some range, with every pair of word values
+    seen = set()
+    for lo, hi, fam in ranges:
+        if lo < hi:
+            diff = lo ^ hi
+            words = [q for q in range(4) if (diff >> (32 * (3 - q))) & 0xFFFFFFFF] if fam == 6 else ["v4"]
+            if len(words) == 1:
+                sh = 0 if fam == 4 else 32 * (3 - words[0])
+                seen.add((words[0], (lo >> sh) & 0xFFFFFFFF, (hi >> sh) & 0xFFFFFFFF))
+    pairs = [(a, b) for a in K.IP_WORDS for b in K.IP_WORDS if a < b]
+    assert len(pairs) == 15
+    for w in (0, 1, 2, 3, "v4"):
+        assert all((w, a, b) in seen for a, b in pairs), w
+    # both ends and their neighbours are probed, in the range's own family
+    asked = {}
+    for (c, _a, t), p in zip(requests, plain):
+        h = clients[c]["peerhost"]
+        asked.setdefault(int(t[2:]), set()).add(None if h is None else
+                                                (ipaddress.ip_address(h).version, int(ipaddress.ip_address(h))))
+    for j, (lo, hi, fam) in enumerate(ranges):
+        top = (1 << (32 if fam == 4 else 128)) - 1
+        for p in (lo - 1, lo, lo + 1, hi - 1, hi, hi + 1):
+            assert not 0 <= p <= top or (fam, p) in asked[j], (j, hex(p))
+        assert None in asked[j] and any(x is not None and x[0] != fam for x in asked[j])
+    assert sum(p[0] == N.TM_ACL_ALLOW for p in plain) > 300 and sum(p[0] == N.TM_ACL_NOMATCH for p in plain) > 300
+
+
+def test_level_table_match_share():
+    """The cross product's pattern form for the client with both fields: 2 to
+    10 % of the pairs match, among them filters ending in '#', holding '+',
+    holding %c and holding an empty level."""
+    assert len(K.LEVEL_FILTERS) == len(set(K.LEVEL_FILTERS)) == 258
+    assert len(K.LEVEL_NAMES) == len(set(K.LEVEL_NAMES)) == 258
+    client = K.full_client(K.LEVEL_CLIENTS[0])
+    assert (client["clientid"], client["username"]) == (b"cid", b"b")
+    hits = []
+    for f in K.LEVEL_FILTERS:
+        rule = R.compile(("allow", R.ALL, "publish", [f.decode()]))
+        hits += [f for x in K.LEVEL_NAMES if R.match(client, x, rule) != "nomatch"]
+    share = len(hits) / (258 * 258)
+    assert 0.02 <= share <= 0.10, share
+    assert any(f.endswith(b"#") for f in hits) and any(b"+" in f.split(b"/") for f in hits)
+    assert any(b"%c" in f.split(b"/") for f in hits) and any(b"" in f.split(b"/") for f in hits)
+    # an undefined field leaves %c / %u literal: it equals a name level spelled the same
+    terms, clients, requests = K.level_case(b"a/%c")
+    v, _r, _k = K.mirror_batch(terms, clients, requests)
+    got = {(c, acc, x) for (c, acc, x), y in zip(requests, v) if y != N.TM_ACL_NOMATCH}
+    assert got == {(0, "publish", b"a/cid"), (2, "publish", b"a/cid"), (1, "publish", b"a/%c"),
+                   (0, "subscribe", b"a/%c"), (1, "subscribe", b"a/%c"), (2, "subscribe", b"a/%c")}
+
+
+def test_max_shape_and_wave_cases():
+    terms, clients, requests = K.max_shape_case()
+    assert {len(q[2]) for q in requests} == {4095, 4096}
+    assert max(len(t) for rule in terms for t in (x[1] if isinstance(x, tuple) else x for x in rule[3])) == 4096
+    assert {len(c["clientid"]) for c in clients if c["clientid"] is not None} >= {0, 1, 2, 3, 4097}
+    _v, r, _k = K.mirror_batch(terms, clients, requests)
+    assert set(r) == {0, 1, 2, 3, 4, N.TM_NONE}
+    for n in (1, 63, 64, 65, 255, 256, 257, 511, 513):
+        for final in (True, False):
+            terms, clients, requests = K.wave_case(n, final)
+            v, r, _k = K.mirror_batch(terms, clients, requests)
+            assert (v[-1], r[-1]) == ((N.TM_ACL_DENY, 48) if final else (N.TM_ACL_NOMATCH, N.TM_NONE))
+            for w in range(0, n - 62, 64):
+                assert len(set(r[w:w + 64])) >= 49 - (w + 64 == n), (n, w)
+    assert 64 % 5 != 0 and len(clients) == 49
+    terms, clients, requests, period = K.slice_case(70000)
+    assert period == 1213 and 35000 % period == 1036
+    assert sum(len(q[2]) for q in requests[:35000]) % 16 != 0
+
+
 # ---- C ABI on a host-only engine ------------------------------------------------------
 def _create(e, arr, n):
     h = C.c_void_p()

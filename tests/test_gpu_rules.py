@@ -39,3 +39,54 @@ def test_random_names_and_rules_both_forms():
     assert np.array_equal(gb, eb)
     assert np.array_equal(gw, ew)
     assert (gb != gw).any()      # the '$' rule makes a difference on this set
+
+
+# ---- the bit words (one per 32 rules) and the block edges of n ----------------------
+@pytest.fixture(scope="module")
+def edge_case():
+    """257 names x 65 rules and both host answers, computed once; the tests take prefixes."""
+    import acl_cases as K
+    names, rules = K.rules_match_case()
+    assert (len(names), len(rules)) == (257, 65)
+    for s in K.RULES_SPECIAL:
+        assert s in names[:255] and s in rules
+    eb = np.array([[O.match(n, f) for f in rules] for n in names])
+    ew = np.array([[T.match(T.words(n), T.words(f)) for f in rules] for n in names])
+    assert (eb != ew).any()                       # the '$' rule makes a difference on this set
+    eb.setflags(write=False)
+    ew.setflags(write=False)
+    return names, rules, eb, ew
+
+
+@pytest.fixture(scope="module")
+def eng():
+    e = Engine(device=0)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+@pytest.mark.parametrize("r", [1, 31, 32, 33, 64, 65])
+def test_rule_word_and_block_edges(eng, edge_case, r, n):
+    names, rules, eb, ew = edge_case
+    for exp in (eb, ew):                          # the last rule's bit is set for some names and clear for others
+        assert 0 < exp[:255, r - 1].sum() < 255
+    gb = eng.rules_match(names[:n], rules[:r], dollar_rule=True)
+    gw = eng.rules_match(names[:n], rules[:r], dollar_rule=False)
+    assert gb.shape == gw.shape == (n, r)
+    assert np.array_equal(gb, eb[:n, :r])
+    assert np.array_equal(gw, ew[:n, :r])
+
+
+def test_a_names_own_hash_is_consumed_before_a_last_hash(eng):
+    """match([H|T1], [H|T2]) is tried before match(_, ['#'])
+    (src/emqx_topic.erl:76-81): the rule '#' does not match the name '#/a'."""
+    names = [b"#/a", b"#", b"a/#/b", b"a/#", b"a/b", b"+/#/a", b"$x/#/a"]
+    rules = [b"#", b"a/#", b"+/#", b"#/a", b"a/#/b", b"+/#/a", b"#/#"]
+    eb = np.array([[O.match(n, f) for f in rules] for n in names])
+    ew = np.array([[T.match(T.words(n), T.words(f)) for f in rules] for n in names])
+    assert not eb[0, 0] and not ew[0, 0] and eb[1, 0] and not ew[2, 1] and not eb[6, 0] and ew[6, 0]
+    assert [bool(x) for x in ew[:, 0]] == [False, True, True, True, True, True, True]
+    assert [bool(x) for x in ew[:, 1]] == [False, False, False, True, True, False, False]
+    assert np.array_equal(eng.rules_match(names, rules, dollar_rule=True), eb)
+    assert np.array_equal(eng.rules_match(names, rules, dollar_rule=False), ew)
