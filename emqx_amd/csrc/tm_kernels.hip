@@ -383,6 +383,130 @@ __device__ __forceinline__ uint32_t tag_sort(uint32_t k) {
     return k;
 }
 
+#ifndef TM_SORT_KPL
+#define TM_SORT_KPL 4   // tagged keys per lane of a row sort; 1: one key per lane, the code of rounds 7-11 (A/B builds)
+// (2 compiles -- 101 VGPRs -- and passes tests/test_gpu_sort_lanes.py; it was never measured: the fallback had 4 not fitted)
+#endif
+static_assert(TM_SORT_KPL == 1 || TM_SORT_KPL == 2 || TM_SORT_KPL == 4, "TM_SORT_KPL: 1, 2 or 4");
+// K tagged keys per lane.  Element e of a row sits in lane e / K of the row's
+// W / K lanes, register e % K, so a wave pass sorts 64 K / W rows and an
+// exchange at element distance < K is a v_min_u32 / v_max_u32 pair between two
+// of the lane's own registers.  The network is the all-ascending bitonic one:
+// the first step of the merge of KK elements compares e with its mirror e ^
+// (KK - 1), the others e with e ^ J (J = KK / 4 .. 1), and the lower element
+// always keeps the lower value -- no step has a direction that depends on the
+// lane, so the in-register steps carry no select (the standard form's merges
+// of 2 K and up alternate by lane and would need one per register).  A mirror
+// across lanes pairs register i with register K - 1 - i of lane l ^ (KK / K -
+// 1): one DPP (quad_perm / row_half_mirror / row_mirror) up to 16 lanes.  In
+// every lane step, lane l keeps the lower values iff its bit D (the distance,
+// or the mirror's upper bit) is clear: a compile-time mask.
+constexpr uint64_t lane_lo_mask(uint32_t d) {
+    uint64_t m = 0;
+    for (uint32_t l = 0; l < 64; ++l)
+        if ((l & d) == 0) m |= 1ull << l;
+    return m;
+}
+
+// the value of lane l ^ X, X = 2^n - 1
+template <uint32_t X>
+__device__ __forceinline__ uint32_t mirror_lane32_bc(uint32_t v) {
+    const int x = (int)v;
+    if constexpr (X == 1) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);
+    else if constexpr (X == 3) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x1B, 0xF, 0xF, true);
+    else if constexpr (X == 7) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x141, 0xF, 0xF, true);
+    else if constexpr (X == 15) return (uint32_t)__builtin_amdgcn_update_dpp(0, x, 0x140, 0xF, 0xF, true);
+    else if constexpr (X == 31) return mirror_lane32_bc<15>(xor_lane32(v, 16));
+    else return mirror_lane32_bc<15>(xor_lane32(xor_lane32(v, 32), 16));
+}
+
+// one step between lanes: distance D (MIRROR: partner l ^ (2 D - 1), registers reversed)
+template <uint32_t K, uint32_t D, bool MIRROR>
+__device__ __forceinline__ void kpl_lane_stage(uint32_t (&k)[K]) {
+    const bool keep_lo = __builtin_amdgcn_inverse_ballot_w64(lane_lo_mask(D));
+    uint32_t o[K];
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i) {
+        uint32_t lo, hi;
+        if constexpr (!MIRROR && D >= 16) {
+            // after the swap both lanes of a pair hold {own, partner} in {p[0], p[1]}
+            const auto p = D == 16 ? __builtin_amdgcn_permlane16_swap(k[i], k[i], false, false)
+                                   : __builtin_amdgcn_permlane32_swap(k[i], k[i], false, false);
+            lo = min(p[0], p[1]);
+            hi = max(p[0], p[1]);
+        } else {
+            uint32_t other;
+            if constexpr (MIRROR) other = mirror_lane32_bc<2 * D - 1>(k[K - 1 - i]);
+            else other = xor_lane32_bc(k[i], D);
+            lo = min(k[i], other);
+            hi = max(k[i], other);
+        }
+        o[i] = keep_lo ? lo : hi;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i) k[i] = o[i];
+}
+
+// the steps at distance J, J / 2 .. 1 of a merge
+template <uint32_t K, uint32_t J>
+__device__ __forceinline__ void kpl_clean(uint32_t (&k)[K]) {
+    if constexpr (J >= K) {
+        kpl_lane_stage<K, J / K, false>(k);
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < K; ++i) {
+            if (i & J) continue;
+            const uint32_t lo = min(k[i], k[i | J]), hi = max(k[i], k[i | J]);
+            k[i] = lo;
+            k[i | J] = hi;
+        }
+    }
+    if constexpr (J > 1) kpl_clean<K, J / 2>(k);
+}
+
+template <uint32_t K, uint32_t W, uint32_t KK = 2>
+__device__ __forceinline__ void kpl_sort(uint32_t (&k)[K]) {
+    if constexpr (KK > K) {
+        kpl_lane_stage<K, KK / (2 * K), true>(k);
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < K; ++i) {
+            const uint32_t p = i ^ (KK - 1);
+            if (i > p) continue;
+            const uint32_t lo = min(k[i], k[p]), hi = max(k[i], k[p]);
+            k[i] = lo;
+            k[p] = hi;
+        }
+    }
+    if constexpr (KK >= 4) kpl_clean<K, KK / 4>(k);
+    if constexpr (KK < W) kpl_sort<K, W, KK * 2>(k);
+}
+
+// One wave pass of the K-keys-per-lane sort: this lane holds elements K l ..
+// K l + K - 1 of the row {cr, pr, dr} (rv: it has one).  Keys are the staged
+// codes' high words with the element's index in the free bits, the padding
+// 0xFFFFFFFF; sorted place e then holds the entry that arrived as number
+// tag.
+template <bool CK, uint32_t K, uint32_t W, uint32_t STAGE>
+__device__ __forceinline__ void kpl_pass(const MatchArgs& a, const uint32_t* stg32, bool rv, uint32_t l, uint32_t cr,
+                                         uint32_t pr, uint32_t dr) {
+    uint32_t k[K];
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i) {
+        const uint32_t e = K * l + i;
+        k[i] = 0xFFFFFFFFu;   // padding: no code's top digit exceeds 4
+        if (rv && e < cr) k[i] = stg32[2 * CK_(pr + e, STAGE, 42) + 1] | e;
+    }
+    kpl_sort<K, W>(k);
+#pragma unroll
+    for (uint32_t i = 0; i < K; ++i) {
+        const uint32_t e = K * l + i;
+        if (rv && e < cr)
+            a.sfids[CK_((uint64_t)dr + e, a.sfids_cap, 44)] =
+                stg32[2 * CK_(pr + (k[i] & (W - 1)), STAGE, 43)] & (uint32_t)~KEY_MASK;
+    }
+}
+
 // Tile epilogue: sort the 64 rows of this wave and write their filter ids to
 // sfids[dst .. dst + c).  The rows are pulled into LDS a chunk of whole rows at
 // a time (at most STAGE elements), eight rows per batch of independent loads:
@@ -392,17 +516,74 @@ __device__ __forceinline__ uint32_t tag_sort(uint32_t k) {
 // wave-instruction, one element per lane, and sorted by a W-wide bitonic
 // network of __shfl_xor exchanges.  65..128 elements: rank count, two per lane.
 // `free` (wave-uniform): zero low bits of every staged code's high word; a
-// class with log2(W) <= free takes the tagged u32 network above.
+// class with log2(W) <= free takes the tagged u32 network above -- with
+// TM_SORT_KPL keys per lane its own classes, 64 K / W rows per pass.
 template <bool CK, class LT>
 __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool keep, uint32_t c, uint32_t pos,
                                              uint32_t dst, uint32_t free) {
     constexpr uint32_t STAGE = LT::STAGE;
-    const uint32_t lane = threadIdx.x;
+    uint32_t lane = threadIdx.x;
+#if TM_SORT_KPL > 1
+    // an empty asm re-defines the lane id here: every class derives a few
+    // values from it alone (its place in a row, its row in a pass), and as
+    // loop invariants of the wave's tile loop they were all hoisted out of it
+    // and held in VGPRs through the whole kernel (128 VGPRs and 18 spilled
+    // with both sets of classes; 104 with this line)
+    asm volatile("" : "+v"(lane));
+#endif
     const unsigned long long* stg = reinterpret_cast<const unsigned long long*>(L.q);
     if (keep && c == 1) a.sfids[CK_(dst, a.sfids_cap, 40)] = (uint32_t)(stg[CK_(pos, STAGE, 41)] & ~KEY_MASK);
+    uint32_t upto = 1;   // rows of up to this many entries are done (wave-uniform)
+#if TM_SORT_KPL > 1
+    // Tagged classes, K = TM_SORT_KPL keys per lane, while log2(W) <= free:
+    // rows of 2..K entries sort inside their own lane (no list, no shuffle, no
+    // barrier: the row's lane is the owner), rows of K + 1..4 K share a class
+    // of four lanes, then W = 8 K .. 128 at W / K lanes a row.  What is left
+    // (free too small for a class, or none at all) takes the loops below as
+    // before.
+    if (TM_TAGGED_SORT) {
+        constexpr uint32_t K = TM_SORT_KPL;
+        const uint32_t* stg32 = reinterpret_cast<const uint32_t*>(L.q);
+        if ((K >> free) <= 1) {
+            const bool mine = keep && c > 1 && c <= K;
+            if (__ballot(mine)) kpl_pass<CK, K, K, STAGE>(a, stg32, mine, 0u, c, pos, dst);
+            upto = K;
+        }
+#pragma unroll
+        for (uint32_t W = 4 * K; W <= 128; W <<= 1) {
+            if ((W >> free) > 1) break;   // log2(W) > free: this class and the wider ones sort u64
+            const bool mine = keep && c > (W == 4 * K ? K : W / 2) && c <= W;
+            upto = W;
+            const uint64_t m = __ballot(mine);
+            if (!m) continue;
+            const uint32_t nrows = __popcll(m);
+            if (mine) L.list[prefix_count(m)] = lane;
+            __syncthreads();
+            const uint32_t LPR = W / K, STEP = 64 / LPR;
+            for (uint32_t g = 0; g < nrows; g += STEP) {
+                const uint32_t r = g + lane / LPR;
+                const bool rv = r < nrows;
+                const uint32_t owner = rv ? L.list[r] : 0u;
+                const uint32_t cr = __shfl(c, owner, 64);
+                const uint32_t pr = __shfl(pos, owner, 64);
+                const uint32_t dr = __shfl(dst, owner, 64);
+                const uint32_t l = lane & (LPR - 1);
+                switch (W) {
+                case 8: kpl_pass<CK, K, 8, STAGE>(a, stg32, rv, l, cr, pr, dr); break;
+                case 16: kpl_pass<CK, K, 16, STAGE>(a, stg32, rv, l, cr, pr, dr); break;
+                case 32: kpl_pass<CK, K, 32, STAGE>(a, stg32, rv, l, cr, pr, dr); break;
+                case 64: kpl_pass<CK, K, 64, STAGE>(a, stg32, rv, l, cr, pr, dr); break;
+                default: kpl_pass<CK, K, 128, STAGE>(a, stg32, rv, l, cr, pr, dr); break;
+                }
+            }
+            __syncthreads();
+        }
+        if (!__ballot(keep && c > upto)) return;
+    }
+#endif
 #pragma unroll
     for (uint32_t W = 2; W <= 64; W <<= 1) {
-        const bool mine = keep && c > W / 2 && c <= W;
+        const bool mine = keep && c > upto && c > W / 2 && c <= W;
         const uint64_t m = __ballot(mine);
         if (!m) continue;
         const uint32_t nrows = __popcll(m);
@@ -417,7 +598,9 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
             const uint32_t cr = __shfl(c, owner, 64);
             const uint32_t pr = __shfl(pos, owner, 64);
             const uint32_t dr = __shfl(dst, owner, 64);
-            if (TM_TAGGED_SORT && (W >> free) <= 1) {   // log2(W) <= free
+            // log2(W) <= free (one key per lane only: with more, the classes
+            // above take the tagged rows and what reaches this loop sorts u64)
+            if (TM_TAGGED_SORT && TM_SORT_KPL == 1 && (W >> free) <= 1) {
                 const uint32_t* stg32 = reinterpret_cast<const uint32_t*>(L.q);
                 uint32_t k32 = 0xFFFFFFFFu;   // padding: no code's top digit exceeds 4
                 if (rv && e < cr) k32 = stg32[2 * CK_(pr + e, STAGE, 42) + 1] | e;
@@ -454,7 +637,7 @@ __device__ __forceinline__ void sort_classes(const MatchArgs& a, LT& L, bool kee
         __syncthreads();
     }
     {
-        const bool mine = keep && c > 64;
+        const bool mine = keep && c > 64 && c > upto;
         uint64_t m = __ballot(mine);
         while (m) {
             const uint32_t owner = (uint32_t)__builtin_ctzll(m);
