@@ -183,6 +183,33 @@ class WindowPrio(C.Structure):
                 ("lookup_kernel_ms", C.c_float), ("pad0", C.c_uint32)]
 
 
+TM_QMSG_EXPIRY, TM_QMSG_CLASS_SHIFT = 4, 4
+TM_DRAIN_BATCH_N = 1000
+TM_DRAIN_NO_ORDER = 0xFFFFFFFF
+TM_DRAIN_SEND0, TM_DRAIN_SEND, TM_DRAIN_KEPT, TM_DRAIN_EXPIRED, TM_DRAIN_COUNT = range(5)
+
+
+class DrainSession(C.Structure):
+    _fields_ = [("next_pkt_id", C.c_uint32), ("inflight_free", C.c_uint32)]
+
+
+class DrainIn(C.Structure):
+    _fields_ = [("sessions", C.POINTER(DrainSession)), ("q_off", C.c_void_p), ("qmsg", C.c_void_p),
+                ("created_ms", C.c_void_p), ("expiry_s", C.c_void_p), ("now_ms", C.c_int64),
+                ("n_sessions", C.c_uint32), ("pad0", C.c_uint32)]
+
+
+class DrainRecord(C.Structure):
+    _fields_ = [("next_pkt_id", C.c_uint32), ("n_send", C.c_uint32), ("n_send0", C.c_uint32),
+                ("n_expired", C.c_uint32)]
+
+
+class DrainOut(C.Structure):
+    _fields_ = [("disp", C.c_void_p), ("packet_ids", C.c_void_p), ("order", C.c_void_p), ("expiry_out", C.c_void_p),
+                ("records", C.POINTER(DrainRecord)), ("popped", C.c_void_p), ("totals", C.c_uint64 * TM_DRAIN_COUNT),
+                ("kernel_ms", C.c_float), ("pad0", C.c_uint32)]
+
+
 class BatchStats(C.Structure):
     _fields_ = [("topics", C.c_uint64), ("visits", C.c_uint64), ("hash_hits", C.c_uint64),
                 ("words", C.c_uint64), ("matches", C.c_uint64), ("slow_topics", C.c_uint64),
@@ -312,6 +339,7 @@ SIGNATURES = {
     "tm_ptable_classes": (C.c_uint32, [P, C.POINTER(C.c_uint16)]),
     "tm_batch_window_prio": (C.c_int, [P, P, C.POINTER(DeliverOpts), C.POINTER(WindowOpts), C.POINTER(WindowPrioOpts),
                                        C.POINTER(SessionWindow), C.POINTER(WindowPrio)]),
+    "tm_sessions_drain": (C.c_int, [P, C.POINTER(DrainIn), C.POINTER(DrainOut)]),
     "tm_match_routes_batch": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(Routes)]),
     "tm_trie_insert_many": (C.c_int, [P, P, P, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     "tm_trie_delete_many": (C.c_int, [P, P, P, C.c_uint32, C.POINTER(C.c_uint64)]),

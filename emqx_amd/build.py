@@ -18,7 +18,8 @@ HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
 TM_SOURCES = ["tm_engine.cpp", "tm_churn.cpp", "tm_upload.cpp", "tm_batch.cpp", "tm_async.cpp", "tm_pipeline.cpp",
-              "tm_fanout.cpp", "tm_shared.cpp", "tm_group.cpp", "tm_shard.cpp", "tm_acl.cpp", "tm_kernels.hip"]
+              "tm_fanout.cpp", "tm_shared.cpp", "tm_group.cpp", "tm_shard.cpp", "tm_acl.cpp", "tm_drain.cpp",
+              "tm_kernels.hip"]
 TM_HEADERS = ["tm_internal.hpp", "tm_buffers.hpp", "tm_engine_impl.hpp", os.path.join("..", "..", "include", "emqx_tm.h")]
 
 

@@ -861,6 +861,21 @@ struct Replica {
         // tm_rules_match
         DevBuf<uint32_t> d_rl;
     } tab;
+    // tm_sessions_drain (tm_drain.cpp): the call's inputs, scratch and results
+    // on the device, the pinned side of its small per-session arrays; kept
+    // between calls (calls on one engine are serialised by its mutex)
+    struct Drain {
+        DevBuf<uint8_t> d_qmsg, d_kind, d_disp;
+        DevBuf<int64_t> d_created;
+        DevBuf<uint32_t> d_expiry, d_expout, d_order, d_heads, d_chbase, d_cw, d_cbs, d_ctot, d_wdisp;
+        DevBuf<uint16_t> d_pid;
+        DevBuf<uint4> d_plan;
+        Mirror<uint32_t> off, popped;    // R + 1 up; R x 8 down
+        Mirror<uint2> sess;              // R up
+        Mirror<uint4> rec;               // R down
+        Mirror<unsigned long long> tot;  // the totals, then the out-of-range count
+        Event ev0, ev1;
+    } drain;
     size_t d_nslots = 0;
     uint64_t fbytes_uploaded = 0;
     size_t d_dict_n = 0;            // cuckoo slots on the device

@@ -581,6 +581,49 @@ struct PrioArgs {
 };
 static_assert(std::has_unique_object_representations_v<PrioArgs>, "PrioArgs has implicit padding");
 
+// The session drain (tm_sessions_drain): emqx_session:dequeue/1 over the
+// queued messages of a batch of sessions, listed per session in arrival order.
+// The host leaves the empty sessions out: a session here owns at least one
+// message, so a message's session is a count of heads as in the window.  Every
+// (wave, class) keeps three counts, one per PLANE: the counted messages (not
+// expired, QoS > 0), the QoS-0 messages not expired, the expired ones; a
+// column is plane * PRIO_CLASSES + class.
+constexpr uint32_t DRAIN_PLANES = 3;
+constexpr uint32_t DRAIN_COLS = DRAIN_PLANES * PRIO_CLASSES;
+constexpr uint32_t DRAIN_NDISP = 4;          // TM_DRAIN_COUNT
+constexpr uint32_t DRAIN_BATCH_N = 1000;     // TM_DRAIN_BATCH_N
+constexpr uint32_t DRAIN_EXPIRY = 4;         // TM_QMSG_EXPIRY
+constexpr uint32_t DRAIN_EXPIRED = 8;        // kind[]: qmsg with this bit for an expired message
+constexpr uint32_t DRAIN_RESERVED = 0x88;    // the bits of qmsg that must be 0
+struct DrainArgs {
+    const uint32_t* off;         // R + 1: the first message of session r; off[R] = Q
+    const uint2* sess;           // R x {next_pkt_id, inflight_free}
+    const uint8_t* qmsg;         // Q
+    const int64_t* created;      // Q, or null (then no message has DRAIN_EXPIRY)
+    const uint32_t* expiry;      // Q, or null
+    int64_t now_ms;
+    uint32_t Q, R, nwaves, ncls; // nwaves = 4 ceil(Q / INBOX_TILE); ncls: the highest class of the call + 1
+    uint32_t* heads;             // 2 ceil(Q / 64) + 2 words, zeroed: bit q = a session starts at message q
+    uint8_t* kind;               // Q: qmsg | DRAIN_EXPIRED (count writes it, classify reads it)
+    uint32_t* chbase;            // R x DRAIN_COLS: the counts of the head's wave before the head
+    uint32_t* cw;                // (nwaves + 1) x DRAIN_COLS: counts per wave, scanned in place (+ cbs)
+    uint32_t* cbs;               // scan blocks x DRAIN_COLS
+    uint32_t* ctot;              // DRAIN_COLS: the call's totals
+    // R x PRIO_CLASSES: {C(m) - scanned counted, U(m) - scanned not expired, scanned members at the class's
+    // first message, the session's members in the classes above}
+    uint4* plan;
+    uint8_t* disp;               // Q
+    uint16_t* pid;               // Q
+    uint32_t* order;             // Q
+    uint32_t* expiry_out;        // Q, or null
+    uint4* rec;                  // R: tm_drain_record
+    uint32_t* popped;            // R x PRIO_CLASSES
+    uint32_t* wdisp;             // nwaves x DRAIN_NDISP: messages per disposition and wave
+    unsigned long long* totals;  // DRAIN_NDISP
+    uint32_t* bad;               // indices out of range
+};
+static_assert(std::has_unique_object_representations_v<DrainArgs>, "DrainArgs has implicit padding");
+
 // Batched emqx_topic:match/2 (tm_rules_match): names x rules -> bitmap.
 struct RulesArgs {
     const uint32_t* nwords;   // name word ids (rule dictionary; unknown = W_UNKNOWN)
@@ -682,6 +725,10 @@ hipError_t launch_window(const WindowArgs& a, hipStream_t s);
 // window's own kernels with the per-class counts, scan, plan and classify
 hipError_t launch_prio_lookup(const PrioLookupArgs& a, hipStream_t s);
 hipError_t launch_window_prio(const WindowArgs& a, const PrioArgs& p, hipStream_t s);
+// drain: heads, the per-wave counts per class and plane, their two-level scan,
+// the plan per session (writes rec and popped), the disposition of every
+// message, the totals
+hipError_t launch_drain(const DrainArgs& a, hipStream_t s);
 hipError_t launch_fan_globalize(const FanArgs& a, hipStream_t s);   // block-relative moff -> global
 uint32_t fan_scan_tile();   // match entries per scan block
 uint32_t fan_fill_tile();   // deliveries per fill block

@@ -3714,6 +3714,313 @@ __global__ __launch_bounds__(INBOX_BLOCK) void tm_winp_classify(WindowArgs a, Pr
     }
 }
 
+// ------------------------------------------ the session drain (tm_sessions_drain)
+//
+// emqx_session:dequeue/1,3 (src/emqx_session.erl:389-413) over the messages a
+// batch of sessions holds in its mqueues, each session's listed in arrival
+// order.  emqx_mqueue:out/1 pops the highest class first and FIFO within a
+// class, so with C(m) = the session's counted messages (not expired, QoS > 0)
+// in the classes above m's plus those of m's class before m, m is popped iff
+// C(m) < Cnt: the fold has a closed form over per-(session, class) ranks, and
+// those are found as the priority window finds its class ranks, here for three
+// PLANES at once (counted, QoS 0 not expired, expired).  Same tiles: wave w of
+// tile t owns messages [4096 t + 1024 w, + 1024), 64 per round.
+//   heads     per session: its bit in `heads` (one atomicOr per session)
+//   count     per message: expired? -> kind; per wave and class: its members
+//             per plane, one ballot per class and one per plane and round;
+//             the lane on a session head stores the wave's counts before it
+//   scan      the waves' counts per column, two levels (tiles of
+//             PRIO_SCAN_TILE waves, then the tiles' sums)
+//   plan      per session: per class the three totals, the counted and the
+//             not-expired messages of the classes above -> the offsets that
+//             turn a scanned position into C(m) and U(m); the cut class; the
+//             record; popped of the classes above the cut (whole) and below
+//             it (nothing)
+//   classify  per message: C(m), U(m) -> disp, packet id, order, expiry_out;
+//             the lane holding the Cnt-th counted message knows its member
+//             index in the cut class: it writes that class's popped and what
+//             the record needs of it
+// No kernel waits for another workgroup, no thread loops over a session, no
+// atomics on the messages.
+
+// the heads before the wave's first message: off[r] < wbase, r < R
+__device__ __forceinline__ uint32_t drain_heads_before(const DrainArgs& a, uint32_t wbase) {
+    uint32_t lo = 0, hi = a.R;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.off[mid] < wbase) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+__device__ __forceinline__ uint64_t drain_head_mask(const DrainArgs& a, uint64_t q0) {   // q0: the round's first message
+    if (q0 >= a.Q) return 0ull;
+    const uint64_t i = (q0 >> 6) * 2;
+    return (uint64_t)a.heads[i] | (uint64_t)a.heads[i + 1] << 32;
+}
+// the scanned count of column col before wave gw (after the scan)
+__device__ __forceinline__ uint32_t drain_scanned(const DrainArgs& a, uint32_t gw, uint32_t col) {
+    return a.cw[(uint64_t)gw * DRAIN_COLS + col] + a.cbs[(uint64_t)(gw / PRIO_SCAN_TILE) * DRAIN_COLS + col];
+}
+// emqx_message:elapsed/1 (src/emqx_message.erl:296-297): max(0, Now - Since), exact for any two int64
+__device__ __forceinline__ uint64_t drain_elapsed(int64_t now, int64_t since) {
+    return since >= now ? 0ull : (uint64_t)now - (uint64_t)since;
+}
+__device__ __forceinline__ uint32_t drain_cnt(uint32_t inflight_free) {   // batch_n/1 (src/emqx_session.erl:680-684)
+    return inflight_free == 0xFFFFFFFFu ? DRAIN_BATCH_N : inflight_free;
+}
+// the plane of a kind byte: 0 counted, 1 QoS 0 and not expired, 2 expired
+__device__ __forceinline__ uint32_t drain_plane(uint32_t kind) {
+    return (kind & DRAIN_EXPIRED) ? 2u : ((kind & 3u) == 0u ? 1u : 0u);
+}
+
+__global__ __launch_bounds__(256) void tm_drain_heads(DrainArgs a) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint32_t o = a.off[r];
+    if (o < a.Q) atomicOr(a.heads + (o >> 5), 1u << (o & 31u));
+    else atomicAdd(a.bad, 1u);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_drain_count(DrainArgs a) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    uint32_t crun[DRAIN_COLS] = {};
+    if (wbase < a.Q) {
+        uint32_t hb = drain_heads_before(a, (uint32_t)wbase), bad = 0;
+#pragma unroll 1
+        for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+            const uint64_t q = wbase + r * 64 + lane;
+            const bool on = q < a.Q;
+            const uint64_t hm = drain_head_mask(a, wbase + r * 64);
+            const bool head = (hm >> lane) & 1ull;
+            const uint32_t ri = hb + inbox_mbcnt(hm) + (head ? 1u : 0u) - 1u;   // heads at or before me, less one
+            hb += (uint32_t)__popcll(hm);
+            const bool ok = on && ri < a.R;
+            if (on && !ok) ++bad;
+            uint32_t k = on ? a.qmsg[q] : 0u;
+            // is_expired/1 (src/emqx_message.erl:224-228); the product in 64 bits
+            if (on && (k & DRAIN_EXPIRY) && a.created && a.expiry &&
+                drain_elapsed(a.now_ms, a.created[q]) > (uint64_t)a.expiry[q] * 1000ull)
+                k |= DRAIN_EXPIRED;
+            if (on) a.kind[q] = (uint8_t)k;
+            const uint32_t plane = drain_plane(k), cls = (k >> 4) & 7u;
+            uint64_t pm[DRAIN_PLANES];
+#pragma unroll
+            for (uint32_t p = 0; p < DRAIN_PLANES; ++p) pm[p] = __ballot(ok && plane == p);
+            uint32_t hv[DRAIN_COLS];
+#pragma unroll
+            for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+                const uint64_t m = c < a.ncls ? __ballot(cls == c) : 0ull;   // (wave-uniform)
+#pragma unroll
+                for (uint32_t p = 0; p < DRAIN_PLANES; ++p) {
+                    const uint32_t col = p * PRIO_CLASSES + c;
+                    hv[col] = crun[col] + inbox_mbcnt(m & pm[p]);
+                    crun[col] += (uint32_t)__popcll(m & pm[p]);
+                }
+            }
+            if (ok && head) {
+                uint4* hbp = reinterpret_cast<uint4*>(a.chbase + (uint64_t)ri * DRAIN_COLS);
+#pragma unroll
+                for (uint32_t j = 0; j < DRAIN_COLS / 4; ++j)
+                    hbp[j] = make_uint4(hv[4 * j], hv[4 * j + 1], hv[4 * j + 2], hv[4 * j + 3]);
+            }
+        }
+        if (bad) atomicAdd(a.bad, bad);
+    }
+    if (lane == 0) {
+        uint4* wp = reinterpret_cast<uint4*>(a.cw + (uint64_t)gw * DRAIN_COLS);
+#pragma unroll
+        for (uint32_t j = 0; j < DRAIN_COLS / 4; ++j)
+            wp[j] = make_uint4(crun[4 * j], crun[4 * j + 1], crun[4 * j + 2], crun[4 * j + 3]);
+    }
+}
+static_assert(DRAIN_COLS % 4 == 0, "a count vector is whole uint4s");
+
+// Level one of the count scan, as tm_winp_scan_tiles: a block owns
+// PRIO_SCAN_TILE waves of one plane (blockIdx.y), thread (segment sg, class c)
+// 32 of them; exclusive in place, the tile's sums to cbs.
+__global__ __launch_bounds__(256) void tm_drain_scan_tiles(DrainArgs a) {
+    __shared__ uint32_t seg[32][PRIO_CLASSES];
+    const uint32_t c = threadIdx.x & 7u, sg = threadIdx.x >> 3, col = blockIdx.y * PRIO_CLASSES + c;
+    const uint32_t w0 = blockIdx.x * PRIO_SCAN_TILE + sg * 32u;
+    uint32_t sum = 0;
+    for (uint32_t i = 0; i < 32u; ++i)
+        if (w0 + i < a.nwaves) sum += a.cw[(uint64_t)(w0 + i) * DRAIN_COLS + col];
+    seg[sg][c] = sum;
+    __syncthreads();
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < sg; ++k) run += seg[k][c];
+    if (sg == 31u) a.cbs[(uint64_t)blockIdx.x * DRAIN_COLS + col] = run + sum;
+    for (uint32_t i = 0; i < 32u; ++i)
+        if (w0 + i < a.nwaves) {
+            const uint64_t at = (uint64_t)(w0 + i) * DRAIN_COLS + col;
+            const uint32_t v = a.cw[at];
+            a.cw[at] = run;
+            run += v;
+        }
+}
+
+// Level two: the tiles' sums, exclusive in place, and the call's totals (one
+// thread per column; at most 4096 tiles, as tm_winp_scan_sums).
+__global__ __launch_bounds__(64) void tm_drain_scan_sums(DrainArgs a, uint32_t nblocks) {
+    const uint32_t col = threadIdx.x;
+    if (col >= DRAIN_COLS) return;
+    uint32_t run = 0;
+    for (uint32_t k = 0; k < nblocks; ++k) {
+        const uint32_t v = a.cbs[(uint64_t)k * DRAIN_COLS + col];
+        a.cbs[(uint64_t)k * DRAIN_COLS + col] = run;
+        run += v;
+    }
+    a.ctot[col] = run;
+}
+
+__global__ __launch_bounds__(256) void tm_drain_plan(DrainArgs a) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= a.R) return;
+    const uint2 s = a.sess[r];
+    const uint32_t o = a.off[r], on = a.off[r + 1];
+    uint4* plan = a.plan + (uint64_t)r * PRIO_CLASSES;
+    uint32_t* popped = a.popped + (uint64_t)r * PRIO_CLASSES;
+    if (o >= a.Q || on > a.Q || on <= o) {   // (the host sends none such) nothing of this session is popped
+#pragma unroll
+        for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+            plan[c] = make_uint4(0xFFFFFFFFu, 0u, 0u, 0u);
+            popped[c] = 0u;
+        }
+        a.rec[r] = make_uint4(s.x, 0u, 0u, 0u);
+        if (o < a.Q) atomicAdd(a.bad, 1u);   // (tm_drain_heads counted the other case)
+        return;
+    }
+    const uint32_t wo = o / INBOX_WAVE_PAIRS, wn = on / INBOX_WAVE_PAIRS;
+    const bool last = r + 1 >= a.R;
+    const uint32_t cnt = drain_cnt(s.y);
+    uint32_t cumK = 0, cumU = 0, cumA = 0;   // counted / not expired / all messages of the classes above
+    uint32_t z_all = 0, x_all = 0;           // QoS 0 not expired / expired messages popped with whole classes
+    bool cut = cnt == 0;                     // the class holding the Cnt-th counted message is at or above c
+#pragma unroll
+    for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+        uint32_t base[DRAIN_PLANES], tot[DRAIN_PLANES];
+#pragma unroll
+        for (uint32_t p = 0; p < DRAIN_PLANES; ++p) {
+            const uint32_t col = p * PRIO_CLASSES + c;
+            base[p] = drain_scanned(a, wo, col) + a.chbase[(uint64_t)r * DRAIN_COLS + col];
+            const uint32_t next = last ? a.ctot[col] : drain_scanned(a, wn, col) + a.chbase[(uint64_t)(r + 1) * DRAIN_COLS + col];
+            tot[p] = next - base[p];
+        }
+        const uint32_t K = tot[0], Z = tot[1], X = tot[2];
+        // behind the cut nothing is popped: C(m) >= Cnt there whatever the offsets say, so they may stay exact
+        plan[c] = make_uint4(cumK - base[0], cumU - (base[0] + base[1]), base[0] + base[1] + base[2], cumA);
+        const bool whole = !cut && cumK + K < cnt;   // every message of the class has C(m) < Cnt
+        popped[c] = whole ? K + Z + X : 0u;          // the cut class: the lane of the Cnt-th counted message writes it
+        if (whole) { z_all += Z; x_all += X; }
+        else cut = true;
+        cumK += K;
+        cumU += K + Z;
+        cumA += K + Z + X;
+    }
+    const uint32_t nsend = min(cumK, cnt);
+    // cumK >= Cnt > 0: the lane of the Cnt-th counted message writes n_send0 and n_expired
+    a.rec[r] = make_uint4((s.x - 1u + nsend % 65535u) % 65535u + 1u, nsend, z_all, x_all);
+}
+
+__global__ __launch_bounds__(INBOX_BLOCK) void tm_drain_classify(DrainArgs a) {
+    const uint32_t lane = threadIdx.x & 63, gw = blockIdx.x * (INBOX_BLOCK / 64) + (threadIdx.x >> 6);
+    const uint64_t wbase = (uint64_t)gw * INBOX_WAVE_PAIRS;
+    if (gw >= a.nwaves) return;
+    uint32_t tot[DRAIN_NDISP] = {};
+    if (wbase < a.Q) {
+        uint32_t crun[DRAIN_COLS];
+#pragma unroll
+        for (uint32_t col = 0; col < DRAIN_COLS; ++col) crun[col] = drain_scanned(a, gw, col);
+        uint32_t hb = drain_heads_before(a, (uint32_t)wbase);
+#pragma unroll 1
+        for (uint32_t r = 0; r < INBOX_ROUNDS; ++r) {
+            const uint64_t q = wbase + r * 64 + lane;
+            const bool on = q < a.Q;
+            const uint64_t hm = drain_head_mask(a, wbase + r * 64);
+            const uint32_t ri = hb + inbox_mbcnt(hm) + (uint32_t)((hm >> lane) & 1ull) - 1u;
+            hb += (uint32_t)__popcll(hm);
+            const bool ok = on && ri < a.R;   // (tm_drain_count counted the others)
+            const uint32_t k = on ? a.kind[q] : 0u;
+            const uint32_t plane = drain_plane(k), cls = (k >> 4) & 7u;
+            uint64_t pm[DRAIN_PLANES];
+#pragma unroll
+            for (uint32_t p = 0; p < DRAIN_PLANES; ++p) pm[p] = __ballot(ok && plane == p);
+            uint32_t mine[DRAIN_PLANES] = {};   // the scanned counts of my class before me
+#pragma unroll
+            for (uint32_t c = 0; c < PRIO_CLASSES; ++c) {
+                const uint64_t m = c < a.ncls ? __ballot(cls == c) : 0ull;   // (wave-uniform)
+#pragma unroll
+                for (uint32_t p = 0; p < DRAIN_PLANES; ++p) {
+                    const uint32_t col = p * PRIO_CLASSES + c;
+                    if (cls == c) mine[p] = crun[col] + inbox_mbcnt(m & pm[p]);
+                    crun[col] += (uint32_t)__popcll(m & pm[p]);
+                }
+            }
+            const uint2 s = ok ? a.sess[ri] : make_uint2(1u, 0u);
+            const uint4 pl = ok ? a.plan[(uint64_t)ri * PRIO_CLASSES + cls] : make_uint4(0u, 0u, 0u, 0u);
+            const uint32_t cnt = drain_cnt(s.y);
+            const uint32_t C = mine[0] + pl.x, U = mine[0] + mine[1] + pl.y;
+            const uint32_t member = mine[0] + mine[1] + mine[2] - pl.z;   // my index among my class's messages
+            const bool pop = ok && C < cnt;
+            uint32_t d = 2u, id = 0u, ord = 0xFFFFFFFFu;                        // TM_DRAIN_KEPT
+            if (pop) {
+                if (plane == 2u) d = 3u;                                        // TM_DRAIN_EXPIRED
+                else {
+                    ord = U;
+                    if (plane == 1u) d = 0u;                                    // TM_DRAIN_SEND0
+                    else { d = 1u; id = (s.x - 1u + C % 65535u) % 65535u + 1u; }   // TM_DRAIN_SEND
+                }
+            }
+            if (on) {
+                a.disp[q] = (uint8_t)d;
+                a.pid[q] = (uint16_t)id;
+                a.order[q] = ord;
+                if (a.expiry_out) {
+                    uint32_t e = a.expiry ? a.expiry[q] : 0u;
+                    if (d < 2u && (k & DRAIN_EXPIRY) && a.created && a.expiry) {   // update_expiry/1 (src/emqx_message.erl:230-239)
+                        const uint64_t el = drain_elapsed(a.now_ms, a.created[q]);
+                        if (el > 0) e = (uint32_t)max<uint64_t>(1ull, (uint64_t)e - min<uint64_t>(el / 1000ull, e));
+                    }
+                    a.expiry_out[q] = e;
+                }
+            }
+            if (pop && plane == 0u && C + 1u == cnt) {   // the Cnt-th counted message: dequeue/3 stops behind it
+                a.popped[(uint64_t)ri * PRIO_CLASSES + cls] = member + 1u;
+                uint32_t* rec = reinterpret_cast<uint32_t*>(a.rec + ri);
+                rec[2] = U + 1u - cnt;                       // not expired and popped, less the counted ones
+                rec[3] = pl.w + member + 1u - (U + 1u);      // popped, less the not expired ones
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < DRAIN_NDISP; ++j) tot[j] += (uint32_t)__popcll(__ballot(on && d == j));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t j = 0; j < DRAIN_NDISP; ++j) a.wdisp[(uint64_t)gw * DRAIN_NDISP + j] = tot[j];
+    }
+}
+
+// the waves' disposition counts -> totals (one block), as tm_window_totals
+__global__ __launch_bounds__(256) void tm_drain_totals(DrainArgs a) {
+    __shared__ unsigned long long sh[4][DRAIN_NDISP];
+    unsigned long long v[DRAIN_NDISP] = {};
+    for (uint32_t i = threadIdx.x; i < a.nwaves; i += 256)
+#pragma unroll
+        for (uint32_t k = 0; k < DRAIN_NDISP; ++k) v[k] += a.wdisp[(uint64_t)i * DRAIN_NDISP + k];
+#pragma unroll
+    for (uint32_t k = 0; k < DRAIN_NDISP; ++k) {
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < DRAIN_NDISP) {
+        const uint32_t k = threadIdx.x;
+        a.totals[k] = sh[0][k] + sh[1][k] + sh[2][k] + sh[3][k];
+    }
+}
+
 // The global table: a slot holds ONE topic, {1 | 10 hash bits | length (13
 // bits) | byte offset (40 bits)}.  A claim probes from the hash's home; an
 // occupant with the same hash bits and length has its bytes compared, and
@@ -5139,6 +5446,20 @@ hipError_t launch_window_prio(const WindowArgs& a, const PrioArgs& p, hipStream_
     hipLaunchKernelGGL(tm_winp_plan, dim3(rblocks), dim3(256), 0, s, a, p);
     hipLaunchKernelGGL(tm_winp_classify, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a, p);
     hipLaunchKernelGGL(tm_window_totals, dim3(1), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_drain(const DrainArgs& a, hipStream_t s) {
+    if (!a.Q || !a.R || !a.nwaves) return hipGetLastError();
+    const uint32_t ntiles = a.nwaves / (INBOX_BLOCK / 64), rblocks = (a.R + 255) / 256;
+    const uint32_t nsb = (a.nwaves + PRIO_SCAN_TILE - 1) / PRIO_SCAN_TILE;
+    hipLaunchKernelGGL(tm_drain_heads, dim3(rblocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_drain_count, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tm_drain_scan_tiles, dim3(nsb, DRAIN_PLANES), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_drain_scan_sums, dim3(1), dim3(64), 0, s, a, nsb);
+    hipLaunchKernelGGL(tm_drain_plan, dim3(rblocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(tm_drain_classify, dim3(ntiles), dim3(INBOX_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(tm_drain_totals, dim3(1), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -55,6 +55,7 @@ void tm_engine::destroy() {
         R->scratch.release();
         R->tokb.release();
         R->tab = {};
+        R->drain = {};
         if (R->stream) (void)hipStreamDestroy(R->stream);
         delete R;
     }

@@ -206,3 +206,94 @@ def window_one_prio(deliveries, st, table, plens):
     assert all(r is not None for r in res)
     rec = (s["next_pkt_id"], len(s["inflight"]) - n0, sum(v[0] for v in per.values()), sum(v[1] for v in per.values()))
     return [(d, p, c) for (d, p), c in zip(res, cls)], rec, {p: tuple(v) for p, v in per.items()}
+
+
+# ---------------------------------------------------------------------------
+# The session drain (tm_sessions_drain): emqx_session:dequeue/1 over a queue
+# rebuilt from its messages in arrival order, and the same without the pqueue
+# for inputs too large for it.
+
+def qmsg_of(qos: int, cls: int = 0, flagged: bool = False) -> int:
+    """The qmsg byte of a queued message (include/emqx_tm.h)."""
+    return qos | (S.TM_QMSG_EXPIRY if flagged else 0) | cls << 4
+
+
+def drain_one(msgs, state, classes, now):
+    """emqx_session:dequeue/1 (src/emqx_session.erl:389-395) for one session.
+
+    msgs     [(qmsg byte, created_ms, expiry_s)] in arrival order, the order
+             in/2 saw them; the two numbers matter only with TM_QMSG_EXPIRY
+    state    {"next_pkt_id", "inflight_free"}
+    classes  the priorities of the queue's table, highest first (classes_of);
+             a message of class c has priority classes[c]
+    -> ([(disp, packet id or 0, order, expiry_out)] per message,
+        (next_pkt_id, n_send, n_send0, n_expired), popped per class (8 long))"""
+    from . import emqx_message as M
+    ptab = {c: p for c, p in enumerate(classes)}
+    mq = init({"max_len": 0, "store_qos0": True, "priorities": ptab})
+    for k, (b, created, expiry) in enumerate(msgs):
+        m = {"qos": b & 3, "topic": (b >> 4) & 7, "k": k, "timestamp": created, "headers": {}}
+        if b & S.TM_QMSG_EXPIRY:
+            m["headers"] = {"properties": {M.EXPIRY: expiry}}
+        d, mq = in_(m, mq)
+        assert d is None
+    free = state.get("inflight_free", S.TM_SESS_UNBOUNDED)
+    unb = free == S.TM_SESS_UNBOUNDED
+    s = S.new_session(state.get("next_pkt_id", 1), 0 if unb else free + 1, [] if unb else [0], mq)
+    n0 = len(s["inflight"])
+    publishes, expired = S.dequeue(s, now)
+    res = [(S.TM_DRAIN_KEPT, 0, S.TM_DRAIN_NO_ORDER, e) for _, _, e in msgs]
+    popped = [0] * TM_PRIO_MAX_CLASSES
+    for m in expired:                                                   # 'delivery.dropped.expired'
+        res[m["k"]] = (S.TM_DRAIN_EXPIRED, 0, S.TM_DRAIN_NO_ORDER, msgs[m["k"]][2])
+        popped[m["topic"]] += 1
+    n_send0 = 0
+    for place, (pid, m) in enumerate(publishes):
+        m1 = M.update_expiry(m, now)                                    # src/emqx_channel.erl:814
+        e = m1["headers"]["properties"][M.EXPIRY] if msgs[m["k"]][0] & S.TM_QMSG_EXPIRY else msgs[m["k"]][2]
+        res[m["k"]] = (S.TM_DRAIN_SEND0, 0, place, e) if pid is None else (S.TM_DRAIN_SEND, pid, place, e)
+        n_send0 += pid is None
+        popped[m["topic"]] += 1
+    return res, (s["next_pkt_id"], len(s["inflight"]) - n0, n_send0, len(expired)), popped
+
+
+def drain_flat(msgs, state, now):
+    """drain_one without the pqueue, for queues too long for its fold: one
+    deque per class, popped highest class first, the same clauses after the
+    pop.  Same arguments (no classes: a class is its own index) and result."""
+    from collections import deque
+    qs = [deque() for _ in range(TM_PRIO_MAX_CLASSES)]
+    for k, (b, _, _) in enumerate(msgs):                                # in/2: max_len 0, store_qos0
+        qs[(b >> 4) & 7].append(k)
+    free = state.get("inflight_free", S.TM_SESS_UNBOUNDED)
+    cnt = S.DEFAULT_BATCH_N if free == S.TM_SESS_UNBOUNDED else free    # batch_n/1
+    pid = state.get("next_pkt_id", 1)
+    res = [(S.TM_DRAIN_KEPT, 0, S.TM_DRAIN_NO_ORDER, e) for _, _, e in msgs]
+    popped = [0] * TM_PRIO_MAX_CLASSES
+    n_send = n_send0 = n_expired = place = 0
+    c = 0
+    while cnt != 0:                                                     # dequeue/3
+        while c < TM_PRIO_MAX_CLASSES and not qs[c]:
+            c += 1
+        if c == TM_PRIO_MAX_CLASSES:                                    # {empty, _Q}
+            break
+        k = qs[c].popleft()
+        popped[c] += 1
+        b, created, expiry = msgs[k]
+        flagged = bool(b & S.TM_QMSG_EXPIRY)
+        el = max(0, now - created) if flagged else 0                    # elapsed/1
+        if flagged and el > 1000 * expiry:                              # is_expired/1
+            res[k] = (S.TM_DRAIN_EXPIRED, 0, S.TM_DRAIN_NO_ORDER, expiry)
+            n_expired += 1
+            continue
+        e = max(1, expiry - el // 1000) if flagged and el > 0 else expiry   # update_expiry/1
+        if b & 3 == 0:                                                  # deliver_msg/2, QoS 0
+            res[k] = (S.TM_DRAIN_SEND0, 0, place, e)
+            n_send0 += 1
+        else:
+            res[k] = (S.TM_DRAIN_SEND, pid, place, e)
+            pid = 1 if pid == 0xFFFF else pid + 1                       # next_pkt_id/1
+            n_send += 1
+            cnt -= 1                                                    # acc_cnt/2
+        place += 1
+    return res, (pid, n_send, n_send0, n_expired), popped

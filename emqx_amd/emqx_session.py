@@ -259,3 +259,69 @@ def session_window(inboxes, states, defaults=None):
     -> {pid: ([(disp, packet id or 0)], (next_pkt_id, n_inflight, n_queued, n_dropped_old))}"""
     defaults = defaults or {}
     return {pid: window_one([d[2] & 3 for d in box], states.get(pid, defaults)) for pid, box in inboxes.items()}
+
+
+# ---------------------------------------------------------------------------
+# The dequeue after acks: what puback/2 and pubcomp/2 run once an inflight slot
+# is free, the tests' reference of tm_sessions_drain (with emqx_mqueue.drain_one
+# around it).
+#
+#   dequeue/1, dequeue/3  src/emqx_session.erl:389-409
+#   acc_cnt/2             src/emqx_session.erl:411-413
+#   batch_n/1             src/emqx_session.erl:680-684
+#   ?DEFAULT_BATCH_N      src/emqx_session.erl:153
+#
+# Here a session's mqueue is an emqx_mqueue value (a dict whose q is an
+# emqx_pqueue), and `now` stands for erlang:system_time(millisecond).
+
+DEFAULT_BATCH_N = 1000
+TM_DRAIN_BATCH_N = DEFAULT_BATCH_N
+(TM_DRAIN_SEND0, TM_DRAIN_SEND, TM_DRAIN_KEPT, TM_DRAIN_EXPIRED) = range(4)
+TM_DRAIN_NO_ORDER = 0xFFFFFFFF
+TM_QMSG_EXPIRY = 4
+
+
+def batch_n(session) -> int:
+    """batch_n/1 (:680-684)."""
+    if session["inflight_max"] == 0:                                   # :682
+        return DEFAULT_BATCH_N
+    return session["inflight_max"] - len(session["inflight"])         # :683
+
+
+def acc_cnt(msg, cnt: int) -> int:
+    """acc_cnt/2 (:411-413)."""
+    if msg["qos"] == 0:                                                # :412
+        return cnt
+    return cnt - 1                                                     # :413
+
+
+def dequeue_n(cnt: int, mq, now: int):
+    """dequeue/3 (:397-409) -> (Msgs in out order, the new queue, the expired
+    messages it threw away, in out order: inc_expired_cnt(delivery) once each)."""
+    from . import emqx_message as M
+    from . import emqx_mqueue as MQ
+    msgs, expired = [], []
+    while cnt != 0:                                                    # :397-398
+        r, mq1 = MQ.out(mq)                                            # :401
+        if r == "empty":                                               # :402
+            break
+        mq = mq1
+        msg = r[1]                                                     # :403
+        if M.is_expired(msg, now):                                     # :404-406
+            expired.append(msg)
+        else:                                                          # :407
+            cnt = acc_cnt(msg, cnt)
+            msgs.append(msg)
+    return msgs, mq, expired
+
+
+def dequeue(session, now: int):
+    """dequeue/1 (:389-395) -> (Publishes, the expired messages); the session
+    changes in place as deliver/2's does."""
+    from . import emqx_mqueue as MQ
+    if MQ.is_empty(session["mqueue"]):                                 # :390-391
+        return [], []
+    msgs, session["mqueue"], expired = dequeue_n(batch_n(session), session["mqueue"], now)   # :393
+    publishes, dropped = MQ.deliver(msgs, session)                     # :394
+    assert not dropped                                                 # the window had batch_n free slots
+    return publishes, expired

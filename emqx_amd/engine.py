@@ -1202,6 +1202,51 @@ class Engine:
             verdict[verdict == N.TM_ACL_NOMATCH] = N.TM_ACL_ALLOW if nomatch == "allow" else N.TM_ACL_DENY
         return verdict, rule
 
+    # ---- emqx_session:dequeue/1 with message expiry -----------------------------
+    def drain(self, sessions, queues, now_ms: int, expiry_out: bool = True):
+        """tm_sessions_drain: the dequeue after acks over a batch of sessions.
+
+        sessions  [(next_pkt_id, inflight_free)] (or an (n, 2) array);
+                  inflight_free TM_SESS_UNBOUNDED for a window of max size 0
+        queues    {"q_off": u64[n + 1], "qmsg": u8[Q], "created_ms": i64[Q] or
+                  None, "expiry_s": u32[Q] or None}: every session's messages
+                  in arrival order (see include/emqx_tm.h for qmsg's bits)
+        -> {"disp": u8[Q], "packet_ids": u16[Q], "order": u32[Q], "expiry_out":
+            u32[Q] or None, "records": u32[n, 4] (next_pkt_id, n_send, n_send0,
+            n_expired), "popped": u32[n, TM_PRIO_MAX_CLASSES]}
+        self.drain_info holds the totals per disposition and kernel_ms."""
+        sess = np.ascontiguousarray(np.asarray(sessions, dtype=np.uint32).reshape(-1, 2))
+        n = len(sess)
+        q_off = np.ascontiguousarray(queues["q_off"], dtype=np.uint64)
+        if len(q_off) != n + 1:
+            raise ValueError("q_off holds one offset more than there are sessions")
+        qmsg = np.ascontiguousarray(queues["qmsg"], dtype=np.uint8)
+        Q = len(qmsg)
+        if int(q_off[n]) != Q:
+            raise ValueError("q_off does not end at the number of messages")
+        created, expiry = queues.get("created_ms"), queues.get("expiry_s")
+        created = None if created is None else np.ascontiguousarray(created, dtype=np.int64)
+        expiry = None if expiry is None else np.ascontiguousarray(expiry, dtype=np.uint32)
+        if any(x is not None and len(x) != Q for x in (created, expiry)):
+            raise ValueError("created_ms / expiry_s hold one value per message")
+        res = {"disp": np.zeros(Q, np.uint8), "packet_ids": np.zeros(Q, np.uint16), "order": np.zeros(Q, np.uint32),
+               "expiry_out": np.zeros(Q, np.uint32) if expiry_out else None,
+               "records": np.zeros((n, 4), np.uint32), "popped": np.zeros((n, N.TM_PRIO_MAX_CLASSES), np.uint32)}
+        di, do = N.DrainIn(), N.DrainOut()
+        di.sessions = C.cast(sess.ctypes.data, C.POINTER(N.DrainSession))
+        di.q_off, di.qmsg = q_off.ctypes.data, qmsg.ctypes.data
+        di.created_ms = None if created is None else created.ctypes.data
+        di.expiry_s = None if expiry is None else expiry.ctypes.data
+        di.now_ms, di.n_sessions = int(now_ms), n
+        do.disp, do.packet_ids, do.order = res["disp"].ctypes.data, res["packet_ids"].ctypes.data, res["order"].ctypes.data
+        do.expiry_out = res["expiry_out"].ctypes.data if expiry_out else None
+        do.records = C.cast(res["records"].ctypes.data, C.POINTER(N.DrainRecord))
+        do.popped = res["popped"].ctypes.data
+        _acl_check(self.L, self.L.tm_sessions_drain(self.h, C.byref(di), C.byref(do)), "tm_sessions_drain")
+        self.drain_info = {"totals": dict(zip(("send0", "send", "kept", "expired"), (int(x) for x in do.totals))),
+                           "kernel_ms": float(do.kernel_ms)}
+        return res
+
     # ---- bulk load / filter-sharded mode -----------------------------------
     def insert_many(self, filters, shard: int = 0, nshards: int = 1) -> int:
         """emqx_trie:insert/1 over a filter list; with nshards > 1 only this

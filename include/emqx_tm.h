@@ -615,7 +615,8 @@ TM_API int tm_batch_deliver(tm_engine* e, tm_batch* b, const tm_deliver_opts* op
  * P and holds zeros otherwise.
  * Not here: priority tables (tm_batch_window_prio, or TM_SESS_HOST), maybe_ack / maybe_nack of
  * shared deliveries (they enter the inboxes of an armed batch as plain
- * delivers, tm_batch_shared_mode), message expiry.
+ * delivers, tm_batch_shared_mode).  Message expiry acts when the queue is
+ * drained: tm_sessions_drain.
  * The call counts as a dispatch of the batch (pointer lifetime as
  * tm_batch_deliver).  The session table is uploaded per call: a second call
  * on the same waited batch with other sessions sees them.  Without
@@ -738,7 +739,8 @@ TM_API int tm_batch_window(tm_engine* e, tm_batch* b, const tm_deliver_opts* dop
  * (TM_SESS_HOST sessions are exempt from these four), a batch without a
  * device copy of its topic bytes.  TM_ENODEV on a host-only engine.
  * Not here: more than TM_PRIO_MAX_CLASSES classes, the group / sharded /
- * multi-process forms, message expiry, maybe_ack / maybe_nack. */
+ * multi-process forms, maybe_ack / maybe_nack.  Message expiry acts when the
+ * queue is drained: tm_sessions_drain. */
 #define TM_PRIO_INFINITY    0xFFFFu  /* the priority `infinity` */
 #define TM_PRIO_MAX_CLASSES 8u       /* classes of one table (distinct priorities + default) */
 #define TM_PRIO_MAX_TABLES  16u      /* tables of one tm_batch_window_prio call */
@@ -773,6 +775,113 @@ typedef struct {
 } tm_window_prio;
 TM_API int tm_batch_window_prio(tm_engine* e, tm_batch* b, const tm_deliver_opts* dopts, const tm_window_opts* wopts,
                                 const tm_window_prio_opts* popts, tm_session_window* out, tm_window_prio* pout);
+
+/* ---- session drain: dequeue after acks, message expiry ----------------- */
+/* What emqx_session:puback/2 and pubcomp/2 do once an inflight slot is free:
+ * dequeue/1 (src/emqx_session.erl:389-413) over the mqueue the host holds, for
+ * a batch of sessions, one disposition per queued message.  Stand-alone as
+ * tm_acl_check: caller-owned host arrays in and out, synchronous, serialised
+ * on the engine's mutex; it runs on the engine's first replica.
+ * in: session r is {next_pkt_id P, inflight_free F} (F = max size - size of
+ * the inflight window once the host took the acked ids out, batch_n/1 :680-684)
+ * and owns messages q_off[r] .. q_off[r + 1] of the message arrays, listed in
+ * ARRIVAL order -- the order emqx_mqueue:in/2 saw them, which is the order
+ * tm_batch_window_prio reported them TM_DISP_QUEUED with their pclass.  The
+ * priority order is worked out here, not by the host.  qmsg[m]: bits 0-1 the
+ * QoS, TM_QMSG_EXPIRY when the message's properties hold
+ * 'Message-Expiry-Interval', bits 4-6 its class (0 the highest, as
+ * tm_ptable_classes orders them; 0 for a session without a table); the other
+ * bits are 0.  created_ms[m] is #message.timestamp, expiry_s[m] the interval,
+ * now_ms erlang:system_time(millisecond) taken once for the call.
+ * Expiry (src/emqx_message.erl:224-228, 296-297): elapsed = max(0, now_ms -
+ * created_ms); a message with TM_QMSG_EXPIRY is expired iff elapsed >
+ * expiry_s * 1000, in 64 bits.  Without the flag it never is, whatever the two
+ * arrays hold for it.
+ * Out order (emqx_mqueue:out/1, src/emqx_mqueue.erl:170-176, over
+ * emqx_pqueue:out/1): the session's messages stably sorted by class.
+ * dequeue(Cnt, ...) with Cnt = F, or TM_DRAIN_BATCH_N for TM_SESS_UNBOUNDED
+ * (?DEFAULT_BATCH_N, :153): it pops in out order, throws expired messages
+ * away (:404-406), counts down on every other message of QoS > 0 (acc_cnt/2
+ * :411-413) and stops at 0 (:397-398) or at the end of the queue (:402).  A
+ * message is COUNTED when it is not expired and its QoS is above 0.  With
+ * C(m) = the session's counted messages in classes above m's plus those of
+ * m's class before m in arrival order, and U(m) the same over the messages
+ * not expired: m is popped iff C(m) < Cnt.  A QoS 0 or expired message behind
+ * the Cnt-th counted one stays (dequeue(0, ...) stops at once).
+ *   popped and expired -> TM_DRAIN_EXPIRED ('delivery.dropped.expired')
+ *   popped, QoS 0      -> TM_DRAIN_SEND0, packet id 0 (deliver_msg/2 :440-441)
+ *   popped, counted    -> TM_DRAIN_SEND, packet id ((P - 1 + C(m) mod 65535)
+ *                         mod 65535) + 1 (:453-456, next_pkt_id/1 :665-669);
+ *                         the window has Cnt free slots, so nothing is queued
+ *                         again
+ *   not popped         -> TM_DRAIN_KEPT
+ * order[m] = U(m) for a TM_DRAIN_SEND / TM_DRAIN_SEND0 message, its place in
+ * the session's publish list (deliver/3 :429-438); TM_DRAIN_NO_ORDER
+ * otherwise.  expiry_out[m] (the array may be NULL) is what
+ * emqx_message:update_expiry/1 leaves in a sent message that has the flag
+ * (src/emqx_channel.erl:814, src/emqx_message.erl:230-239): max(1, expiry_s -
+ * elapsed div 1000) when elapsed > 0, else expiry_s; for every other message
+ * the input value (0 when expiry_s is NULL).
+ * records[r] = {the new next_pkt_id ((P - 1 + n_send mod 65535) mod 65535) + 1,
+ * n_send, n_send0, n_expired}; popped[r * TM_PRIO_MAX_CLASSES + c] = how many
+ * messages to take off the front of class c of the queue the host holds,
+ * their sum n_send + n_send0 + n_expired.  Cnt = 0 or an empty queue
+ * (is_empty/1 :390-391): nothing is popped, next_pkt_id stays.  totals[] are
+ * the messages per disposition; kernel_ms the device time (HIP events) of the
+ * drain kernels only.
+ * TM_EINVAL + tm_last_error(): NULL in or out; n_sessions > 0 with NULL
+ * sessions, q_off, records or popped; Q = q_off[n_sessions] > 0 with NULL
+ * qmsg, disp, packet_ids or order; a next_pkt_id outside 1..65535; offsets not
+ * monotone or not starting at 0; Q >= 2^32; QoS 3; a reserved bit of qmsg or
+ * pad0 set; a message with
+ * TM_QMSG_EXPIRY while created_ms or expiry_s is NULL.  All of them are found
+ * before anything runs, on a host-only engine too; then TM_ENODEV on a
+ * host-only engine.  TM_EIO + tm_last_error() if a kernel met an index past Q
+ * or n_sessions.  n_sessions = 0 is TM_OK with zero totals.
+ * Not here: retry/1 over the inflight window, maybe_ack / maybe_nack, more
+ * than TM_PRIO_MAX_CLASSES classes, device-pointer outputs, the group /
+ * sharded forms, a split over replicas. */
+#define TM_QMSG_EXPIRY     4u           /* qmsg: the message has a Message-Expiry-Interval */
+#define TM_QMSG_CLASS_SHIFT 4u          /* qmsg: bits 4-6 the class */
+#define TM_DRAIN_BATCH_N   1000u        /* ?DEFAULT_BATCH_N: Cnt of a window of max size 0 */
+#define TM_DRAIN_NO_ORDER  0xFFFFFFFFu  /* order[] of a message that is not sent */
+#define TM_DRAIN_SEND0     0u  /* QoS 0: sent with packet id `undefined` */
+#define TM_DRAIN_SEND      1u  /* packet id assigned, inflight */
+#define TM_DRAIN_KEPT      2u  /* still in the mqueue */
+#define TM_DRAIN_EXPIRED   3u  /* popped and thrown away: 'delivery.dropped.expired' */
+#define TM_DRAIN_COUNT     4u
+typedef struct {
+    uint32_t next_pkt_id;   /* 1..65535 */
+    uint32_t inflight_free; /* max size - size of the inflight window, or TM_SESS_UNBOUNDED */
+} tm_drain_session;
+typedef struct {
+    const tm_drain_session* sessions;   /* n_sessions */
+    const uint64_t*         q_off;      /* n_sessions + 1, monotone from 0; q_off[n_sessions] = Q < 2^32 */
+    const uint8_t*          qmsg;       /* Q */
+    const int64_t*          created_ms; /* Q; may be NULL when no message has TM_QMSG_EXPIRY */
+    const uint32_t*         expiry_s;   /* Q; may be NULL when no message has TM_QMSG_EXPIRY */
+    int64_t                 now_ms;
+    uint32_t                n_sessions;
+    uint32_t                pad0;       /* 0 */
+} tm_drain_in;
+typedef struct {
+    uint32_t next_pkt_id;   /* the new value */
+    uint32_t n_send;        /* TM_DRAIN_SEND messages: they enter the inflight window */
+    uint32_t n_send0;       /* TM_DRAIN_SEND0 messages */
+    uint32_t n_expired;     /* TM_DRAIN_EXPIRED messages */
+} tm_drain_record;
+typedef struct {
+    uint8_t*         disp;        /* Q: TM_DRAIN_* */
+    uint16_t*        packet_ids;  /* Q: 0 unless disp is TM_DRAIN_SEND */
+    uint32_t*        order;       /* Q */
+    uint32_t*        expiry_out;  /* Q, or NULL: not wanted */
+    tm_drain_record* records;     /* n_sessions */
+    uint32_t*        popped;      /* n_sessions x TM_PRIO_MAX_CLASSES */
+    uint64_t         totals[TM_DRAIN_COUNT];   /* messages per disposition */
+    float            kernel_ms;   /* device time of the drain kernels only */
+    uint32_t         pad0;
+} tm_drain_out;
+TM_API int tm_sessions_drain(tm_engine* e, const tm_drain_in* in, tm_drain_out* out);
 
 /* ---- shared subscriptions: emqx_shared_sub dispatch on the device ------ */
 /* The ?SHARED_SUBS bag ({Group, Topic} -> SubPid, src/emqx_shared_sub.erl:
